@@ -17,9 +17,20 @@ fixed as N grows).  Rank 0 prints ONE JSON line.
                      beside it in "strong": alone, and pipelined with the fill (column blocks are exchanged as the
                      kernels finish them, plonky2-ecdsa_amd/dist.py ColumnAssembly) -> "value_with_allgather".
                      --compact assembles the compact container instead (28 % fewer bytes over xGMI).
-  N > 1, default (weak) mode: the line ALSO carries that "strong" object -- the same measurements on ONE global batch of
-                     2^16 after the timed weak region -- so that whichever way the driver launches N ranks, the
-                     metric's literal configuration is on the line (--no-strong-leg skips it).
+  N > 1, default (weak) mode, with --full: the line ALSO carries that "strong" object -- the same measurements on ONE
+                     global batch of 2^16 after the timed weak region -- so that whichever way the driver launches N
+                     ranks, the metric's literal configuration is on the line (--no-strong-leg skips it).
+
+  --dump-outputs DIR after the timed steps, write what the last step computed as DIR/<name>.npy (float64; a u64 column
+                     splits exactly into its two 32-bit halves): the columns of 32 signatures picked with a fixed seed
+                     (columns_lo32 / columns_hi32, shape (columns, 32); --compact: narrow / wide_lo32 / wide_hi32), and
+                     the err and valid flags of the whole batch.  At most 43 MB; rank 0 only.  Inputs are seeded, so two
+                     builds can be compared output for output.
+
+A plain run (no --full) sets up, warms up, times --steps steps and prints the line with the objects that come from those
+steps: phase_ms_per_step, whole_fill, roofline, roofline_k_expand, roofline_k_expand_fb_run, median_step_ms.  The
+objects below that take runs of their own (roofline_limb_split, cpu_baseline*, checked_vs_oracle, p256_verify) and the
+weak mode's "strong" object are only measured with --full.
 
 Extra objects on the line:
   roofline     the dominant kernel, k_expand_runs (the MSM double/double/conditional-add loop: 59 495 of the
@@ -38,8 +49,8 @@ Extra objects on the line:
                host cores of this box.  kind "port": the Rust reference cannot be built offline.
   cpu_baseline_optimised   the same C code with Montgomery batch inversion across lock-step groups of 256
                signatures (BASELINE.md section 2 variant b): the baseline a careful CPU implementation would set.
-  checked_vs_oracle   signatures of the LAST timed output buffer compared column by column with the C oracle (default:
-               every signature of the batch, after the timed region).
+  checked_vs_oracle   signatures of the LAST timed output buffer compared column by column with the C oracle (--full
+               default: every signature of the batch, after the timed region; --check K asks for it in any run).
   p256_verify  (N = 1) the widened path on the same line: verify_p256_message_circuit (gadgets/ecdsa.rs:55-78) as a curve
                program, batch 2^16, 115 557 columns per fill: fills/s (median of 5 synchronous calls), whole-fill share of
                the HBM peak, and the expansion kernels' share from the library's HIP-event pairs.  Outside the timed
@@ -269,6 +280,31 @@ def strong_shape(p2e, torch, dist, args, world, rank, dev, dev_index, backend, c
     return out
 
 
+DUMP_SEED, DUMP_SIGNATURES = 20261015, 32
+
+
+def dump_outputs(out_dir, torch, n, mats, err, valid):
+    """--dump-outputs: the output matrices of one fill restricted to a seeded sample of signatures (every column), and
+    the flags of the whole batch.  ``mats``: name -> (columns, >= n) int32 / int64 device matrix.  Every value is
+    written as float64, which holds a 32-bit word exactly: 64-bit columns go out as their low and high halves."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SIGNATURES), replace=False))
+    idx = torch.from_numpy(sample).to(mats[next(iter(mats))].device)
+    arrays = {"err": err.cpu().numpy().astype(np.float32), "valid": valid.cpu().numpy().astype(np.float32)}
+    for name, m in mats.items():
+        got = m.index_select(1, idx).cpu().numpy()
+        if got.dtype == np.int32:
+            arrays[name] = got.view(np.uint32).astype(np.float64)
+        else:
+            got = got.view(np.uint64)
+            arrays[name + "_lo32"] = (got & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            arrays[name + "_hi32"] = (got >> np.uint64(32)).astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def pmc_traffic():
     """HBM bytes per k_expand launch from the committed rocprofv3 PMC summary, if any."""
     best = None
@@ -294,8 +330,14 @@ def main():
     ap.add_argument("--no-strong-leg", action="store_true",
                     help="N>1, weak mode: skip the extra 'strong' object (one global batch of 2^k split over the ranks + assembly)")
     ap.add_argument("--no-limb-split", action="store_true", help="skip the limb-split roofline leg")
-    ap.add_argument("--check", type=int, default=1 << 16,
-                    help="signatures of the last output buffer compared with the oracle, every column (default: the whole batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own: oracle check of the whole batch, limb-split roofline, "
+                         "CPU baselines, P-256 verifier, the strong object at N > 1 (the --no-* options skip single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (see the top of this file)")
+    ap.add_argument("--check", type=int, default=None,
+                    help="signatures of the last output buffer compared with the oracle, every column "
+                         "(default: the whole batch with --full, none otherwise)")
     ap.add_argument("--allgather-cols", type=int, default=0,
                     help="N>1 only: after the timed region, all-gather this many columns over RCCL and report GB/s")
     ap.add_argument("--ld-pad", type=int, default=16, help="column stride = batch + this many elements")
@@ -312,6 +354,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-p256", action="store_true", help="skip the P-256 verifier leg (SURVEY 8(f) rank 4 on the driver's line)")
     args = ap.parse_args()
+    if args.check is None:
+        args.check = 1 << 16 if args.full else 0
 
     import numpy as np
     import torch
@@ -444,6 +488,14 @@ def main():
                   "GBps_per_rank": round(g.numel() * 8 / tg / 1e9, 1)}
         del g
 
+    if rank == 0 and args.dump_outputs:
+        k = (issued[0] - 1) % depth                    # the buffer set the last timed step wrote
+        if args.compact:
+            mats = {"narrow": nar_bufs[k], "wide": wid_bufs[k]}
+        else:
+            mats = {"columns": cols_bufs[k]}
+        dump_outputs(args.dump_outputs, torch, n, mats, errs[k], valids[k])
+
     checked = None
     if rank == 0 and args.check > 0 and args.compact:
         # the compact container of THIS run against the oracle: sampled signatures, every column
@@ -481,7 +533,7 @@ def main():
             checked = int(len(sample))
 
     strong = None
-    if world > 1 and (args.scaling == "strong" or not args.no_strong_leg):
+    if world > 1 and (args.scaling == "strong" or (args.full and not args.no_strong_leg)):
         # free this leg's output buffers first: the assembled tensor is another (world, cols, ld) matrix
         keep_ms = elapsed / args.steps * 1e3 if (args.scaling == "strong" and depth == 1) else None
         cols_bufs.clear()
@@ -496,7 +548,7 @@ def main():
             strong = {"error": f"{type(e).__name__}: {e}"}
 
     limb_split = None
-    if rank == 0 and not args.no_limb_split:
+    if rank == 0 and args.full and not args.no_limb_split:
         # the 29-bit limb-split kernel of the north star (>= 40 % of HBM peak asked): 2^26 packed values -> 9 limb columns
         m = 1 << 26
         packed = torch.randint(0, 256, (m, 32), dtype=torch.uint8, device=dev)
@@ -589,9 +641,9 @@ def main():
             line["strong"] = strong
             if args.scaling == "strong" and "value_with_allgather" in strong:
                 line["value_with_allgather"] = strong["value_with_allgather"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"], line["cpu_baseline_optimised"] = cpu_baseline(p2e, seed=4)
-        if world == 1 and not args.no_p256 and not args.compact and args.batch_log2 == 16:
+        if world == 1 and args.full and not args.no_p256 and not args.compact and args.batch_log2 == 16:
             try:
                 cols_bufs.clear()
                 torch.cuda.empty_cache()

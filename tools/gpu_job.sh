@@ -42,7 +42,7 @@ for job in "$@"; do
               run "py_${script%.py}${sargs:+_}${sargs//[^A-Za-z0-9_]/_}" 1100 python "tools/$script" ${sargs//+/ } || exit 1 ;;
     ranks)    # ranks:N[:ARGS]  bench.py on N gloo ranks sharing the one GPU (rehearsal of the N>1 code paths; ARGS as for bench)
               nr=${arg%%:*}; rargs=""; [[ "$arg" == *:* ]] && rargs=${arg#*:}
-              run "ranks_${nr}${rargs:+_}${rargs//[^A-Za-z0-9_]/_}" 900 env P2E_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node "$nr" --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus "$nr" --steps 4 --warmup 1 --check 64 ${rargs//+/ } || exit 1 ;;
+              run "ranks_${nr}${rargs:+_}${rargs//[^A-Za-z0-9_]/_}" 900 env P2E_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node "$nr" --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus "$nr" --steps 4 --warmup 1 --check 64 ${rargs//+/ } || exit 1 ;;
     *)        echo "unknown job $job"; exit 2 ;;
     esac
 done
