@@ -329,7 +329,8 @@ long p2e_schedule_num_cols(int program);
  *   c < 2^29                     first limb column c of the witness matrix (limbs in consecutive columns)
  *   P2E_SRC_AUX | c              column c of the built-in-generator matrix (a mul_biguint_by_bool product, a
  *                                random_access_curve_points selection: p2e_aux_witness_batch)
- *   P2E_SRC_INPUT | slot         a caller input: 0 pk.y, 1 pk.x, 2 msg (glv_mul: k), 3 r, 4 s (9-limb virtual targets)
+ *   P2E_SRC_INPUT | slot         a caller input: 0 pk.y, 1 pk.x, 2 msg (glv_mul: k), 3 r, 4 s (9-limb virtual targets);
+ *                                the MSM curve program also 5 q.x, 6 q.y
  *   P2E_SRC_CONST | id           a circuit constant (constant_biguint, gadgets/biguint.rs:165-175): p2e_wiring_const
  * num_limbs[k]: limbs that target has (constants: convert_base's count, zero has none -- quirk Q5; k1, k2: 5).
  * range_check: the gadget's range_check flag (one more cmp_biguint in its constraint block, nonnative.rs:180-190). */
@@ -352,6 +353,8 @@ int p2e_wiring_const(uint32_t id, uint8_t out32[32]);
  *   P2E_CP_WINDOWED_MUL  curve_scalar_mul_windowed(p, n, true)  gadgets/curve_windowed_mul.rs:131-173   98 185 columns
  *   P2E_CP_SCALAR_MUL    curve_scalar_mul(p, n, true)           gadgets/curve.rs:245-285               139 354 columns
  *   P2E_CP_VERIFY        verify_p256_message_circuit            gadgets/ecdsa.rs:55-78 (P-256 only)    115 557 columns
+ *   P2E_CP_MSM           curve_msm_circuit(p, q, n, m)          gadgets/curve_msm.rs:21-79             112 309 columns
+ *   P2E_CP_FIXED_BASE_MUL  fixed_base_curve_mul_circuit(base, n)  gadgets/curve_fixed_base.rs:18-66     16 797 columns
  * Both gadgets blind with a point drawn by rand() WHILE THE CIRCUIT IS BUILT (precompute_window
  * gadgets/curve_windowed_mul.rs:57, curve_scalar_mul gadgets/curve.rs:253), so their witness depends on the build:
  * a program object stands for one built circuit and takes that point (canonical affine coordinates, 32 little-endian
@@ -364,12 +367,23 @@ int p2e_wiring_const(uint32_t id, uint8_t out32[32]);
  * [selected x (9), selected y (9), is_zero, should_add, not_b, sum.x*b, sum.y*b, p1.x*not_b, p1.y*not_b], 6 bit split,
  * 7 bit of curve_scalar_mul [not_bit, sum.x*bit, result.x*not_bit, sum.y*bit, result.y*not_bit]),
  * p2e_curve_program_gate_internal_batch and p2e_curve_program_ux_witness_batch (+ _ux_describe).
- * A program belongs to the context's device; u64 column matrix only for the fill. */
+ * A program belongs to the context's device; u64 column matrix only for the fill.
+ * The MSM program has full 9-limb scalars (131 two-bit digits, MSB first) and no per-build randomness: its blinding point
+ * is KeccakHash::<32>(F::ZERO) * G of its curve, so the point arguments of p2e_curve_program_create are ignored (may be
+ * NULL) and its witness is a pure function of (p, q, n, m).  Fill: p2e_curve_msm_witness[_compact]_batch; aux kinds 1
+ * split2 (261 bits + 131 digits per scalar) and 3 MSM digit [index, selected x (9), selected y (9), is_zero, should_add,
+ * not_b, sum.x*b, sum.y*b, p1.x*not_b, p1.y*not_b]; its wiring reads q through P2E_SRC_INPUT slots 5 (q.x) and 6 (q.y).
+ * The constraint-block pass does not take the MSM program yet (p2e_curve_program_ux_witness_batch has no slot for q:
+ * it returns P2E_E_INVALID).
+ * The fixed-base program multiplies a CONSTANT base: the point arguments of p2e_curve_program_create are that base
+ * (canonical, on the program's curve); its fill is p2e_curve_mul_witness[_compact]_batch with px32 = py32 = NULL. */
 #define P2E_CURVE_SECP256K1 0
 #define P2E_CURVE_P256 1
 #define P2E_CP_WINDOWED_MUL 1
 #define P2E_CP_SCALAR_MUL 2
 #define P2E_CP_VERIFY 3
+#define P2E_CP_MSM 4
+#define P2E_CP_FIXED_BASE_MUL 5
 typedef struct p2e_curve_program p2e_curve_program;
 int p2e_curve_program_create(p2e_ctx *ctx, int kind, int curve, const uint8_t *blind_x32, const uint8_t *blind_y32,
                              p2e_curve_program **out);
@@ -384,7 +398,8 @@ int p2e_curve_program_const(const p2e_curve_program *prog, uint32_t id, uint8_t 
 long p2e_curve_program_num_gate_cols(const p2e_curve_program *prog);
 long p2e_curve_program_num_ux_cols(const p2e_curve_program *prog);
 long p2e_curve_program_ux_describe(const p2e_curve_program *prog, p2e_ux_desc *out, size_t cap);
-/* inputs as for the program's fill (multiplication programs: the scalar in msg32, r32 = s32 = NULL) */
+/* inputs as for the program's fill (multiplication programs: the scalar in msg32, r32 = s32 = NULL; the MSM program: n in
+ * msg32, m in r32, s32 and the points may be NULL; the fixed-base program: the scalar in msg32, everything else may be NULL) */
 /* the wire map of p2e_wire_map_create for this program's matrices (then p2e_assemble_wires / p2e_wire_map_destroy) */
 int p2e_curve_program_wire_map_create(p2e_ctx *ctx, const p2e_curve_program *prog, const p2e_wire_map_entry *entries,
                                       size_t count, uint32_t num_wires, uint32_t degree, p2e_wire_map **out);
@@ -398,9 +413,17 @@ long p2e_curve_program_ux_witness_batch(p2e_ctx *ctx, const p2e_curve_program *p
                                         size_t ld, const uint64_t *aux, size_t ld_aux, void *ux, int ux_u32, size_t ld_ux, size_t n,
                                         uint8_t *err);
 /* replaces the run_once bodies of every generator curve_scalar_mul_windowed / curve_scalar_mul registers for a batch
- * of (point, scalar) pairs; cols[num_cols][ld].  valid: always 1 unless flagged (the gadgets connect nothing). */
+ * of (point, scalar) pairs; cols[num_cols][ld].  valid: always 1 unless flagged (the gadgets connect nothing).
+ * The fixed-base program (P2E_CP_FIXED_BASE_MUL) takes the scalars alone: px32 = py32 = NULL (ignored if given); the
+ * other two kinds fail with P2E_E_INVALID on a NULL point. */
 long p2e_curve_mul_witness_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint8_t *px32, const uint8_t *py32,
                                  const uint8_t *k32, uint64_t *cols, size_t n, size_t ld, uint8_t *err, uint8_t *valid);
+/* curve_msm_circuit(p, q, n, m) = n p + m q for a batch (P2E_CP_MSM programs only): p in (px32, py32), q in (qx32, qy32),
+ * n32 / m32 32-byte little-endian scalars (as k32 above); cols[num_cols][ld].  valid: 1 unless flagged; exceptional
+ * additions (p = +-q, n = m = 0, ...) set P2E_ERR_INVERSE_OF_ZERO on that element. */
+long p2e_curve_msm_witness_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint8_t *px32, const uint8_t *py32,
+                                 const uint8_t *qx32, const uint8_t *qy32, const uint8_t *n32, const uint8_t *m32, uint64_t *cols,
+                                 size_t n, size_t ld, uint8_t *err, uint8_t *valid);
 /* the same for verify_p256_message_circuit; valid = curve_assert_valid's connect and r == x both hold */
 long p2e_p256_verify_witness_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint8_t *msg32, const uint8_t *r32,
                                    const uint8_t *s32, const uint8_t *pkx32, const uint8_t *pky32, uint64_t *cols, size_t n,
@@ -417,6 +440,10 @@ long p2e_p256_verify_witness_compact_batch(p2e_ctx *ctx, const p2e_curve_program
                                            const uint8_t *s32, const uint8_t *pkx32, const uint8_t *pky32, uint32_t *narrow,
                                            size_t ld_narrow, uint64_t *wide, size_t ld_wide, size_t n, uint8_t *err,
                                            uint8_t *valid);
+long p2e_curve_msm_witness_compact_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint8_t *px32, const uint8_t *py32,
+                                         const uint8_t *qx32, const uint8_t *qy32, const uint8_t *n32, const uint8_t *m32,
+                                         uint32_t *narrow, size_t ld_narrow, uint64_t *wide, size_t ld_wide, size_t n, uint8_t *err,
+                                         uint8_t *valid);
 long p2e_curve_program_compact_layout(const p2e_curve_program *prog, uint32_t *col_map, size_t cap, uint32_t *num_narrow,
                                       uint32_t *num_wide);
 /* the P-256 verifier's verdict alone (the counterpart of p2e_ecdsa_verify_batch; native: curve/ecdsa.rs:42-62

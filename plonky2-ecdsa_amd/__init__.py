@@ -48,8 +48,8 @@ GLV_MUL_GATE_COLS = 5621
 PROGRAM_VERIFY, PROGRAM_GLV_MUL = 0, 1
 # curve programs (include/p2e.h P2E_CURVE_* / P2E_CP_*)
 CURVE_SECP256K1, CURVE_P256 = 0, 1
-CP_WINDOWED_MUL, CP_SCALAR_MUL, CP_VERIFY = 1, 2, 3
-WINDOWED_MUL_COLS, SCALAR_MUL_COLS, P256_VERIFY_COLS = 98185, 139354, 115557
+CP_WINDOWED_MUL, CP_SCALAR_MUL, CP_VERIFY, CP_MSM, CP_FIXED_BASE_MUL = 1, 2, 3, 4, 5
+WINDOWED_MUL_COLS, SCALAR_MUL_COLS, P256_VERIFY_COLS, MSM_COLS, FIXED_BASE_MUL_COLS = 98185, 139354, 115557, 112309, 16797
 
 # every symbol include/p2e.h declares
 EXPORTS = (
@@ -70,6 +70,7 @@ EXPORTS = (
     "p2e_curve_program_aux_witness_batch", "p2e_curve_program_gate_internal_batch", "p2e_curve_program_ux_witness_batch",
     "p2e_curve_program_wire_map_create", "p2e_p256_verify_batch",
     "p2e_curve_mul_witness_compact_batch", "p2e_p256_verify_witness_compact_batch", "p2e_curve_program_compact_layout",
+    "p2e_curve_msm_witness_batch", "p2e_curve_msm_witness_compact_batch",
 )
 
 
@@ -307,14 +308,19 @@ def synth_signatures_curve(curve: int, seed: int, n: int, first: int = 0):
 
 
 class CurveProgram:
-    """One built circuit of curve_scalar_mul_windowed / curve_scalar_mul / verify_p256_message_circuit
-    (gadgets/curve_windowed_mul.rs:131-173, gadgets/curve.rs:245-285, gadgets/ecdsa.rs:55-78) on CURVE_SECP256K1 or
-    CURVE_P256.  ``blind`` = the point the gadget draws with rand() while the circuit is built, as (x, y) ints."""
+    """One built circuit of curve_scalar_mul_windowed / curve_scalar_mul / verify_p256_message_circuit /
+    curve_msm_circuit / fixed_base_curve_mul_circuit (gadgets/curve_windowed_mul.rs:131-173, gadgets/curve.rs:245-285,
+    gadgets/ecdsa.rs:55-78, gadgets/curve_msm.rs:21-79, gadgets/curve_fixed_base.rs:18-66) on CURVE_SECP256K1 or
+    CURVE_P256.  ``blind`` = the point the gadget draws with rand() while the circuit is built, as (x, y) ints;
+    CP_FIXED_BASE_MUL: ``base`` (or ``blind``) = the constant base; CP_MSM takes no point."""
 
-    def __init__(self, ctx, kind: int, curve: int, blind):
+    def __init__(self, ctx, kind: int, curve: int, blind=None, base=None):
         self._ctx, self.kind, self.curve = ctx, kind, curve
-        bx = np.frombuffer(int(blind[0]).to_bytes(32, "little"), np.uint8).copy()
-        by = np.frombuffer(int(blind[1]).to_bytes(32, "little"), np.uint8).copy()
+        pt = base if base is not None else blind
+        bx = by = None
+        if pt is not None:
+            bx = np.frombuffer(int(pt[0]).to_bytes(32, "little"), np.uint8).copy()
+            by = np.frombuffer(int(pt[1]).to_bytes(32, "little"), np.uint8).copy()
         h = C.c_void_p()
         rc = ctx._L.p2e_curve_program_create(ctx._h, C.c_int(kind), C.c_int(curve), _ptr(bx), _ptr(by), C.byref(h))
         if rc != 0:
@@ -377,9 +383,10 @@ class CurveProgram:
         return cols, err, valid, ld if ld is not None else _ld(cols)
 
     def mul_witness_batch(self, px, py, k, cols=None, err=None, valid=None, ld=None):
-        """(num_cols, n) columns of every generator the gadget registers for n (point, scalar) pairs."""
+        """(num_cols, n) columns of every generator the gadget registers for n (point, scalar) pairs
+        (CP_FIXED_BASE_MUL: px = py = None, the base is the program's)."""
         ctx = self._ctx
-        n = ctx._shape(px)[0]
+        n = ctx._shape(k)[0]
         cols, err, valid, ld = self._out(n, cols, err, valid, ld)
         bad = ctx._check(ctx._L.p2e_curve_mul_witness_batch(ctx._h, self._h, _ptr(px), _ptr(py), _ptr(k), _ptr(cols), C.c_size_t(n),
                                                             C.c_size_t(ld), _ptr(err), _ptr(valid)))
@@ -424,10 +431,32 @@ class CurveProgram:
     def mul_witness_compact_batch(self, px, py, k, narrow=None, wide=None, err=None, valid=None, ld_narrow=None, ld_wide=None):
         """mul_witness_batch writing the compact container: (narrow u32, wide u64, err, valid, bad)"""
         ctx = self._ctx
-        n = ctx._shape(px)[0]
+        n = ctx._shape(k)[0]
         narrow, wide, err, valid, ldn, ldw = self._compact_out(n, narrow, wide, err, valid, ld_narrow, ld_wide)
         ctx._L.p2e_curve_mul_witness_compact_batch.restype = C.c_long
         bad = ctx._check(ctx._L.p2e_curve_mul_witness_compact_batch(ctx._h, self._h, _ptr(px), _ptr(py), _ptr(k), _ptr(narrow), C.c_size_t(ldn),
+                                                                    _ptr(wide), C.c_size_t(ldw), C.c_size_t(n), _ptr(err), _ptr(valid)))
+        return narrow, wide, err, valid, bad
+
+    def msm_witness_batch(self, px, py, qx, qy, n_scalar, m_scalar, cols=None, err=None, valid=None, ld=None):
+        """CP_MSM: (num_cols, n) columns of curve_msm_circuit(p, q, n, m) for a batch; points and scalars as (n, 32)
+        little-endian byte arrays"""
+        ctx = self._ctx
+        n = ctx._shape(px)[0]
+        cols, err, valid, ld = self._out(n, cols, err, valid, ld)
+        bad = ctx._check(ctx._L.p2e_curve_msm_witness_batch(ctx._h, self._h, _ptr(px), _ptr(py), _ptr(qx), _ptr(qy), _ptr(n_scalar),
+                                                            _ptr(m_scalar), _ptr(cols), C.c_size_t(n), C.c_size_t(ld), _ptr(err),
+                                                            _ptr(valid)))
+        return cols, err, valid, bad
+
+    def msm_witness_compact_batch(self, px, py, qx, qy, n_scalar, m_scalar, narrow=None, wide=None, err=None, valid=None,
+                                  ld_narrow=None, ld_wide=None):
+        """msm_witness_batch writing the compact container: (narrow u32, wide u64, err, valid, bad)"""
+        ctx = self._ctx
+        n = ctx._shape(px)[0]
+        narrow, wide, err, valid, ldn, ldw = self._compact_out(n, narrow, wide, err, valid, ld_narrow, ld_wide)
+        bad = ctx._check(ctx._L.p2e_curve_msm_witness_compact_batch(ctx._h, self._h, _ptr(px), _ptr(py), _ptr(qx), _ptr(qy),
+                                                                    _ptr(n_scalar), _ptr(m_scalar), _ptr(narrow), C.c_size_t(ldn),
                                                                     _ptr(wide), C.c_size_t(ldw), C.c_size_t(n), _ptr(err), _ptr(valid)))
         return narrow, wide, err, valid, bad
 
@@ -443,10 +472,14 @@ class CurveProgram:
         return narrow, wide, err, valid, bad
 
     def _inputs(self, inputs):
-        """(msg, r, s, pkx, pky) pointers from the program's input tuple: (px, py, k) or (msg, r, s, pkx, pky)"""
+        """(msg, r, s, pkx, pky) pointers from the program's input tuple: (px, py, k) (fixed-base: px = py = None),
+        (px, py, qx, qy, n, m) for CP_MSM, or (msg, r, s, pkx, pky)"""
         if len(inputs) == 3:
             px, py, k = inputs
             return k, None, None, px, py
+        if len(inputs) == 6:
+            px, py, _qx, _qy, n, m = inputs
+            return n, m, None, px, py
         return tuple(inputs)
 
     def ux_describe(self):
@@ -461,7 +494,7 @@ class CurveProgram:
         """built-in-generator targets of the program's circuit from its finished witness matrix: (num_aux_cols, n)"""
         ctx = self._ctx
         msg, r, s, px, py = self._inputs(inputs)
-        n = n if n is not None else ctx._shape(px)[0]
+        n = n if n is not None else ctx._shape(msg)[0]
         ld = ld if ld is not None else _ld(cols)
         aux = aux if aux is not None else ctx._cols(self.num_aux_cols, n)
         err = err if err is not None else ctx._vec(n, np.uint8)
@@ -483,7 +516,7 @@ class CurveProgram:
         """constraint-block (U29 gate) values from the finished witness and aux matrices: (num_ux_cols, n) u32 / u64"""
         ctx = self._ctx
         msg, r, s, px, py = self._inputs(inputs)
-        n = n if n is not None else ctx._shape(px)[0]
+        n = n if n is not None else ctx._shape(msg)[0]
         ld = ld if ld is not None else _ld(cols)
         if ux is None:
             if ctx.host_pointers:

@@ -26,6 +26,7 @@ constexpr u32 AUX_SRC_INPUT_PY = 0x40000000u;  // the caller's pk.y
 constexpr u32 AUX_SRC_AUX = 0x20000000u;       // | column of the built-in-generator (aux) matrix
 constexpr u32 AUX_SRC_KIND_MASK = 0xE0000000u;
 constexpr u32 INPUT_PY = 0, INPUT_PX = 1, INPUT_MSG = 2, INPUT_R = 3, INPUT_S = 4;   // Buffers / p2e.h argument slots
+constexpr u32 INPUT_QX = 5, INPUT_QY = 6;   // the MSM curve program's second point (p2e_curve_msm_witness_batch)
 // scalar constants the gadgets create (constant_nonnative): zero has NO limbs (Q5), B = 7 one
 constexpr u32 CONSTV_ZERO = 6, CONSTV_B7 = 7, CONSTV_GLV_S = 8, CONSTV_GLV_BETA = 9, NUM_CONSTV = 10;
 // columns of the result limbs inside the column block of one curve op (gadgets/curve.rs:160-243 emission order)
@@ -67,7 +68,7 @@ struct AuxArgs {
     const u32* nar;          // compact source: narrow matrix, its stride, wide columns before column c
     size_t ldn;
     const u32* wide_before;
-    const uint8_t* in[5];    // curve programs: every packed input by INPUT_* slot (in[INPUT_PY] == py)
+    const uint8_t* in[7];    // curve programs: every packed input by INPUT_* slot (in[INPUT_PY] == py)
 };
 
 P2E_HD u64 aux_col(const AuxArgs& A, u32 c, size_t i) {
@@ -353,6 +354,38 @@ P2E_HD void body_aux_cv(const AuxArgs& A, int item, size_t i) {
         aux_put_select(e, l, NL, 1);
         aux_limbs_of(r.y, l);
         aux_put_select(e, l, NL, 1);
+        e.put(is_zero);   // not(should_add)
+        aux_put_products_cv(e, A, it.sumx, NL, i, should_add);
+        aux_put_products_cv(e, A, it.sumy, NL, i, should_add);
+        aux_put_products_cv(e, A, it.p1x, (int)it.nlx, i, is_zero);
+        aux_put_products_cv(e, A, it.p1y, (int)it.nly, i, is_zero);
+        e.flush();
+    } else if (it.kind == AUX_SPLIT2) {   // gadgets/split_nonnative.rs:52-72 of a full 9-limb scalar (the MSM program)
+        aux_load_limbs_cv(A, it.a, i, l, NL);
+        bool bad = false;
+        P2E_UNROLL
+        for (int k = 0; k < NL; k++) {
+            bad = bad || (l[k] >> BITS) != 0;
+            P2E_UNROLL
+            for (int j = 0; j < BITS; j++) e.put((l[k] >> j) & 1);
+        }
+        if (bad) err_or(&A.err[i], ERR_LIMB_RANGE);
+        P2E_UNROLL
+        for (int t = 0; 2 * t < NL * BITS; t++) e.put(aux_digit_of_limbs<2>(l, t));
+        e.flush();
+    } else if (it.kind == AUX_MSMDIG) {   // gadgets/curve_msm.rs:67-71: index, random access, is_equal, not, conditional add
+        aux_load_limbs_cv(A, it.a, i, l, NL);
+        const u32 dn = aux_digit_of_limbs<2>(l, (int)it.b);
+        aux_load_limbs_cv(A, it.c, i, l, NL);
+        const u32 idx = 4 * aux_digit_of_limbs<2>(l, (int)it.b) + dn;
+        e.put(idx);
+        aux_load_limbs_cv(A, A.tab->tabx[idx], i, l, NL);
+        aux_put_select(e, l, NL, 1);
+        aux_load_limbs_cv(A, A.tab->taby[idx], i, l, NL);
+        aux_put_select(e, l, NL, 1);
+        const u64 is_zero = idx == 0, should_add = 1 - is_zero;
+        e.put(is_zero);
+        e.put(should_add);
         e.put(is_zero);   // not(should_add)
         aux_put_products_cv(e, A, it.sumx, NL, i, should_add);
         aux_put_products_cv(e, A, it.sumy, NL, i, should_add);

@@ -60,10 +60,10 @@ inline U256 hash0_scalar(int nbytes) {
     for (int i = 0; i < nbytes && i < 32; i++) v.w[i >> 2] |= (u32)h[i] << (8 * (i & 3));
     return v;
 }
+// the table of fixed_base_curve_mul_circuit for the constant point `base` (the verifiers: the curve's generator)
 template <class CV>
-inline std::vector<Aff> fixed_base_table_cv() {   // [66][16], slot 0 := slot 1 (gadgets/curve_fixed_base.rs:56)
+inline std::vector<Aff> fixed_base_table_cv(Aff base) {   // [66][16], slot 0 := slot 1 (gadgets/curve_fixed_base.rs:56)
     std::vector<Aff> t((size_t)FB_WINDOWS * 16);
-    Aff base = generator_cv<CV>();
     for (int w = 0; w < FB_WINDOWS; w++) {
         Aff acc = base;
         for (int k = 1; k < 16; k++) {
@@ -81,12 +81,28 @@ struct CurveProgramHost {
     ScheduleBuilder sb;
 };
 
-// blind: the point the gadget draws with rand() at circuit-build time (precompute_window's g / curve_scalar_mul's rando)
+// blind: the point the gadget draws with rand() at circuit-build time (precompute_window's g / curve_scalar_mul's rando);
+// CP_FIXED_BASE_MUL: the constant base; CP_MSM: unused
 template <class CV>
 inline void build_curve_program(CurveProgramHost& H, int kind, const Aff& blind) {
     ScheduleBuilder& sb = H.sb;
     sb.begin_curve_program(kind, H.curve, CV::a(), CV::b());
     const Aff G = generator_cv<CV>();
+    if (kind == CP_MSM || kind == CP_FIXED_BASE_MUL) {
+        // rando = KeccakHash::<32>(F::ZERO) * G of the program's curve (gadgets/curve_msm.rs:33-39,
+        // gadgets/curve_fixed_base.rs:34-38): no per-build randomness
+        const Aff r = scalar_mul_cv<CV>(hash0_scalar(32), G);
+        const u32 rando = sb.add_const_point(r), neg = sb.add_const_point(aff_neg_cv<CV>(r));
+        if (kind == CP_FIXED_BASE_MUL) {
+            sb.gfbtab = fixed_base_table_cv<CV>(blind);
+            sb.fixed_base_circuit(rando, neg);
+            return;
+        }
+        Aff u = r;   // the unblinding constant -2^(2 * 131) rando (gadgets/curve_msm.rs:74-76)
+        for (int i = 0; i < 2 * CP_MSM_DIGITS; i++) u = aff_dbl_cv<CV>(u);
+        sb.msm_circuit(rando, neg, sb.add_const_point(aff_neg_cv<CV>(u)));
+        return;
+    }
     if (kind == CP_SCALAR_MUL) {
         const u32 rando = sb.add_const_point(blind), neg = sb.add_const_point(aff_neg_cv<CV>(blind));
         sb.scalar_mul_circuit(rando, neg);
@@ -97,7 +113,7 @@ inline void build_curve_program(CurveProgramHost& H, int kind, const Aff& blind)
         const Aff r = scalar_mul_cv<CV>(hash0_scalar(32), G);
         rando32 = sb.add_const_point(r);
         neg_rando32 = sb.add_const_point(aff_neg_cv<CV>(r));
-        sb.gfbtab = fixed_base_table_cv<CV>();
+        sb.gfbtab = fixed_base_table_cv<CV>(G);
     }
     const Aff start = scalar_mul_cv<CV>(hash0_scalar(25), G);
     Aff spm = start;
@@ -112,7 +128,7 @@ inline void build_curve_program(CurveProgramHost& H, int kind, const Aff& blind)
 // curve: 0 secp256k1, 1 P-256 (include/p2e.h P2E_CURVE_*).  The verifier program exists for P-256 only: secp256k1's
 // verifier is the built-in program 0 (it multiplies by GLV, not by windows).
 inline bool make_curve_program(CurveProgramHost& H, int kind, int curve, const Aff& blind) {
-    if (kind != CP_WINDOWED && kind != CP_SCALAR_MUL && kind != CP_VERIFY) return false;
+    if (kind < CP_WINDOWED || kind > CP_FIXED_BASE_MUL) return false;
     if (curve != 0 && curve != 1) return false;
     if (kind == CP_VERIFY && curve != 1) return false;
     H.kind = kind;

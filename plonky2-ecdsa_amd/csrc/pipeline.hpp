@@ -107,6 +107,7 @@ struct Program {
 struct Buffers {
     // inputs, packed 32-byte little-endian, element i at +32*i
     const uint8_t *msg, *r, *s, *pkx, *pky;  // glv_mul-only: pkx, pky, and k in `msg`
+    const uint8_t *qx, *qy;                  // the MSM curve program's second point (null otherwise)
     Sink sink;       // where the witness values go (u64 column matrix, or the compact container)
     size_t n;
     u32* err;        // per-element error bits (never null; OR-ed atomically by phases B and C)
@@ -114,7 +115,7 @@ struct Buffers {
     // scratch, [slot][n]: Jacobian points + numerator of v^-1 (phase A), prefix products and affine points (phase B)
     U256 *PX, *PY, *PZ, *PW, *PREF, *AX, *AY;
     uint8_t* dig4;   // [66][n]
-    uint8_t* dig2;   // [73][n]   4*m_d + n_d
+    uint8_t* dig2;   // [73][n]   4*m_d + n_d  (curve programs: [cp_rows][n])
     uint16_t* msrc;  // [73][n]   resolved source id of precomputation[4*m_d + n_d] (slot, or constant | DYN_CONST_BIT)
     uint16_t* dyn;   // [num_cadd][n]
     uint16_t* src;   // [2 * num_ops][n]: resolved operand ids of every op (written by phase A for phase C)

@@ -142,8 +142,8 @@ public:
     }
     void split_nonnative_to_2_bit_limbs(NonNativeTarget v) {
         AuxItem it{};
-        it.kind = AUX_SPLIT2;   // ... and the 5 limbs of a GLV half-scalar here
-        assert(v.nl == 5);
+        it.kind = AUX_SPLIT2;   // ... and the 5 limbs of a GLV half-scalar here (a curve program's MSM: 9 limbs)
+        assert(v.nl == 5 || (generic_ && v.nl == NL));
         it.a = v.col;
         it.nlx = (uint8_t)v.nl;
         const u32 nbits = (u32)v.nl * BITS;
@@ -382,13 +382,23 @@ public:
     }
 
     // ---- curve_msm_circuit(builder, p, q, n, m) ----
-    AffinePointTarget curve_msm_circuit(AffinePointTarget p, AffinePointTarget q, NonNativeTarget n, NonNativeTarget m) {
+    // The gadget's shape follows from its scalars' limb count: `digits` 2-bit digits, and the constants rando,
+    // -rando and -2^(2 digits) rando.  The built-in programs: 5-limb GLV halves (73 digits) and the secp256k1 constants
+    // of consts.hpp; the MSM curve program: full 9-limb scalars (131 digits) and the program's own constants.
+    struct MsmShape {
+        int digits;
+        u32 rando, neg_rando, unblind;
+    };
+    AffinePointTarget curve_msm_circuit(AffinePointTarget p, AffinePointTarget q, NonNativeTarget n, NonNativeTarget m,
+                                        MsmShape sh = {MSM_DIGITS, CONST_RANDO, CONST_NEG_RANDO, CONST_NEG_RANDO_146}) {
+        assert(n.nl == m.nl && sh.digits == (n.nl * BITS + 1) / 2);
         split_nonnative_to_2_bit_limbs(n);
         split_nonnative_to_2_bit_limbs(m);
-        AffinePointTarget rando = constant_affine_point(CONST_RANDO);
-        AffinePointTarget neg_rando = constant_affine_point(CONST_NEG_RANDO);
+        AffinePointTarget rando = constant_affine_point((int)sh.rando);
+        AffinePointTarget neg_rando = constant_affine_point((int)sh.neg_rando);
         AffinePointTarget pre[16];
         for (auto& x : pre) x = p;
+        const int t0 = (int)ops.size();
         {
             Scope s(this, "table");
             AffinePointTarget cur_p = rando, cur_q = rando;
@@ -410,11 +420,15 @@ public:
             aux_tab.tabx[i] = pre[i].xcol;
             aux_tab.taby[i] = pre[i].ycol;
         }
+        if (generic_) {   // a curve program's launch plan finds its window table and digit rows here
+            prog.cp_table_ops = (int32_t)ops.size() - t0;
+            prog.cp_rows = sh.digits;
+        }
         AffinePointTarget result = rando;
-        prog.msm_loop_begin = (int32_t)ops.size();
-        prog.msm_loop_iters = MSM_DIGITS;
+        prog.msm_loop_begin = loop_begin_ = (int32_t)ops.size();
+        prog.msm_loop_iters = loop_iters_ = sh.digits;
         prog.loop_dbls = 2;
-        for (int d = MSM_DIGITS - 1; d >= 0; d--) {
+        for (int d = sh.digits - 1; d >= 0; d--) {
             Scope s(this, "digit" + std::to_string(d));
             result = curve_repeated_double(result, 2);
             // mul_add(four, limb_m, limb_n), random_access_curve_points(index, pre), is_equal, not, conditional add
@@ -433,7 +447,22 @@ public:
             aux(it, 1 + 2 * NL + 2 + 1 + 2 * NL + (u32)it.nlx + (u32)it.nly);
         }
         Scope s(this, "unblind");
-        return curve_add(result, constant_affine_point(CONST_NEG_RANDO_146), true);
+        return curve_add(result, constant_affine_point((int)sh.unblind), true);
+    }
+    // stand-alone curve_msm_circuit(p, q, n, m): p in (px, py), q in (qx, qy), n in the msg slot, m in the r slot
+    void msm_circuit(u32 rando, u32 neg_rando, u32 unblind) {
+        AffinePointTarget q{make_ref(R_SLOT, SLOT_SP_PLACEHOLDER), true, AUX_SRC_INPUT | INPUT_QX, AUX_SRC_INPUT | INPUT_QY};
+        curve_msm_circuit(input_point(), q, NonNativeTarget{FIELD_SCALAR, AUX_SRC_INPUT | INPUT_MSG, NL},
+                          NonNativeTarget{FIELD_SCALAR, AUX_SRC_INPUT | INPUT_R, NL}, MsmShape{CP_MSM_DIGITS, rando, neg_rando, unblind});
+        finish_curve_program();
+    }
+    // stand-alone fixed_base_curve_mul_circuit(base, scalar): the base's table is the program's (gfbtab), the scalar
+    // in the msg slot
+    void fixed_base_circuit(u32 rando, u32 neg_rando) {
+        id_rando_ = (int)rando;
+        id_neg_rando_ = (int)neg_rando;
+        fixed_base_curve_mul_circuit(NonNativeTarget{FIELD_SCALAR, AUX_SRC_INPUT | INPUT_MSG, NL});
+        finish_curve_program();
     }
 
     // ---- CircuitBuilderGlv ----

@@ -81,6 +81,8 @@ pub const P2E_CURVE_P256: i32 = 1;
 pub const P2E_CP_WINDOWED_MUL: i32 = 1;
 pub const P2E_CP_SCALAR_MUL: i32 = 2;
 pub const P2E_CP_VERIFY: i32 = 3;
+pub const P2E_CP_MSM: i32 = 4;
+pub const P2E_CP_FIXED_BASE_MUL: i32 = 5;
 
 // tests/test_ffi_surface.py parses this block and include/p2e.h and requires the same symbols, argument counts and
 // integer widths: add a declaration here whenever the header gains one.
@@ -210,6 +212,11 @@ extern "C" {
     pub fn p2e_p256_verify_witness_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, msg32: *const u8, r32: *const u8,
         s32: *const u8, pkx32: *const u8, pky32: *const u8, cols: *mut u64, n: usize, ld: usize, err: *mut u8,
         valid: *mut u8) -> i64;
+    // curve_msm_circuit(p, q, n, m) (P2E_CP_MSM); the fixed-base program fills through p2e_curve_mul_witness_batch with
+    // null points
+    pub fn p2e_curve_msm_witness_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, px32: *const u8, py32: *const u8,
+        qx32: *const u8, qy32: *const u8, n32: *const u8, m32: *const u8, cols: *mut u64, n: usize, ld: usize, err: *mut u8,
+        valid: *mut u8) -> i64;
     // the same two fills into the compact container (u32 narrow + u64 wide matrices), and its column map
     pub fn p2e_curve_mul_witness_compact_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, px32: *const u8, py32: *const u8,
         k32: *const u8, narrow: *mut u32, ld_narrow: usize, wide: *mut u64, ld_wide: usize, n: usize, err: *mut u8,
@@ -217,6 +224,9 @@ extern "C" {
     pub fn p2e_p256_verify_witness_compact_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, msg32: *const u8, r32: *const u8,
         s32: *const u8, pkx32: *const u8, pky32: *const u8, narrow: *mut u32, ld_narrow: usize, wide: *mut u64, ld_wide: usize,
         n: usize, err: *mut u8, valid: *mut u8) -> i64;
+    pub fn p2e_curve_msm_witness_compact_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, px32: *const u8, py32: *const u8,
+        qx32: *const u8, qy32: *const u8, n32: *const u8, m32: *const u8, narrow: *mut u32, ld_narrow: usize, wide: *mut u64,
+        ld_wide: usize, n: usize, err: *mut u8, valid: *mut u8) -> i64;
     pub fn p2e_curve_program_compact_layout(prog: *const P2eCurveProgram, col_map: *mut u32, cap: usize, num_narrow: *mut u32,
         num_wide: *mut u32) -> i64;
 }

@@ -1,7 +1,8 @@
 """Curve programs: fills/s and the roofline of their expansion kernel.
 One JSON line per (program, curve, batch): whole call (wall, median of REPS) and the expansion launches alone
 (kc_expand: algorithmic bytes = columns x 8 B x n, durations = the library's own HIP event pairs around every launch,
-p2e_last_phase_ms).  Usage: python tools/bench_curve_programs.py [log2 n ...]   (default 13 15)"""
+p2e_last_phase_ms).  Usage: python tools/bench_curve_programs.py [log2 n ...]   (default 13 15); KINDS=4,5 restricts the
+run to those program kinds (P2E_CP_*: 4 = curve_msm_circuit, 5 = fixed_base_curve_mul_circuit)"""
 import json
 import os
 import sys
@@ -16,6 +17,7 @@ import plonky2_ecdsa_amd as p2e
 PEAK = 8000.0
 reps = int(os.environ.get("REPS", "5"))
 logs = [int(a) for a in sys.argv[1:]] or [13, 15]
+only = {int(k) for k in os.environ.get("KINDS", "").split(",") if k}
 ctx = p2e.Context(device=0, phase_timing=True)
 # any point of the curve serves as the circuit's rand() point: 0xC0FFEE * G, computed by the synthetic-signature helper's
 # own arithmetic is not exposed, so take a public key of the synthetic stream (a uniformly random multiple of G)
@@ -23,10 +25,12 @@ for curve, cname in ((p2e.CURVE_SECP256K1, "secp256k1"), (p2e.CURVE_P256, "p256"
     bsig = p2e.synth_signatures_curve(curve, seed=777, n=1)
     blind = (int.from_bytes(bytes(bsig[3][0]), "little"), int.from_bytes(bytes(bsig[4][0]), "little"))
     for kind, kname in ((p2e.CP_WINDOWED_MUL, "curve_scalar_mul_windowed"), (p2e.CP_SCALAR_MUL, "curve_scalar_mul"),
-                        (p2e.CP_VERIFY, "verify_p256_message_circuit")):
-        if kind == p2e.CP_VERIFY and curve != p2e.CURVE_P256:
+                        (p2e.CP_VERIFY, "verify_p256_message_circuit"), (p2e.CP_MSM, "curve_msm_circuit"),
+                        (p2e.CP_FIXED_BASE_MUL, "fixed_base_curve_mul_circuit")):
+        if (kind == p2e.CP_VERIFY and curve != p2e.CURVE_P256) or (only and kind not in only):
             continue
-        prog = p2e.CurveProgram(ctx, kind, curve, blind)
+        # (the fixed-base program takes the same random point as its base; the MSM program takes none)
+        prog = p2e.CurveProgram(ctx, kind, curve, None if kind == p2e.CP_MSM else blind)
         for lg in logs:
             n = 1 << lg
             sig = [torch.from_numpy(a).cuda() for a in p2e.synth_signatures_curve(curve, seed=5, n=n)]
@@ -36,6 +40,12 @@ for curve, cname in ((p2e.CURVE_SECP256K1, "secp256k1"), (p2e.CURVE_P256, "p256"
             valid = torch.empty(n, dtype=torch.uint8, device="cuda")
             if kind == p2e.CP_VERIFY:
                 call = lambda: prog.verify_witness_batch(*sig, cols=cols[:, :n], err=err, valid=valid, ld=ld)
+            elif kind == p2e.CP_MSM:   # p, n from one synthetic stream, q, m from another
+                sig2 = [torch.from_numpy(a).cuda() for a in p2e.synth_signatures_curve(curve, seed=6, n=n)]
+                call = lambda: prog.msm_witness_batch(sig[3], sig[4], sig2[3], sig2[4], sig[0], sig2[0], cols=cols[:, :n], err=err,
+                                                      valid=valid, ld=ld)
+            elif kind == p2e.CP_FIXED_BASE_MUL:
+                call = lambda: prog.mul_witness_batch(None, None, sig[0], cols=cols[:, :n], err=err, valid=valid, ld=ld)
             else:
                 call = lambda: prog.mul_witness_batch(sig[3], sig[4], sig[0], cols=cols[:, :n], err=err, valid=valid, ld=ld)
             _, _, _, bad = call()
@@ -72,7 +82,7 @@ for curve, cname in ((p2e.CURVE_SECP256K1, "secp256k1"), (p2e.CURVE_P256, "p256"
                                            "achieved": round(alg / tot_ms / 1e6, 1), "peak": PEAK, "unit": "GB/s",
                                            "frac": round(alg / tot_ms / 1e6 / PEAK, 4), "per_kernel": per_kernel},
                               "scalar_ms": round(p0["scalar"], 3), "scratch_GB": round(prog.scratch_bytes(n) / 1e9, 2)}), flush=True)
-            if os.environ.get("CP_PASSES") and lg <= 14:
+            if os.environ.get("CP_PASSES") and lg <= 14 and kind in (p2e.CP_WINDOWED_MUL, p2e.CP_SCALAR_MUL, p2e.CP_VERIFY):
                 # the three streaming passes over the finished matrix (aux -> gate-internal -> U29 blocks): wall time of
                 # each synchronous call, algorithmic bytes = what the pass must read + write
                 inputs = sig if kind == p2e.CP_VERIFY else (sig[3], sig[4], sig[0])
