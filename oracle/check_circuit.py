@@ -573,9 +573,10 @@ class Circuit:
         limbs_m = self.split_2(m)
         self.require(len(limbs_n) == len(limbs_m), "curve_msm", "digit counts differ")
         num = len(limbs_n)
-        rando = R.rando_point()
+        C = self.curve
+        rando = C.hash_point(32)                                # KeccakHash::<32>(F::ZERO) * G of the circuit's curve (:33-39)
         rando_t = const_point(rando)
-        neg_rando = const_point(R.ec_neg(rando))
+        neg_rando = const_point(C.neg(rando))
         pre = [p] * 16
         cur_p, cur_q = rando_t, rando_t
         with self.scope("table"):
@@ -601,9 +602,9 @@ class Circuit:
                 result = self.curve_conditional_add(result, r, should_add, False)
         spm = rando
         for _ in range(2 * num):
-            spm = R.ec_double(spm)
+            spm = C.double(spm)
         with self.scope("unblind"):
-            return self.curve_add(result, const_point(R.ec_neg(spm)), True)
+            return self.curve_add(result, const_point(C.neg(spm)), True)
 
     # ---- gadgets/glv.rs:53-104 ----------------------------------------------------------------------------------------
     def decompose_secp256k1_scalar(self, k):
@@ -762,6 +763,25 @@ def check_scalar_mul(curve, cols, px, py, k, rando, aux=None):
     """curve_scalar_mul(p, k) (gadgets/curve.rs:245-285) with blinding point rando"""
     c = Circuit(cols, aux=aux, curve=curve)
     pt = c.curve_scalar_mul((input_t("px", px), input_t("py", py)), input_t("k", k), rando, True)
+    c.finish()
+    return c, (pt[0].value(), pt[1].value())
+
+
+def check_msm(curve, cols, px, py, qx, qy, n, m, aux=None):
+    """curve_msm_circuit(p, q, n, m) (gadgets/curve_msm.rs:21-79) with two raw 256-bit scalars of 9 limbs; returns the
+    Circuit (its .aux / .gate are the derived built-in-generator and gate-internal vectors) and the result point"""
+    c = Circuit(cols, aux=aux, curve=curve)
+    pt = c.curve_msm((input_t("px", px), input_t("py", py)), (input_t("qx", qx), input_t("qy", qy)), input_t("n", n),
+                     input_t("m", m))
+    c.finish()
+    return c, (pt[0].value(), pt[1].value())
+
+
+def check_fixed_base(curve, cols, base, k, aux=None, ux=None):
+    """fixed_base_curve_mul_circuit(base, k) (gadgets/curve_fixed_base.rs:18-66) with an affine base (x, y); returns the
+    Circuit (.aux, .gate, .ux) and the result point"""
+    c = Circuit(cols, aux=aux, ux=ux, curve=curve)
+    pt = c.fixed_base_curve_mul(base, input_t("k", k))
     c.finish()
     return c, (pt[0].value(), pt[1].value())
 

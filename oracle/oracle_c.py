@@ -262,6 +262,54 @@ def curve_program(kind, curve, blind, args, nthreads=0, lockstep=0, want_aux=Tru
     return cols, aux, err, flags
 
 
+CP_MSM, CP_FIXED_BASE_MUL = 4, 5
+
+
+def _b32(v):
+    if isinstance(v, int):
+        return np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8).copy()
+    return np.ascontiguousarray(v, dtype=np.uint8)
+
+
+def curve_msm(curve, px, py, qx, qy, n, m, nthreads=0, lockstep=0, want_aux=True):
+    """curve_msm_circuit(p, q, n, m) with two raw 256-bit scalars (p2e_oracle.h p2e_oracle_curve_msm, kind 4); every argument
+    (count, 32) uint8.  Returns (cols, aux, err, flags); err has ERR_INVERSE_OF_ZERO where the reference panics."""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in (px, py, qx, qy, n, m)]
+    cnt = arrs[0].shape[0]
+    assert all(a.shape == (cnt, 32) for a in arrs)
+    nc, na = curve_program_num_cols(CP_MSM, curve)
+    cols = _cols(nc, cnt)
+    aux = _cols(na, cnt) if want_aux else None
+    err, flags = np.zeros(cnt, dtype=np.uint8), np.zeros(cnt, dtype=np.uint8)
+    f = lib().p2e_oracle_curve_msm
+    f.restype = C.c_long
+    rc = f(C.c_int(curve), *[_p(a) for a in arrs], _p(cols), C.c_size_t(cnt), C.c_size_t(cnt), _p(aux) if want_aux else None,
+           C.c_size_t(cnt), _p(err), _p(flags), C.c_int(nthreads), C.c_int(lockstep))
+    if rc < 0:
+        raise RuntimeError(f"p2e_oracle_curve_msm: {rc}")
+    return cols, aux, err, flags
+
+
+def curve_fixed_base(curve, base, k, nthreads=0, lockstep=0, want_aux=True):
+    """fixed_base_curve_mul_circuit(base, k) (p2e_oracle.h p2e_oracle_curve_fixed_base, kind 5).  base: (x, y) python ints or
+    two 32-byte arrays; k (count, 32) uint8.  Returns (cols, aux, err, flags)."""
+    bx, by = _b32(base[0]), _b32(base[1])
+    k = np.ascontiguousarray(k, dtype=np.uint8)
+    cnt = k.shape[0]
+    assert k.shape == (cnt, 32)
+    nc, na = curve_program_num_cols(CP_FIXED_BASE_MUL, curve)
+    cols = _cols(nc, cnt)
+    aux = _cols(na, cnt) if want_aux else None
+    err, flags = np.zeros(cnt, dtype=np.uint8), np.zeros(cnt, dtype=np.uint8)
+    f = lib().p2e_oracle_curve_fixed_base
+    f.restype = C.c_long
+    rc = f(C.c_int(curve), _p(bx), _p(by), _p(k), _p(cols), C.c_size_t(cnt), C.c_size_t(cnt), _p(aux) if want_aux else None,
+           C.c_size_t(cnt), _p(err), _p(flags), C.c_int(nthreads), C.c_int(lockstep))
+    if rc < 0:
+        raise RuntimeError(f"p2e_oracle_curve_fixed_base: {rc}")
+    return cols, aux, err, flags
+
+
 def rando():
     x = np.zeros(32, dtype=np.uint8)
     y = np.zeros(32, dtype=np.uint8)

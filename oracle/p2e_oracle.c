@@ -501,6 +501,9 @@ typedef struct curve_t {
     u64 RANDO_L[2][NL], NEG_RANDO_L[2][NL];
     u64 FB_TABLE[FB_WINDOWS][16][2][NL];    /* [window][digit][x|y][limb]; slot 0 := slot 1 */
     apt start25, start25_264;               /* KeccakHash::<25>(0) * G and 2^264 times it, gadgets/curve_windowed_mul.rs:140-153 */
+    /* -2^(2 digits) rando, the MSM's unblinding constant (gadgets/curve_msm.rs:73-77): [0] 73 digits (5-limb scalars of
+     * the GLV path), [1] 131 digits (9-limb scalars of curve_msm_circuit on its own) */
+    u64 NEG_RANDO_POW_L[2][2][NL];
 } curve_t;
 static curve_t SECP, P256C;
 
@@ -558,8 +561,8 @@ static void ecc_mul(const curve_t *c, apt *r, const w32 *k, const apt *p) {
     *r = acc;
 }
 
-static apt RANDO, NEG_RANDO, NEG_RANDO_146;
-static u64 RANDO_L[2][NL], NEG_RANDO_L[2][NL], NEG_RANDO_146_L[2][NL], BETA_L[NL], GLV_S_L[NL];
+static apt RANDO;
+static u64 BETA_L[NL], GLV_S_L[NL];
 static int INIT_DONE = 0;
 
 static void point_limbs(const apt *p, u64 out[2][NL]) {
@@ -571,6 +574,24 @@ static int const_nlimbs(const u64 *l) {
     int n = NL;
     while (n > 0 && l[n - 1] == 0) n--;
     return n;
+}
+/* gadgets/curve_fixed_base.rs:24-30,45-56: window w holds t * 16^w * base for t = 1..15, slot 0 := slot 1 */
+static void fb_table_init(const curve_t *c, const apt *base0, u64 (*table)[16][2][NL]) {
+    apt base = *base0;
+    for (int w = 0; w < FB_WINDOWS; w++) {
+        apt acc = base;
+        for (int t = 1; t < 16; t++) {
+            point_limbs(&acc, table[w][t]);
+            if (t == 1) point_limbs(&acc, table[w][0]);
+            if (t < 15) {
+                if (t == 1)
+                    ecc_double(c, &acc, &acc);
+                else
+                    ecc_add(c, &acc, &acc, &base);
+            }
+        }
+        for (int i = 0; i < 4; i++) ecc_double(c, &base, &base);
+    }
 }
 static void curve_init(curve_t *c, int fbase, int fscalar, const w32 *a, const w32 *b, const w32 *gx, const w32 *gy) {
     c->fbase = fbase, c->fscalar = fscalar;
@@ -595,21 +616,15 @@ static void curve_init(curve_t *c, int fbase, int fscalar, const w32 *a, const w
     apt d = c->start25;
     for (int i = 0; i < 4 * FB_WINDOWS; i++) ecc_double(c, &d, &d); /* windows.len() * 4 doublings, :146-152 */
     c->start25_264 = d; /* the gadget negates it itself (curve_neg of the constant, :168-169) */
-    /* gadgets/curve_fixed_base.rs:24-30,45-56 */
-    apt base = c->g;
-    for (int w = 0; w < FB_WINDOWS; w++) {
-        apt acc = base;
-        for (int t = 1; t < 16; t++) {
-            point_limbs(&acc, c->FB_TABLE[w][t]);
-            if (t == 1) point_limbs(&acc, c->FB_TABLE[w][0]);
-            if (t < 15) {
-                if (t == 1)
-                    ecc_double(c, &acc, &acc);
-                else
-                    ecc_add(c, &acc, &acc, &base);
-            }
+    fb_table_init(c, &c->g, c->FB_TABLE);
+    d = c->rando;
+    for (int i = 1; i <= 2 * 131; i++) { /* gadgets/curve_msm.rs:73-75: one doubling per bit of the padded scalar */
+        ecc_double(c, &d, &d);
+        if (i == 2 * 73 || i == 2 * 131) {
+            apt neg;
+            ecc_neg(c, &neg, &d);
+            point_limbs(&neg, c->NEG_RANDO_POW_L[i == 2 * 131]);
         }
-        for (int i = 0; i < 4; i++) ecc_double(c, &base, &base);
     }
 }
 static void oracle_init(void) {
@@ -620,13 +635,6 @@ static void oracle_init(void) {
             curve_init(&SECP, P2E_O_FIELD_BASE, P2E_O_FIELD_SCALAR, SECP_A, SECP_B, GEN_X, GEN_Y);
             curve_init(&P256C, P2E_O_FIELD_P256_BASE, P2E_O_FIELD_P256_SCALAR, P256_A, P256_B, P256_GX, P256_GY);
             RANDO = SECP.rando;
-            NEG_RANDO = SECP.neg_rando;
-            apt d = RANDO;
-            for (int i = 0; i < 146; i++) ecc_double(&SECP, &d, &d); /* gadgets/curve_msm.rs:74 (2*73 doublings) */
-            ecc_neg(&SECP, &NEG_RANDO_146, &d);
-            point_limbs(&RANDO, RANDO_L);
-            point_limbs(&NEG_RANDO, NEG_RANDO_L);
-            point_limbs(&NEG_RANDO_146, NEG_RANDO_146_L);
             words_to_limbs(GLV_BETA, 8, BETA_L, NL);
             words_to_limbs(GLV_S, 8, GLV_S_L, NL);
             INIT_DONE = 1;
@@ -821,8 +829,10 @@ static void aux_point(walker *w, const pt *p) {
     aux_emit(w, p->x.l, NL);
     aux_emit(w, p->y.l, NL);
 }
-static pt w_fixed_base(walker *w, const nn *scalar) { /* gadgets/curve_fixed_base.rs:18-66; base = the curve's generator */
+/* gadgets/curve_fixed_base.rs:18-66; table = the windows of the base (fb_table_init), NULL = the curve's generator */
+static pt w_fixed_base(walker *w, const nn *scalar, u64 (*table)[16][2][NL]) {
     const curve_t *cv = cv_of(w);
+    if (!table) table = (u64(*)[16][2][NL])cv->FB_TABLE;
     u64(*RANDO_L)[NL] = (u64(*)[NL])cv->RANDO_L, (*NEG_RANDO_L)[NL] = (u64(*)[NL])cv->NEG_RANDO_L;
     pt result = pt_from(RANDO_L);
     int nlx = const_nlimbs(RANDO_L[0]), nly = const_nlimbs(RANDO_L[1]);
@@ -836,7 +846,7 @@ static pt w_fixed_base(walker *w, const nn *scalar) { /* gadgets/curve_fixed_bas
     for (int i = 0; i < FB_WINDOWS; i++) {
         unsigned d = digit_of(scalar->l, NL, 4, i);
         u64 should_add = w_not(w, w_is_zero(w, d));
-        pt r = pt_from((u64(*)[NL])cv->FB_TABLE[i][d]);
+        pt r = pt_from(table[i][d]);
         aux_point(w, &r);
         result = w_curve_cond_add(w, &result, nlx, nly, &r, should_add);
         nlx = nly = NL;
@@ -844,15 +854,19 @@ static pt w_fixed_base(walker *w, const nn *scalar) { /* gadgets/curve_fixed_bas
     pt nr = pt_from(NEG_RANDO_L);
     return w_curve_add(w, &result, &nr);
 }
-static pt w_msm(walker *w, const pt *p, const pt *q, const u64 *n5, const u64 *m5) { /* gadgets/curve_msm.rs:21-79 */
+/* gadgets/curve_msm.rs:21-79 on the walker's curve; nl = limbs of the two scalars: 5 (the GLV halves: 145 bits padded to
+ * 146, 73 digits) or 9 (curve_msm_circuit on its own: 261 bits padded to 262, 131 digits) */
+static pt w_msm(walker *w, const pt *p, const pt *q, const u64 *nlimbs, const u64 *mlimbs, int nl) {
+    const curve_t *cv = cv_of(w);
+    const int ndig = (nl * BITS + 1) / 2;
     pt pre[16];
-    pt rando = pt_from(RANDO_L), nr = pt_from(NEG_RANDO_L);
+    pt rando = pt_from((u64(*)[NL])cv->RANDO_L), nr = pt_from((u64(*)[NL])cv->NEG_RANDO_L);
     /* split_nonnative_to_2_bit_limbs(n), then (m): gadgets/split_nonnative.rs:52-72 */
     for (int which = 0; which < 2; which++) {
-        const u64 *l5 = which ? m5 : n5;
-        aux_bits(w, l5, 5);
-        for (int t = 0; t < 73; t++) {
-            u64 dg = digit_of(l5, 5, 2, t);
+        const u64 *l = which ? mlimbs : nlimbs;
+        aux_bits(w, l, nl);
+        for (int t = 0; t < ndig; t++) {
+            u64 dg = digit_of(l, nl, 2, t);
             aux_emit(w, &dg, 1);
         }
     }
@@ -871,16 +885,16 @@ static pt w_msm(walker *w, const pt *p, const pt *q, const u64 *n5, const u64 *m
     for (int i = 1; i < 4; i++)
         for (int j = 1; j < 4; j++) pre[i + 4 * j] = w_curve_add(w, &pre[i], &pre[4 * j]);
     pt result = rando;
-    for (int d = 72; d >= 0; d--) { /* 5 limbs -> 145 bits -> 146 -> 73 digits, MSB first */
+    for (int d = ndig - 1; d >= 0; d--) { /* MSB first */
         result = w_curve_double(w, &result);
         result = w_curve_double(w, &result);
-        u64 idx = 4 * digit_of(m5, 5, 2, d) + digit_of(n5, 5, 2, d); /* mul_add(four, limb_m, limb_n) */
+        u64 idx = 4 * digit_of(mlimbs, nl, 2, d) + digit_of(nlimbs, nl, 2, d); /* mul_add(four, limb_m, limb_n) */
         aux_emit(w, &idx, 1);
         aux_point(w, &pre[idx]);
         u64 should_add = w_not(w, w_is_zero(w, idx));
         result = w_curve_cond_add(w, &result, NL, NL, &pre[idx], should_add);
     }
-    pt to_add = pt_from(NEG_RANDO_146_L);
+    pt to_add = pt_from((u64(*)[NL])cv->NEG_RANDO_POW_L[nl == NL]);
     return w_curve_add(w, &result, &to_add);
 }
 static int nn_eq(const nn *a, const nn *b) { return memcmp(a->l, b->l, sizeof a->l) == 0; }
@@ -908,7 +922,7 @@ static pt w_glv_mul(walker *w, const pt *p, const nn *k, int *ok) { /* gadgets/g
     pn.y = w_cond_neg(w, &p->y, NL, n1, P2E_O_FIELD_BASE);
     spn.x = sp.x;
     spn.y = w_cond_neg(w, &sp.y, NL, n2, P2E_O_FIELD_BASE);
-    return w_msm(w, &pn, &spn, k1.l, k2.l);
+    return w_msm(w, &pn, &spn, k1.l, k2.l, 5);
 }
 static nn nn_from_bytes(const uint8_t *b) {
     w32 wv[8];
@@ -937,7 +951,7 @@ static void walk_verify(walker *w, const uint8_t *msg32, const uint8_t *r32, con
     nn c = w_inv(w, &s, S);
     nn u1 = w_mul(w, &msg, &c, S);
     nn u2 = w_mul(w, &r, &c, S);
-    pt p1 = w_fixed_base(w, &u1);
+    pt p1 = w_fixed_base(w, &u1, NULL);
     pt p2 = w_glv_mul(w, &pk, &u2, &ok);
     pt sum = w_curve_add(w, &p1, &p2);
     ok &= nn_eq(&sum.x, &r);
@@ -1035,7 +1049,7 @@ static void walk_verify_p256(walker *w, const uint8_t *msg32, const uint8_t *r32
     nn c = w_inv(w, &s, S);
     nn u1 = w_mul(w, &msg, &c, S);
     nn u2 = w_mul(w, &r, &c, S);
-    pt p1 = w_fixed_base(w, &u1);
+    pt p1 = w_fixed_base(w, &u1, NULL);
     pt p2 = w_windowed_mul(w, &pk, &u2, g);
     pt sum = w_curve_add(w, &p1, &p2);
     ok &= nn_eq(&sum.x, &r);
@@ -1046,6 +1060,8 @@ typedef struct {
     const curve_t *cv;
     apt blind;
     const uint8_t *msg, *r, *s, *px, *py;
+    const uint8_t *qx, *qy, *m;             /* kind 4: the second point and its scalar (the first scalar is msg) */
+    u64 (*fb_table)[16][2][NL];             /* kind 5: the windows of the caller's base */
 } cp_job;
 static void walk_curve_program(walker *w, const cp_job *J, size_t i, uint8_t *flag) {
     w->cv = J->cv;
@@ -1053,10 +1069,24 @@ static void walk_curve_program(walker *w, const cp_job *J, size_t i, uint8_t *fl
         walk_verify_p256(w, J->msg + 32 * i, J->r + 32 * i, J->s + 32 * i, J->px + 32 * i, J->py + 32 * i, &J->blind, flag);
         return;
     }
+    nn k = nn_from_bytes(J->msg + 32 * i);
+    if (J->kind == P2E_O_CP_FIXED_BASE_MUL) { /* fixed_base_curve_mul_circuit gadgets/curve_fixed_base.rs:18-66 */
+        (void)w_fixed_base(w, &k, J->fb_table);
+        *flag = w->err == 0;
+        return;
+    }
     pt p;
     p.x = nn_from_bytes(J->px + 32 * i);
     p.y = nn_from_bytes(J->py + 32 * i);
-    nn k = nn_from_bytes(J->msg + 32 * i);
+    if (J->kind == P2E_O_CP_MSM) { /* curve_msm_circuit gadgets/curve_msm.rs:21-79 with two full 9-limb scalars */
+        pt q;
+        q.x = nn_from_bytes(J->qx + 32 * i);
+        q.y = nn_from_bytes(J->qy + 32 * i);
+        nn m = nn_from_bytes(J->m + 32 * i);
+        (void)w_msm(w, &p, &q, k.l, m.l, NL);
+        *flag = w->err == 0;
+        return;
+    }
     if (J->kind == P2E_O_CP_WINDOWED_MUL)
         (void)w_windowed_mul(w, &p, &k, &J->blind);
     else
@@ -1463,25 +1493,59 @@ long p2e_oracle_verify_witness_aux_lockstep(const uint8_t *msg, const uint8_t *r
     oracle_init();
     return run_lockstep(NULL, msg, r, s, pkx, pky, cols, n, ld, aux, ald, err, flags, nthreads, group);
 }
+/* kinds 1-3: (bx, by) = the blinding point; kind 4: none (NULL); kind 5: the base, whose windows are built here */
 static int cp_job_init(cp_job *J, int kind, int curve, const uint8_t *bx, const uint8_t *by) {
-    if (kind < 1 || kind > 3 || curve < 0 || curve > 1 || (kind == P2E_O_CP_VERIFY && curve != 1) || !bx || !by) return -1;
+    if (kind < 1 || kind > 5 || curve < 0 || curve > 1 || (kind == P2E_O_CP_VERIFY && curve != 1)) return -1;
+    if (kind != P2E_O_CP_MSM && (!bx || !by)) return -1;
     oracle_init();
     memset(J, 0, sizeof *J);
     J->kind = kind;
     J->cv = curve ? &P256C : &SECP;
+    if (kind == P2E_O_CP_MSM) return 0;
     bytes_to_words(bx, J->blind.x);
     bytes_to_words(by, J->blind.y);
+    if (kind == P2E_O_CP_FIXED_BASE_MUL) {
+        J->fb_table = malloc(sizeof(u64[FB_WINDOWS][16][2][NL]));
+        if (!J->fb_table) return -2;
+        fb_table_init(J->cv, &J->blind, J->fb_table);
+    }
     return 0;
 }
+static long cp_job_run(const cp_job *J, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
+                       uint8_t *flags, int nthreads, int lockstep_group);
 long p2e_oracle_curve_program(int kind, int curve, const uint8_t *blind_x32, const uint8_t *blind_y32,
                               const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *px,
                               const uint8_t *py, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
                               uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group) {
     cp_job J;
-    if (cp_job_init(&J, kind, curve, blind_x32, blind_y32)) return -1;
+    if (kind > P2E_O_CP_VERIFY || cp_job_init(&J, kind, curve, blind_x32, blind_y32)) return -1;
     J.msg = msg, J.r = r, J.s = s, J.px = px, J.py = py;
+    return cp_job_run(&J, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+}
+long p2e_oracle_curve_msm(int curve, const uint8_t *px, const uint8_t *py, const uint8_t *qx, const uint8_t *qy,
+                          const uint8_t *n_scalar, const uint8_t *m_scalar, uint64_t *cols, size_t n, size_t ld,
+                          uint64_t *aux, size_t ald, uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group) {
+    cp_job J;
+    if (cp_job_init(&J, P2E_O_CP_MSM, curve, NULL, NULL)) return -1;
+    J.msg = n_scalar, J.m = m_scalar, J.px = px, J.py = py, J.qx = qx, J.qy = qy;
+    return cp_job_run(&J, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+}
+long p2e_oracle_curve_fixed_base(int curve, const uint8_t *base_x32, const uint8_t *base_y32, const uint8_t *k,
+                                 uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
+                                 uint8_t *flags, int nthreads, int lockstep_group) {
+    cp_job J;
+    int rc0 = cp_job_init(&J, P2E_O_CP_FIXED_BASE_MUL, curve, base_x32, base_y32);
+    if (rc0) return rc0;
+    J.msg = k;
+    long rc = cp_job_run(&J, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+    free(J.fb_table);
+    return rc;
+}
+static long cp_job_run(const cp_job *Jp, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
+                       uint8_t *flags, int nthreads, int lockstep_group) {
+    const cp_job J = *Jp;
     if (lockstep_group > 0) {
-        long rc = run_lockstep(&J, msg, r, s, px, py, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+        long rc = run_lockstep(&J, NULL, NULL, NULL, NULL, NULL, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
         return rc == -1 ? -2 : rc;
     }
 #ifdef _OPENMP
@@ -1502,7 +1566,10 @@ long p2e_oracle_curve_program(int kind, int curve, const uint8_t *blind_x32, con
 long p2e_oracle_curve_program_num_cols(int kind, int curve, long *num_aux) {
     cp_job J;
     uint8_t zero[32] = {0}, gx[32], gy[32];
-    if (cp_job_init(&J, kind, curve, zero, zero)) return -1;
+    if (kind < 1 || kind > 5) return -1;
+    /* (kind 5 is set up as kind 1 here: no windows of a base are built, the walk below uses the generator's) */
+    if (cp_job_init(&J, kind == P2E_O_CP_FIXED_BASE_MUL ? P2E_O_CP_WINDOWED_MUL : kind, curve, zero, zero)) return -1;
+    J.kind = kind;
     /* any point will do for counting: 2G as the blinding point, G as the input point, all-ones bytes elsewhere */
     apt g2;
     ecc_double(J.cv, &g2, &J.cv->g);
@@ -1511,7 +1578,8 @@ long p2e_oracle_curve_program_num_cols(int kind, int curve, long *num_aux) {
     words_to_bytes(J.cv->g.y, gy);
     uint8_t ones[32];
     memset(ones, 0x11, sizeof ones);
-    J.msg = J.r = J.s = ones, J.px = gx, J.py = gy;
+    J.msg = J.r = J.s = J.m = ones, J.px = gx, J.py = gy;
+    J.qx = J.px, J.qy = J.py; /* (p = q meets an inverse of zero; the column count does not depend on it) */
     walker w = {NULL, 0, 0, 0, 0, NULL, 0, 0, NULL};
     uint8_t f = 0;
     walk_curve_program(&w, &J, 0, &f);

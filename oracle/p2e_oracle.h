@@ -123,7 +123,23 @@ long p2e_oracle_curve_program(int kind, int curve, const uint8_t *blind_x32, con
                               const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *px,
                               const uint8_t *py, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
                               uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group);
-/* column counts of a curve program by a dry walk: returns num_cols, *num_aux = built-in-generator values */
+/* kind 4: curve_msm_circuit(p, q, n, m) gadgets/curve_msm.rs:21-79 on its own, with two raw 256-bit scalars of 9 limbs
+ *         each (261 bits padded to 262, 131 two-bit digits, MSB first); the blinding point is KeccakHash::<32>(F::ZERO) * G
+ *         of the curve (:33-39) and the unblinding constant -2^262 times it          -- 112 309 columns, 8 382 aux values
+ * kind 5: fixed_base_curve_mul_circuit(base, k) gadgets/curve_fixed_base.rs:18-66 with a caller-supplied affine base
+ *         (66 windows of 16 entries built once per call, slot 0 := slot 1)           --  16 797 columns, 4 221 aux values
+ * Both take raw scalars (no reduction).  err: P2E_O_ERR_INVERSE_OF_ZERO where the reference panics (an addition of two
+ * points with the same x: p = +-q, n = m = 0, k = 0, a base or point that meets the blinding point); flags = (err == 0).
+ * Same return values, aux, nthreads and lockstep_group as p2e_oracle_curve_program. */
+#define P2E_O_CP_MSM 4
+#define P2E_O_CP_FIXED_BASE_MUL 5
+long p2e_oracle_curve_msm(int curve, const uint8_t *px, const uint8_t *py, const uint8_t *qx, const uint8_t *qy,
+                          const uint8_t *n_scalar, const uint8_t *m_scalar, uint64_t *cols, size_t n, size_t ld,
+                          uint64_t *aux, size_t ald, uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group);
+long p2e_oracle_curve_fixed_base(int curve, const uint8_t *base_x32, const uint8_t *base_y32, const uint8_t *k,
+                                 uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
+                                 uint8_t *flags, int nthreads, int lockstep_group);
+/* column counts of a curve program (kinds 1-5) by a dry walk: returns num_cols, *num_aux = built-in-generator values */
 long p2e_oracle_curve_program_num_cols(int kind, int curve, long *num_aux);
 
 /* constants computed at init (for tests): rando = keccak256(0u64 LE) as LE scalar * G */

@@ -595,7 +595,8 @@ long emu_pack(const u64* limbs, uint8_t* packed, size_t n, size_t ld, uint8_t* e
 // of run_curve_program (pieces of `piece` ops, the per-signature table as its own piece and affine afterwards) --------
 template <class CV>
 static long run_curve(const host::CurveProgramHost& H, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx,
-                      const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int piece) {
+                      const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int piece,
+                      const uint8_t* qx = nullptr, const uint8_t* qy = nullptr) {
     const host::ScheduleBuilder& sb = H.sb;
     const Program& G = sb.prog;
     const size_t rows = (size_t)(G.cp_rows > MSM_DIGITS ? G.cp_rows : MSM_DIGITS);
@@ -606,6 +607,7 @@ static long run_curve(const host::CurveProgramHost& H, const uint8_t* msg, const
     std::vector<u32> err32(n);
     Buffers B{};
     B.msg = msg; B.r = r; B.s = s; B.pkx = pkx; B.pky = pky;
+    B.qx = qx; B.qy = qy;   // the MSM program's second point (null for every other program)
     B.sink = Sink{cols, ld, nullptr, 0, nullptr, 0, nullptr};
     B.n = n;
     B.err = err32.data(); B.valid = valid8.data();
@@ -637,27 +639,44 @@ static long run_curve(const host::CurveProgramHost& H, const uint8_t* msg, const
     host::ScheduleBuilder marked;
     if (piece < 0) {
         // the large-batch plan of run_curve_program: runs of -piece windows (op table with the run marks), the verifier's
-        // fixed-base windows as one run per signature
-        const int R = -piece, lb = G.msm_loop_begin, iters = G.msm_loop_iters, le = lb + 5 * iters;
-        if (iters <= 0) return -2;
+        // fixed-base windows as one run per signature; the op stride of a loop iteration is its doublings + the
+        // conditional add (4 + 1 in the windowed loop, 2 + 1 in the MSM program's digit loop)
+        const int R = -piece, lb = G.msm_loop_begin, iters = G.msm_loop_iters, stride = G.loop_dbls + 1, le = lb + stride * iters;
         marked = sb;
         marked.mark_runs(R);
         B.ops = marked.ops.data();
-        if (G.fb_begin >= 0) {
+        if (iters == 0) {
+            // the fixed-base program: one piece, its windows as one run per element, then the unblinding add
+            if (G.fb_begin != 0) return -2;
+            const int t_after = G.fb_begin + G.fb_windows;
+            chain_binv(G.fb_begin, G.num_ops, false);
+#pragma omp parallel for
+            for (long long i = 0; i < (long long)n; i++) body_expand_fb_run<Emit, CV>(G, B, (size_t)i, t_after);
+            expand(t_after, G.num_ops);
+        }
+        if (iters > 0 && G.loop_dbls != 2 && G.loop_dbls != 4) return -2;
+        if (iters > 0 && G.fb_begin >= 0) {
             const int fe = G.fb_begin + G.fb_windows + 1;
             chain_binv(G.fb_begin, fe, false);
 #pragma omp parallel for
             for (long long i = 0; i < (long long)n; i++) body_expand_fb_run<Emit, CV>(G, B, (size_t)i, fe - 1);
             expand(fe - 1, fe);
         }
-        chain_binv(tb, te, false);
-        expand(tb, te);
+        if (iters > 0) {
+            chain_binv(tb, te, false);
+            expand(tb, te);
+        }
         for (int it = 0; it < iters; it += R) {
             const int it1 = std::min(it + R, iters);
-            const int hi = it1 == iters ? G.num_ops : lb + 5 * it1;
-            chain_binv(lb + 5 * it, hi, true);
+            const int hi = it1 == iters ? G.num_ops : lb + stride * it1;
+            chain_binv(lb + stride * it, hi, true);
 #pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) body_expand_run<Emit, CV, 4>(G, B, (size_t)i, it, it1);
+            for (long long i = 0; i < (long long)n; i++) {
+                if (G.loop_dbls == 2)   // kc_expand_runs2
+                    body_expand_run<Emit, CV, 2>(G, B, (size_t)i, it, it1);
+                else                    // kc_expand_runs
+                    body_expand_run<Emit, CV, 4>(G, B, (size_t)i, it, it1);
+            }
             if (it1 == iters) expand(le, G.num_ops);
         }
     } else {
@@ -707,6 +726,16 @@ long emu_curve_program(int kind, int curve, const uint8_t* blind_x, const uint8_
     if (piece == 0) piece = 32;   // piece < 0: the run plan with -piece windows per run
     if (curve == 1) return run_curve<P256>(H, msg, r, s, pkx, pky, cols, n, ld, err, valid, piece);
     return run_curve<Secp256k1>(H, msg, r, s, pkx, pky, cols, n, ld, err, valid, piece);
+}
+// P2E_CP_MSM: curve_msm_circuit(p, q, n, m); as emu_curve_program with the second point (the program takes no blinding point)
+long emu_curve_msm(int curve, const uint8_t* px, const uint8_t* py, const uint8_t* qx, const uint8_t* qy, const uint8_t* n_scalar,
+                   const uint8_t* m_scalar, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int piece) {
+    host::CurveProgramHost H;
+    if (!host::make_curve_program(H, CP_MSM, curve, Aff{})) return -1;
+    if (n == 0) return 0;
+    if (piece == 0) piece = 32;
+    if (curve == 1) return run_curve<P256>(H, n_scalar, m_scalar, n_scalar, px, py, cols, n, ld, err, valid, piece, qx, qy);
+    return run_curve<Secp256k1>(H, n_scalar, m_scalar, n_scalar, px, py, cols, n, ld, err, valid, piece, qx, qy);
 }
 // generator table (kind, field, first column, column count) and operand wiring of a curve program, for the host tests
 long emu_curve_program_gens(int kind, int curve, const uint8_t* blind_x, const uint8_t* blind_y, int32_t* kinds, int32_t* fields,

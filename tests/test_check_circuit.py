@@ -158,3 +158,76 @@ def test_library_wiring_equals_the_replayed_gadget_wiring(program):
             # operands shorter than 9 limbs do not change the count: add_biguint runs over max(len) limbs
             assert un - base[kind] == int(w_rc), (label, kind, un, w_rc)
     assert n_rc > 0
+
+
+# ---- the MSM and fixed-base curve programs (oracle kinds 4 and 5) on both curves ----------------------------------------
+import msm_inputs as MI
+
+_CP_CURVES = [R.SECP256K1, R.P256]
+
+
+def _cp_witness(kind, curve_id):
+    """element 13 (a uniform scalar) and element 14 (a sparse one) of a small oracle batch: (replay(cols, aux) -> Circuit,
+    cols, aux) per element"""
+    cv = _CP_CURVES[curve_id]
+    out = []
+    if kind == "msm":
+        ins, _ = MI.exhaustive_msm_inputs(curve_id, 32, 7)
+        cols, aux, err, _flags = oracle_c.curve_msm(curve_id, *ins)
+        for i in (13, 14):
+            v = [MI.ints(a[i:i + 1])[0] for a in ins]
+            out.append((lambda c, a=None, v=v: CC.check_msm(cv, c, *v, aux=a), cols[:, i], aux[:, i], err[i],
+                        cv.add(cv.mul(v[4], (v[0], v[1])), cv.mul(v[5], (v[2], v[3])))))
+    else:
+        base = cv.mul(R.SplitMix64(91 + curve_id).below(cv.n), cv.g)
+        ks, _ = MI.exhaustive_fb_inputs(curve_id, 32, 3)
+        cols, aux, err, _flags = oracle_c.curve_fixed_base(curve_id, base, ks)
+        for i in (13, 14):
+            k = MI.ints(ks[i:i + 1])[0]
+            out.append((lambda c, a=None, k=k: CC.check_fixed_base(cv, c, base, k, aux=a), cols[:, i], aux[:, i], err[i],
+                        cv.mul(k, base)))
+    return out
+
+
+# (kind, offset inside the generator's columns): add / sub result limb and overflow, add_many, mul r / q / check_sum / carry,
+# inv result and quotient
+_CP_MUTATIONS = [("add", 0), ("add", 9), ("sub", 8), ("sub", 9), ("add_many", 3), ("mul", 0), ("mul", 9), ("mul", 18),
+                 ("mul", 35), ("inv", 0), ("inv", 9)]
+
+
+@pytest.mark.parametrize("curve_id", [0, 1])
+@pytest.mark.parametrize("kind", ["msm", "fixed_base"])
+def test_msm_and_fixed_base_oracle_witnesses_pass_the_replay_and_mutations_do_not(kind, curve_id):
+    """an oracle witness of curve_msm_circuit / fixed_base_curve_mul_circuit (any base) satisfies the reference's own
+    equations on both curves, with the oracle's aux attached; one flipped bit in one column of every generator kind, in a
+    2-bit / 4-bit digit or in a selected limb of the random access is rejected"""
+    rng = np.random.default_rng(5 + curve_id)
+    for replay, cols, aux, err, want_pt in _cp_witness(kind, curve_id):
+        assert err == 0
+        c, pt = replay(cols, aux)
+        assert pt == want_pt and c.cur == len(cols) and len(c.aux) == len(aux)
+        assert (len(cols), len(c.gens), len(aux)) == ((112309, 4694, 8382) if kind == "msm" else (16797, 802, 4221))
+    kinds = {g[0] for g in c.gens}
+    assert kinds == ({"add", "sub", "add_many", "mul", "inv"} if kind == "msm" else {"add", "sub", "mul", "inv"})
+    tried = 0
+    for gk, off in _CP_MUTATIONS:
+        gens = [g for g in c.gens if g[0] == gk]
+        if not gens:
+            continue
+        picks = [gens[int(rng.integers(0, min(len(gens), 12)))]] + ([gens[int(rng.integers(0, len(gens)))]] if off == 0 else [])
+        for g in picks:
+            bad = cols.copy()
+            bit = 0 if (gk in ("add", "sub", "add_many") and off == 9) else int(rng.integers(0, 29))   # (overflow flags: bit 0)
+            bad[g[2] + off] = int(bad[g[2] + off]) ^ (1 << bit)
+            with pytest.raises(CC.ConstraintViolation):
+                replay(bad)
+            tried += 1
+    assert tried == (14 if kind == "msm" else 13)
+    # built-in-generator values: a bit of the scalar's split, a digit, an access index (MSM), a selected limb, a product
+    nbits = 2 * 261 if kind == "msm" else 261
+    for col in (5, nbits + 3, nbits + (270 if kind == "msm" else 66 * 3) + 1, nbits + (270 if kind == "msm" else 66 * 3) + 7,
+                len(aux) - 5):
+        bad = aux.copy()
+        bad[col] = int(bad[col]) ^ 1
+        with pytest.raises(CC.ConstraintViolation):
+            replay(cols, bad)

@@ -13,6 +13,7 @@ import pytest
 
 import msm_walk as W
 import p2e_ref as R
+from msm_inputs import FLAGGED, fb_inputs as _fb_inputs, msm_inputs as _msm_inputs   # (shared with the CPU tests)
 
 CURVES = [R.SECP256K1, R.P256]
 P_GL = 0xFFFFFFFF00000001
@@ -44,25 +45,6 @@ def _ctx(monkeypatch, plan):
     return p2e.Context(device=0)
 
 
-def _msm_inputs(curve_id, n, seed):
-    """(px, py, qx, qy, n, m) as (n, 32) byte arrays: random points (public keys of synthetic signatures), random scalars,
-    and the edge cases in the first rows"""
-    import plonky2_ecdsa_amd as p2e
-    cv = CURVES[curve_id]
-    a = p2e.synth_signatures_curve(curve_id, seed=seed, n=n)
-    b = p2e.synth_signatures_curve(curve_id, seed=seed + 1, n=n)
-    px, py, qx, qy = _ints(a[3]), _ints(a[4]), _ints(b[3]), _ints(b[4])
-    ns, ms = _ints(a[0]), _ints(b[0])
-    edge = [(1, 1), (cv.n - 1, 5), (7, cv.n - 1), ((1 << 255) + 12345, (1 << 255) | 3), (123456789, 0), (0, 987654321),
-            (ns[6], ns[6]), (0, 0), (1, 2), ((1 << 256) - 1, 3)]
-    for i, (x, y) in enumerate(edge):
-        ns[i], ms[i] = x, y
-    px[10], py[10] = qx[10], qy[10]                  # p = q: the table's p + q is a doubling (flagged)
-    px[11], py[11] = qx[11], (cv.p - qy[11]) % cv.p  # p = -q (flagged)
-    return [px, py, qx, qy, ns, ms]
-
-
-FLAGGED = (7, 10, 11)   # n = m = 0, p = q, p = -q
 SAMPLE = list(range(40)) + [100, 233, 255, 256, 257, 511, 600, 699]
 
 
@@ -160,13 +142,6 @@ def test_gpu_msm_other_passes_against_the_restatement(msm_case):
                 want += [int(idx != 0), pow(idx, P_GL - 2, P_GL) if idx else 0, idx, int(idx != 0), idx]
             assert np.array_equal(gate[:, i], np.asarray(want, np.uint64)), (cid, i)
         prog.close()
-
-
-def _fb_inputs(cv, n, seed):
-    rng = R.SplitMix64(seed)
-    ks = [rng.below(cv.n) for _ in range(n)]
-    ks[0], ks[1], ks[2], ks[3] = 1, cv.n - 1, 16, (1 << 255) + 99   # (k = 0 is the unblinding add's inverse of zero)
-    return ks
 
 
 @pytest.mark.gpu
