@@ -221,6 +221,10 @@ long p2e_aux_num_cols(int program);
 long p2e_gate_internal_batch(p2e_ctx *ctx, int program, const uint64_t *aux, size_t ld_aux, uint64_t *gate, size_t ld_gate,
                              size_t n);
 long p2e_gate_internal_num_cols(int program);
+/* the same pass from the u32 aux matrix of p2e_aux_witness_compact_batch (same values; the gate matrix stays u64: the
+ * equality gadget's inverse is a full Goldilocks element) */
+long p2e_gate_internal_compact_batch(p2e_ctx *ctx, int program, const uint32_t *aux32, size_t ld_aux, uint64_t *gate,
+                                     size_t ld_gate, size_t n);
 
 /* ---- constraint-block columns ---------------------------------------------- */
 /* The values of the targets the plonky2_ux U29 gates fill INSIDE the constraint blocks of the non-native gadgets
@@ -239,6 +243,12 @@ long p2e_gate_internal_num_cols(int program);
 long p2e_ux_witness_batch(p2e_ctx *ctx, int program, const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32,
                           const uint8_t *pkx32, const uint8_t *pky32, const uint64_t *cols, size_t ld, const uint64_t *aux,
                           size_t ld_aux, void *ux, int ux_u32, size_t ld_ux, size_t n, uint8_t *err);
+/* the same pass inside the compact container: every witness column it reads is a limb, an overflow word or a flag, so
+ * it reads the u32 narrow matrix of the compact fills and the u32 aux matrix of p2e_aux_witness_compact_batch -- same
+ * values, same err semantics, half the bytes read.  Any ld_narrow >= n works (no alignment assumption). */
+long p2e_ux_witness_compact_batch(p2e_ctx *ctx, int program, const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32,
+                                  const uint8_t *pkx32, const uint8_t *pky32, const uint32_t *narrow, size_t ld_narrow,
+                                  const uint32_t *aux32, size_t ld_aux, void *ux, int ux_u32, size_t ld_ux, size_t n, uint8_t *err);
 typedef struct p2e_ux_desc {
     uint32_t first_col, num_cols; /* this generator's block (num_cols = 0: none, e.g. an unchecked mul) */
 } p2e_ux_desc;
@@ -275,6 +285,14 @@ void p2e_wire_map_destroy(p2e_ctx *ctx, p2e_wire_map *map);
 long p2e_assemble_wires(p2e_ctx *ctx, const p2e_wire_map *map, const uint64_t *cols, size_t ld, const uint64_t *aux,
                         size_t ld_aux, const void *ux, int ux_u32, size_t ld_ux, const uint64_t *gate, size_t ld_gate,
                         uint64_t *wires, size_t wire_stride, size_t n);
+/* The same scatter from the compact container: witness entries gather from narrow / wide, aux entries from the u32 aux
+ * matrix.  A map keeps its witness sources in both coordinates (p2e_wire_map_create and
+ * p2e_curve_program_wire_map_create know the program's compact layout), so one map serves both containers.  narrow or
+ * wide may be NULL if no entry names a column of it. */
+long p2e_assemble_wires_compact(p2e_ctx *ctx, const p2e_wire_map *map, const uint32_t *narrow, size_t ld_narrow,
+                                const uint64_t *wide, size_t ld_wide, const uint32_t *aux32, size_t ld_aux, const void *ux,
+                                int ux_u32, size_t ld_ux, const uint64_t *gate, size_t ld_gate, uint64_t *wires,
+                                size_t wire_stride, size_t n);
 
 /* ---- layout helper --------------------------------------------------------------------------------- */
 /* cols[ncols][ld] (column-major over the batch) -> rows[n][row_ld], one contiguous witness per signature:
@@ -367,14 +385,16 @@ int p2e_wiring_const(uint32_t id, uint8_t out32[32]);
  * [selected x (9), selected y (9), is_zero, should_add, not_b, sum.x*b, sum.y*b, p1.x*not_b, p1.y*not_b], 6 bit split,
  * 7 bit of curve_scalar_mul [not_bit, sum.x*bit, result.x*not_bit, sum.y*bit, result.y*not_bit]),
  * p2e_curve_program_gate_internal_batch and p2e_curve_program_ux_witness_batch (+ _ux_describe).
- * A program belongs to the context's device; u64 column matrix only for the fill.
+ * A program belongs to the context's device.  Every fill and every pass exists for the u64 column matrix and for the
+ * compact container (the *_compact_batch entry points below).
  * The MSM program has full 9-limb scalars (131 two-bit digits, MSB first) and no per-build randomness: its blinding point
  * is KeccakHash::<32>(F::ZERO) * G of its curve, so the point arguments of p2e_curve_program_create are ignored (may be
  * NULL) and its witness is a pure function of (p, q, n, m).  Fill: p2e_curve_msm_witness[_compact]_batch; aux kinds 1
  * split2 (261 bits + 131 digits per scalar) and 3 MSM digit [index, selected x (9), selected y (9), is_zero, should_add,
  * not_b, sum.x*b, sum.y*b, p1.x*not_b, p1.y*not_b]; its wiring reads q through P2E_SRC_INPUT slots 5 (q.x) and 6 (q.y).
- * The constraint-block pass does not take the MSM program yet (p2e_curve_program_ux_witness_batch has no slot for q:
- * it returns P2E_E_INVALID).
+ * Its constraint-block pass is p2e_curve_msm_ux_witness_batch (u64 matrices) or
+ * p2e_curve_program_ux_witness_compact_batch; p2e_curve_program_ux_witness_batch has no slot for q and returns
+ * P2E_E_INVALID for it.
  * The fixed-base program multiplies a CONSTANT base: the point arguments of p2e_curve_program_create are that base
  * (canonical, on the program's curve); its fill is p2e_curve_mul_witness[_compact]_batch with px32 = py32 = NULL. */
 #define P2E_CURVE_SECP256K1 0
@@ -412,6 +432,26 @@ long p2e_curve_program_ux_witness_batch(p2e_ctx *ctx, const p2e_curve_program *p
                                         const uint8_t *s32, const uint8_t *pkx32, const uint8_t *pky32, const uint64_t *cols,
                                         size_t ld, const uint64_t *aux, size_t ld_aux, void *ux, int ux_u32, size_t ld_ux, size_t n,
                                         uint8_t *err);
+/* the MSM program's constraint-block pass on the u64 matrices (argument order of p2e_curve_msm_witness_batch) */
+long p2e_curve_msm_ux_witness_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint8_t *px32, const uint8_t *py32,
+                                    const uint8_t *qx32, const uint8_t *qy32, const uint8_t *n32, const uint8_t *m32,
+                                    const uint64_t *cols, size_t ld, const uint64_t *aux, size_t ld_aux, void *ux, int ux_u32,
+                                    size_t ld_ux, size_t n, uint8_t *err);
+/* The three passes inside the compact container (as p2e_aux_witness_compact_batch / p2e_gate_internal_compact_batch /
+ * p2e_ux_witness_compact_batch): narrow is the u32 matrix of the program's compact fill, aux32 the u32 aux matrix.  The
+ * constraint-block pass takes every program kind: qx32 / qy32 are required for P2E_CP_MSM and ignored (may be NULL)
+ * otherwise. */
+long p2e_curve_program_aux_witness_compact_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint8_t *msg32,
+                                                 const uint8_t *r32, const uint8_t *s32, const uint8_t *pkx32,
+                                                 const uint8_t *pky32, const uint32_t *narrow, size_t ld_narrow,
+                                                 uint32_t *aux32, size_t ld_aux, size_t n, uint8_t *err);
+long p2e_curve_program_gate_internal_compact_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint32_t *aux32,
+                                                   size_t ld_aux, uint64_t *gate, size_t ld_gate, size_t n);
+long p2e_curve_program_ux_witness_compact_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const uint8_t *msg32,
+                                                const uint8_t *r32, const uint8_t *s32, const uint8_t *pkx32,
+                                                const uint8_t *pky32, const uint8_t *qx32, const uint8_t *qy32,
+                                                const uint32_t *narrow, size_t ld_narrow, const uint32_t *aux32, size_t ld_aux,
+                                                void *ux, int ux_u32, size_t ld_ux, size_t n, uint8_t *err);
 /* replaces the run_once bodies of every generator curve_scalar_mul_windowed / curve_scalar_mul registers for a batch
  * of (point, scalar) pairs; cols[num_cols][ld].  valid: always 1 unless flagged (the gadgets connect nothing).
  * The fixed-base program (P2E_CP_FIXED_BASE_MUL) takes the scalars alone: px32 = py32 = NULL (ignored if given); the

@@ -71,6 +71,9 @@ EXPORTS = (
     "p2e_curve_program_wire_map_create", "p2e_p256_verify_batch",
     "p2e_curve_mul_witness_compact_batch", "p2e_p256_verify_witness_compact_batch", "p2e_curve_program_compact_layout",
     "p2e_curve_msm_witness_batch", "p2e_curve_msm_witness_compact_batch",
+    "p2e_ux_witness_compact_batch", "p2e_gate_internal_compact_batch", "p2e_assemble_wires_compact",
+    "p2e_curve_program_aux_witness_compact_batch", "p2e_curve_program_gate_internal_compact_batch",
+    "p2e_curve_program_ux_witness_compact_batch", "p2e_curve_msm_ux_witness_batch",
 )
 
 
@@ -150,7 +153,8 @@ def lib():
                                                    "p2e_curve_program_num_aux_cols", "p2e_curve_program_describe",
                                                    "p2e_curve_program_wiring", "p2e_curve_program_aux_describe",
                                                    "p2e_curve_program_num_gate_cols", "p2e_curve_program_num_ux_cols",
-                                                   "p2e_curve_program_ux_describe", "p2e_curve_program_compact_layout"):
+                                                   "p2e_curve_program_ux_describe", "p2e_curve_program_compact_layout",
+                                                   "p2e_assemble_wires", "p2e_assemble_wires_compact"):
                 getattr(_lib, name).restype = C.c_long
         _lib.p2e_curve_program_scratch_bytes.restype = C.c_size_t
     return _lib
@@ -183,6 +187,10 @@ def _ptr(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(C.c_void_p)
     return C.c_void_p(a.data_ptr())
+
+
+def _is_u32(a):
+    return (a.dtype == np.uint32) if isinstance(a, np.ndarray) else (a.element_size() == 4)
 
 
 def schedule_describe(program: int = PROGRAM_VERIFY):
@@ -530,6 +538,63 @@ class CurveProgram:
                                                                    C.c_int(1 if u32 else 0), C.c_size_t(_ld(ux)), C.c_size_t(n), _ptr(err)))
         return ux, err, bad
 
+    # ---- the same three passes inside the compact container (include/p2e.h *_compact_batch) -----------------------
+    def _ux_out(self, n, ux, u32):
+        ctx = self._ctx
+        if ux is None:
+            return ctx._mat(self.num_ux_cols, n, u32), u32
+        return ux, _is_u32(ux)
+
+    def aux_witness_compact_batch(self, inputs, narrow, n=None, ld_narrow=None, aux32=None, err=None):
+        """aux_witness_batch reading the narrow u32 matrix of the program's compact fill: (num_aux_cols, n) u32"""
+        ctx = self._ctx
+        msg, r, s, px, py = self._inputs(inputs)
+        n = n if n is not None else ctx._shape(msg)[0]
+        ld_narrow = ld_narrow if ld_narrow is not None else _ld(narrow)
+        aux32 = aux32 if aux32 is not None else ctx._mat(self.num_aux_cols, n, True)
+        err = err if err is not None else ctx._vec(n, np.uint8)
+        bad = ctx._check(ctx._L.p2e_curve_program_aux_witness_compact_batch(
+            ctx._h, self._h, _ptr(msg), _ptr(r), _ptr(s), _ptr(px), _ptr(py), _ptr(narrow), C.c_size_t(ld_narrow), _ptr(aux32),
+            C.c_size_t(_ld(aux32)), C.c_size_t(n), _ptr(err)))
+        return aux32, err, bad
+
+    def gate_internal_compact_batch(self, aux32, n=None, gate=None):
+        """gate_internal_batch from the u32 aux matrix: (num_gate_cols, n) u64"""
+        ctx = self._ctx
+        n = n if n is not None else aux32.shape[1]
+        gate = gate if gate is not None else ctx._cols(self.num_gate_cols, n)
+        ctx._check(ctx._L.p2e_curve_program_gate_internal_compact_batch(ctx._h, self._h, _ptr(aux32), C.c_size_t(_ld(aux32)), _ptr(gate),
+                                                                        C.c_size_t(_ld(gate)), C.c_size_t(n)))
+        return gate
+
+    def ux_witness_compact_batch(self, inputs, narrow, aux32, n=None, ld_narrow=None, ux=None, err=None, u32=True):
+        """ux_witness_batch from the narrow u32 matrix and the u32 aux matrix; every program kind (the MSM program's
+        6-tuple carries q): (num_ux_cols, n) u32 / u64"""
+        ctx = self._ctx
+        msg, r, s, px, py = self._inputs(inputs)
+        qx, qy = (inputs[2], inputs[3]) if len(inputs) == 6 else (None, None)
+        n = n if n is not None else ctx._shape(msg)[0]
+        ld_narrow = ld_narrow if ld_narrow is not None else _ld(narrow)
+        ux, u32 = self._ux_out(n, ux, u32)
+        err = err if err is not None else ctx._vec(n, np.uint8)
+        bad = ctx._check(ctx._L.p2e_curve_program_ux_witness_compact_batch(
+            ctx._h, self._h, _ptr(msg), _ptr(r), _ptr(s), _ptr(px), _ptr(py), _ptr(qx), _ptr(qy), _ptr(narrow), C.c_size_t(ld_narrow),
+            _ptr(aux32), C.c_size_t(_ld(aux32)), _ptr(ux), C.c_int(1 if u32 else 0), C.c_size_t(_ld(ux)), C.c_size_t(n), _ptr(err)))
+        return ux, err, bad
+
+    def msm_ux_witness_batch(self, inputs, cols, aux, n=None, ld=None, ux=None, err=None, u32=True):
+        """CP_MSM: the constraint-block pass on the u64 matrices; inputs = (px, py, qx, qy, n, m)"""
+        ctx = self._ctx
+        px, py, qx, qy, ns, ms = inputs
+        n = n if n is not None else ctx._shape(px)[0]
+        ld = ld if ld is not None else _ld(cols)
+        ux, u32 = self._ux_out(n, ux, u32)
+        err = err if err is not None else ctx._vec(n, np.uint8)
+        bad = ctx._check(ctx._L.p2e_curve_msm_ux_witness_batch(
+            ctx._h, self._h, _ptr(px), _ptr(py), _ptr(qx), _ptr(qy), _ptr(ns), _ptr(ms), _ptr(cols), C.c_size_t(ld), _ptr(aux),
+            C.c_size_t(_ld(aux)), _ptr(ux), C.c_int(1 if u32 else 0), C.c_size_t(_ld(ux)), C.c_size_t(n), _ptr(err)))
+        return ux, err, bad
+
     def verify_batch(self, msg, r, s, pkx, pky, err=None, valid=None):
         """the verifier circuit's verdict alone (no witness): (err, valid, flagged count)"""
         ctx = self._ctx
@@ -651,6 +716,13 @@ class Context:
             return np.zeros((k, n), dtype=np.uint64)
         import torch
         return torch.empty((k, n), dtype=torch.int64, device=f"cuda:{self.device}")
+
+    def _mat(self, k, n, u32):
+        """(k, n) u32 or u64 matrix"""
+        if self.host_pointers:
+            return np.zeros((k, n), dtype=np.uint32 if u32 else np.uint64)
+        import torch
+        return torch.empty((k, n), dtype=torch.int32 if u32 else torch.int64, device=f"cuda:{self.device}")
 
     def _vec(self, n, dtype=np.uint64):
         if self.host_pointers:
@@ -979,6 +1051,62 @@ class Context:
                                                                 C.c_size_t(ld_narrow), _ptr(aux32), C.c_size_t(ld_aux),
                                                                 C.c_size_t(n), _ptr(err)))
         return aux32, err, bad
+
+    def gate_internal_compact_batch(self, program, aux32, n=None, ld_aux=None, gate=None, ld_gate=None):
+        """gate_internal_batch from the u32 aux matrix of aux_witness_compact_batch: (10703 | 5621, n) uint64."""
+        n = n if n is not None else self._shape(aux32)[1]
+        ld_aux = ld_aux if ld_aux is not None else _ld(aux32)
+        if gate is None:
+            gate = self._cols(VERIFY_GATE_COLS if program == PROGRAM_VERIFY else GLV_MUL_GATE_COLS, n)
+        ld_gate = ld_gate if ld_gate is not None else _ld(gate)
+        self._check(self._L.p2e_gate_internal_compact_batch(self._h, C.c_int(program), _ptr(aux32), C.c_size_t(ld_aux), _ptr(gate),
+                                                            C.c_size_t(ld_gate), C.c_size_t(n)))
+        return gate
+
+    def ux_witness_compact_batch(self, program, inputs, narrow, aux32, n=None, ld_narrow=None, ld_aux=None, ux=None, ld_ux=None,
+                                 err=None, u32=True):
+        """ux_witness_batch inside the compact container: reads the narrow u32 matrix and the u32 aux matrix (same values,
+        half the bytes read).  inputs as ux_witness_batch."""
+        if program == PROGRAM_VERIFY:
+            msg, r, s, pkx, pky = inputs
+        else:
+            pkx, pky, msg = inputs
+            r = s = None
+        n = n if n is not None else self._shape(pky)[0]
+        ld_narrow = ld_narrow if ld_narrow is not None else _ld(narrow)
+        ld_aux = ld_aux if ld_aux is not None else _ld(aux32)
+        if ux is None:
+            ux = self._mat(VERIFY_UX_COLS if program == PROGRAM_VERIFY else GLV_MUL_UX_COLS, n, u32)
+        else:
+            u32 = _is_u32(ux)
+        ld_ux = ld_ux if ld_ux is not None else _ld(ux)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_ux_witness_compact_batch(
+            self._h, C.c_int(program), _ptr(msg), _ptr(r), _ptr(s), _ptr(pkx), _ptr(pky), _ptr(narrow), C.c_size_t(ld_narrow),
+            _ptr(aux32), C.c_size_t(ld_aux), _ptr(ux), C.c_int(1 if u32 else 0), C.c_size_t(ld_ux), C.c_size_t(n), _ptr(err)))
+        return ux, err, bad
+
+    def assemble_wires_compact(self, wmap, narrow=None, wide=None, aux32=None, ux=None, gate=None, wires=None, n=None):
+        """assemble_wires from the compact container and the u32 aux matrix; the same map serves both.  narrow / wide may
+        be None if no entry of the map names a column of it."""
+        ref = next(m for m in (narrow, wide, aux32, ux, gate) if m is not None)
+        n = n if n is not None else self._shape(ref)[1]
+        cells = wmap.num_wires * wmap.degree
+        if wires is None:
+            if self.host_pointers:
+                wires = np.zeros((n, cells), dtype=np.uint64)
+            else:
+                import torch
+                wires = torch.zeros((n, cells), dtype=torch.int64, device=f"cuda:{self.device}")
+        u32 = int(_is_u32(ux)) if ux is not None else 0
+
+        def ld(m):
+            return C.c_size_t(_ld(m) if m is not None else 0)
+
+        self._check(self._L.p2e_assemble_wires_compact(self._h, wmap._h, _ptr(narrow), ld(narrow), _ptr(wide), ld(wide), _ptr(aux32),
+                                                       ld(aux32), _ptr(ux), C.c_int(u32), ld(ux), _ptr(gate), ld(gate), _ptr(wires),
+                                                       C.c_size_t(_ld(wires)), C.c_size_t(n)))
+        return wires
 
     def glv_mul_witness_batch(self, px, py, k, cols=None, err=None, valid=None, ld=None):
         """glv_mul (gadgets/glv.rs:87-104): (65243, n) Goldilocks columns."""

@@ -192,6 +192,7 @@ struct GateArgs {
     size_t gld, n;
     const GateItem* items;
     u64 inv16[16];  // Goldilocks inverses of 0..15 (inv16[0] = 0)
+    const u32* aux32;   // compact source (body_gate<E, true>): the u32 aux matrix, stride ald
 };
 template <class E>
 P2E_HD void gate_put_eq(E& e, u32 idx, const u64* inv16) {
@@ -210,10 +211,10 @@ P2E_HD void gate_put_ra(E& e, u32 idx) {
         for (int b = 0; b < 4; b++) e.put((idx >> b) & 1u);
     }
 }
-template <class E>
+template <class E, bool CS = false>
 P2E_HD void body_gate(const GateArgs& A, int item, size_t i) {
     const GateItem it = A.items[item];
-    const u32 idx = (u32)A.aux[(size_t)it.idx_col * A.ald + i] & 15u;
+    const u32 idx = (CS ? A.aux32[(size_t)it.idx_col * A.ald + i] : (u32)A.aux[(size_t)it.idx_col * A.ald + i]) & 15u;
     // the 16 inverses: a register select chain would be long; they sit in the kernel arguments (scalar loads)
     E e = E::at(A.gate, A.gld, i, it.gate_col);
     if (it.ra_first) {

@@ -87,6 +87,11 @@ __global__ __launch_bounds__(BS) void kc_ux(UxArgs A, size_t first) {
     size_t i = lane_sig<(MODE & 1) != 0>(first);
     if ((MODE & 1) || i < A.n) body_ux_cv<typename AuxEmitOf<MODE>::type>(A, (int)blockIdx.y, i);
 }
+template <int MODE>
+__global__ __launch_bounds__(BS) void kc_ux_compact(UxArgs A, size_t first) {
+    size_t i = lane_sig<(MODE & 1) != 0>(first);
+    if ((MODE & 1) || i < A.n) body_ux_cv<typename AuxEmitOf<MODE>::type, true>(A, (int)blockIdx.y, i);
+}
 
 #endif   // P2E_HAS(0)
 
@@ -101,6 +106,7 @@ struct p2e_curve_program {
     AuxTables* d_aux_tab = nullptr;
     GateItem* d_gate_items = nullptr;
     UxItem* d_ux_items = nullptr;
+    UxItem* d_ux_items_compact = nullptr;   // in compact coordinates (host::ux_items_compact)
     U256* d_constv = nullptr;   // constants by source id: points at 2c / 2c + 1, scalar constants from AUX_GCONST_BASE
     // compact container (include/p2e.h p2e_curve_program_compact_layout): per column its slot in the u32 narrow matrix
     // or COMPACT_WIDE | slot in the u64 wide matrix (the check_sum / carry columns of the mul generators), in
@@ -174,6 +180,20 @@ extern "C" int p2e_curve_program_create(p2e_ctx* c, int kind, int curve, const u
         set_error("curve program: an aux item reads q (input slot 5 / 6), which the aux pass has no argument for");
         return P2E_E_INVALID;
     }
+    {   // compact container layout (as build_compact_map of the built-in programs), and the host-only check of what the
+        // compact-source ux pass walks: before anything is allocated on the device
+        host::CompactLayout L = host::compact_layout(P->H.sb.gens, (size_t)P->H.sb.prog.num_cols);
+        P->compact_map = std::move(L.map);
+        P->wide_before = std::move(L.wide_before);
+        P->num_narrow = L.num_narrow;
+        P->num_wide = L.num_wide;
+        std::string why;
+        if (!host::ux_items_compact_ok(P->H.sb.ux_items, P->compact_map, why)) {
+            delete P;
+            set_error(why);
+            return P2E_E_INVALID;
+        }
+    }
     DeviceGuard guard(c->device);
     P->device = c->device;
     struct Cleanup {
@@ -208,16 +228,10 @@ extern "C" int p2e_curve_program_create(p2e_ctx* c, int kind, int curve, const u
     }
     HIP_TRY(hipMalloc(&P->d_ux_items, sizeof(UxItem) * sb.ux_items.size()));
     HIP_TRY(hipMemcpy(P->d_ux_items, sb.ux_items.data(), sizeof(UxItem) * sb.ux_items.size(), hipMemcpyHostToDevice));
-    {   // compact container layout: as build_compact_map of the built-in programs
-        P->compact_map.assign((size_t)sb.prog.num_cols, 0);
-        for (const auto& g : sb.gens)
-            for (u32 k = 0; k < g.ncols; k++) {
-                const bool wide = g.kind == host::GEN_MUL && k >= 2 * NL;
-                P->compact_map[g.col + k] = wide ? (0x80000000u | P->num_wide++) : P->num_narrow++;
-            }
-        P->wide_before.assign((size_t)sb.prog.num_cols + 1, 0);
-        for (size_t col = 0; col < P->compact_map.size(); col++)
-            P->wide_before[col + 1] = P->wide_before[col] + ((P->compact_map[col] & 0x80000000u) ? 1u : 0u);
+    {
+        const std::vector<UxItem> cux = host::ux_items_compact(sb.ux_items, P->compact_map);
+        HIP_TRY(hipMalloc(&P->d_ux_items_compact, sizeof(UxItem) * cux.size()));
+        HIP_TRY(hipMemcpy(P->d_ux_items_compact, cux.data(), sizeof(UxItem) * cux.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMalloc(&P->d_wide_before, sizeof(u32) * P->wide_before.size()));
         HIP_TRY(hipMemcpy(P->d_wide_before, P->wide_before.data(), sizeof(u32) * P->wide_before.size(), hipMemcpyHostToDevice));
     }
@@ -247,6 +261,7 @@ extern "C" void p2e_curve_program_destroy(p2e_ctx* c, p2e_curve_program* P) {
     (void)hipFree(P->d_aux_tab);
     (void)hipFree(P->d_gate_items);
     (void)hipFree(P->d_ux_items);
+    (void)hipFree(P->d_ux_items_compact);
     (void)hipFree(P->d_constv);
     (void)hipFree(P->d_wide_before);
     delete P;
@@ -714,6 +729,15 @@ static bool curve_msm_args_ok(const p2e_curve_program* P) {
     }
     return true;
 }
+// what the MSM program's constraint-block pass reads, in either container: p, q and both scalars (n in msg32, m in r32)
+static bool curve_msm_ux_inputs_ok(const uint8_t* px, const uint8_t* py, const uint8_t* qx, const uint8_t* qy, const uint8_t* n32,
+                                   const uint8_t* m32) {
+    if (!px || !py || !qx || !qy || !n32 || !m32) {
+        set_error("the MSM program's constraint-block pass reads p, q, n and m: none of their pointers may be NULL");
+        return false;
+    }
+    return true;
+}
 // the verifier circuit's verdict alone: valid[i] = curve_assert_valid's connect and r == x both hold (and no error
 // flag), no witness written -- a pre-filter for invalid signatures; native counterpart curve/ecdsa.rs:42-62
 // verify_message on P-256, with exactly the circuit's verdict
@@ -810,6 +834,52 @@ static bool curve_inputs_ok(const p2e_curve_program* P, const uint8_t* msg, cons
 }
 // built-in-generator targets (split bits / digits, is_equal / not, random-access selections, bool products) from the
 // finished witness matrix: aux[num_aux_cols][ld_aux], order and layout p2e_curve_program_aux_describe
+// cols == nullptr: read the compact container's narrow matrix and write the u32 aux matrix (as run_aux)
+static long run_curve_aux(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
+                          const uint8_t* pkx32, const uint8_t* pky32, const uint64_t* cols, size_t ld, const uint32_t* narrow, size_t ldn,
+                          void* aux, size_t ld_aux, size_t n, uint8_t* err) {
+    const bool compact = cols == nullptr;
+    const host::ScheduleBuilder& sb = P->H.sb;
+    Staged S(c);
+    msg32 = S.in(msg32, 32 * n);
+    if (r32) r32 = S.in(r32, 32 * n);
+    if (s32) s32 = S.in(s32, 32 * n);
+    if (pkx32) pkx32 = S.in(pkx32, 32 * n);
+    if (pky32) pky32 = S.in(pky32, 32 * n);
+    if (compact)
+        narrow = S.in(narrow, (size_t)P->num_narrow * ldn * 4);
+    else
+        cols = S.in(cols, (size_t)sb.prog.num_cols * ld * 8);
+    aux = S.out((char*)aux, (size_t)sb.aux_tab.num_aux_cols * ld_aux * (compact ? 4 : 8));
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    if (int rc = ensure_scratch(c, n * sizeof(u32))) return S.done(rc);
+    ZERO_COUNTER(c);
+    u32* err32 = (u32*)c->scratch;
+    HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
+    AuxArgs A{cols, ld, aux, ld_aux, n, pky32, P->d_cpts, P->d_fbtab, P->d_aux_items, P->d_aux_tab, err32, narrow, ldn,
+              compact ? P->d_wide_before : nullptr, {}};
+    A.in[INPUT_PY] = pky32;
+    A.in[INPUT_PX] = pkx32;
+    A.in[INPUT_MSG] = msg32;
+    A.in[INPUT_R] = r32 ? r32 : msg32;
+    A.in[INPUT_S] = s32 ? s32 : msg32;
+    // (A.in[INPUT_QX / INPUT_QY] stay null: p2e_curve_program_create refuses a program whose aux items would read q)
+    const unsigned gx = (unsigned)((n + BS - 1) / BS), items = (unsigned)sb.aux_items.size();
+    const bool wide_ok = (ld_aux % 2 == 0) && ((reinterpret_cast<uintptr_t>(aux) & (compact ? 7 : 15)) == 0) && !getenv("P2E_NARROW_STORES");
+    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
+    const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
+    if (compact) {
+        if (n_wide) hipLaunchKernelGGL(kc_aux<3>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
+        if (n > n_wide) hipLaunchKernelGGL(kc_aux<2>, gt, dim3(BS), 0, c->stream, A, n_wide);
+    } else {
+        if (n_wide) hipLaunchKernelGGL(kc_aux<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
+        if (n > n_wide) hipLaunchKernelGGL(kc_aux<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
+    }
+    hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, err32, (const uint8_t*)nullptr, err, (uint8_t*)nullptr, n, c->d_counter);
+    c->have_phases = false;
+    return S.done(finish_call(c));
+}
 extern "C" long p2e_curve_program_aux_witness_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg32, const uint8_t* r32,
                                                     const uint8_t* s32, const uint8_t* pkx32, const uint8_t* pky32, const uint64_t* cols,
                                                     size_t ld, uint64_t* aux, size_t ld_aux, size_t n, uint8_t* err) {
@@ -818,79 +888,90 @@ extern "C" long p2e_curve_program_aux_witness_batch(p2e_ctx* c, const p2e_curve_
         return P2E_E_INVALID;
     }
     if (n == 0) return 0;
-    const host::ScheduleBuilder& sb = P->H.sb;
-    Staged S(c);
-    msg32 = S.in(msg32, 32 * n);
-    if (r32) r32 = S.in(r32, 32 * n);
-    if (s32) s32 = S.in(s32, 32 * n);
-    if (pkx32) pkx32 = S.in(pkx32, 32 * n);
-    if (pky32) pky32 = S.in(pky32, 32 * n);
-    cols = S.in(cols, (size_t)sb.prog.num_cols * ld * 8);
-    aux = S.out(aux, (size_t)sb.aux_tab.num_aux_cols * ld_aux * 8);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    if (int rc = ensure_scratch(c, n * sizeof(u32))) return S.done(rc);
-    ZERO_COUNTER(c);
-    u32* err32 = (u32*)c->scratch;
-    HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
-    AuxArgs A{cols, ld, aux, ld_aux, n, pky32, P->d_cpts, P->d_fbtab, P->d_aux_items, P->d_aux_tab, err32, nullptr, 0, nullptr, {}};
-    A.in[INPUT_PY] = pky32;
-    A.in[INPUT_PX] = pkx32;
-    A.in[INPUT_MSG] = msg32;
-    A.in[INPUT_R] = r32 ? r32 : msg32;
-    A.in[INPUT_S] = s32 ? s32 : msg32;
-    // (A.in[INPUT_QX / INPUT_QY] stay null: p2e_curve_program_create refuses a program whose aux items would read q)
-    const unsigned gx = (unsigned)((n + BS - 1) / BS), items = (unsigned)sb.aux_items.size();
-    const bool wide_ok = (ld_aux % 2 == 0) && ((reinterpret_cast<uintptr_t>(aux) & 15) == 0) && !getenv("P2E_NARROW_STORES");
-    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
-    const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
-    if (n_wide) hipLaunchKernelGGL(kc_aux<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
-    if (n > n_wide) hipLaunchKernelGGL(kc_aux<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
-    hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, err32, (const uint8_t*)nullptr, err, (uint8_t*)nullptr, n, c->d_counter);
-    c->have_phases = false;
-    return S.done(finish_call(c));
+    return run_curve_aux(c, P, msg32, r32, s32, pkx32, pky32, cols, ld, nullptr, 0, aux, ld_aux, n, err);
 }
-// gate-internal values of the built-in gates behind the windows (is_equal internals, RandomAccessGate index bits), from
-// the aux matrix: gate[num_gate_cols][ld_gate] (curve_scalar_mul has none)
-extern "C" long p2e_curve_program_gate_internal_batch(p2e_ctx* c, const p2e_curve_program* P, const uint64_t* aux, size_t ld_aux,
-                                                      uint64_t* gate, size_t ld_gate, size_t n) {
-    if (bad_common(c, n, ld_aux) || !P || !aux || !gate || ld_gate < n || P->H.sb.gate_items.empty()) {
-        if (c && P && P->H.sb.gate_items.empty()) set_error("this program has no gate-internal values");
+extern "C" long p2e_curve_program_aux_witness_compact_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg32,
+                                                            const uint8_t* r32, const uint8_t* s32, const uint8_t* pkx32,
+                                                            const uint8_t* pky32, const uint32_t* narrow, size_t ld_narrow, uint32_t* aux32,
+                                                            size_t ld_aux, size_t n, uint8_t* err) {
+    if (bad_common(c, n, ld_narrow) || !curve_inputs_ok(P, msg32, r32, s32, pkx32, pky32) || !narrow || !aux32 || !err || ld_aux < n) {
+        if (c && ld_aux < n) set_error("ld_aux < n");
         return P2E_E_INVALID;
     }
     if (n == 0) return 0;
+    return run_curve_aux(c, P, msg32, r32, s32, pkx32, pky32, nullptr, 0, narrow, ld_narrow, aux32, ld_aux, n, err);
+}
+// gate-internal values of the built-in gates behind the windows (is_equal internals, RandomAccessGate index bits), from
+// the aux matrix: gate[num_gate_cols][ld_gate] (curve_scalar_mul has none)
+static bool curve_gate_args_ok(p2e_ctx* c, const p2e_curve_program* P, const void* aux, size_t ld_aux, const uint64_t* gate, size_t ld_gate,
+                               size_t n) {
+    if (bad_common(c, n, ld_aux) || !P || !aux || !gate || ld_gate < n || P->H.sb.gate_items.empty()) {
+        if (c && P && P->H.sb.gate_items.empty()) set_error("this program has no gate-internal values");
+        return false;
+    }
+    return true;
+}
+extern "C" long p2e_curve_program_gate_internal_batch(p2e_ctx* c, const p2e_curve_program* P, const uint64_t* aux, size_t ld_aux,
+                                                      uint64_t* gate, size_t ld_gate, size_t n) {
+    if (!curve_gate_args_ok(c, P, aux, ld_aux, gate, ld_gate, n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
     const host::ScheduleBuilder& sb = P->H.sb;
-    Staged S(c);
-    aux = S.in(aux, (size_t)sb.aux_tab.num_aux_cols * ld_aux * 8);
-    gate = S.out(gate, (size_t)sb.num_gate_cols * ld_gate * 8);
-    if (S.rc) return S.done(S.rc);
-    ZERO_COUNTER(c);
-    GateArgs A{};
-    A.aux = aux;
-    A.ald = ld_aux;
-    A.gate = gate;
-    A.gld = ld_gate;
-    A.n = n;
-    A.items = P->d_gate_items;
-    A.inv16[0] = 0;
-    for (u64 d = 1; d < 16; d++) A.inv16[d] = gl_pow_host(d, P_GL - 2);
-    const unsigned items = (unsigned)sb.gate_items.size();
-    const bool wide_ok = (ld_gate % 2 == 0) && ((reinterpret_cast<uintptr_t>(gate) & 15) == 0) && !getenv("P2E_NARROW_STORES");
-    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
-    const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
-    if (n_wide) hipLaunchKernelGGL(k_gate<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
-    if (n > n_wide) hipLaunchKernelGGL(k_gate<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
-    c->have_phases = false;
-    return S.done(finish_call(c));
+    return run_gate(c, aux, false, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, P->d_gate_items,
+                    (unsigned)sb.gate_items.size());
+}
+extern "C" long p2e_curve_program_gate_internal_compact_batch(p2e_ctx* c, const p2e_curve_program* P, const uint32_t* aux32, size_t ld_aux,
+                                                              uint64_t* gate, size_t ld_gate, size_t n) {
+    if (!curve_gate_args_ok(c, P, aux32, ld_aux, gate, ld_gate, n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    const host::ScheduleBuilder& sb = P->H.sb;
+    return run_gate(c, aux32, true, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, P->d_gate_items,
+                    (unsigned)sb.gate_items.size());
 }
 // constraint-block (U29 gate) values from the finished witness and aux matrices: ux[num_ux_cols][ld_ux], u32 or u64
+static UxCall curve_ux_call(const p2e_curve_program* P, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32, const uint8_t* pkx32,
+                            const uint8_t* pky32, const uint8_t* qx32, const uint8_t* qy32, void* ux, int ux_u32, size_t ld_ux, size_t n,
+                            uint8_t* err) {
+    const host::ScheduleBuilder& sb = P->H.sb;
+    UxCall U;
+    U.in[INPUT_PY] = pky32;
+    U.in[INPUT_PX] = pkx32;
+    U.in[INPUT_MSG] = msg32;
+    U.in[INPUT_R] = r32;
+    U.in[INPUT_S] = s32;
+    if (P->H.kind == CP_MSM) {
+        U.in[INPUT_QX] = qx32;
+        U.in[INPUT_QY] = qy32;
+    }
+    U.ux = ux;
+    U.ux_u32 = ux_u32;
+    U.ld_ux = ld_ux;
+    U.n = n;
+    U.err = err;
+    U.num_cols = (u32)sb.prog.num_cols;
+    U.num_narrow = P->num_narrow;
+    U.num_aux_cols = sb.aux_tab.num_aux_cols;
+    U.num_ux_cols = sb.num_ux_cols;
+    U.d_consts = P->d_constv;
+    U.d_items = P->d_ux_items;
+    U.d_items_compact = P->d_ux_items_compact;
+    U.items = (unsigned)sb.ux_items.size();
+    return U;
+}
+static long run_curve_ux_u64(p2e_ctx* c, UxCall U, const uint64_t* cols, size_t ld, const uint64_t* aux, size_t ld_aux) {
+    U.cols = cols;
+    U.ld = ld;
+    U.aux = aux;
+    U.ld_aux = ld_aux;
+    static const UxKernel kern[4] = {kc_ux<0>, kc_ux<1>, kc_ux<2>, kc_ux<3>};
+    return run_ux(c, U, kern);
+}
 extern "C" long p2e_curve_program_ux_witness_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg32, const uint8_t* r32,
                                                    const uint8_t* s32, const uint8_t* pkx32, const uint8_t* pky32, const uint64_t* cols,
                                                    size_t ld, const uint64_t* aux, size_t ld_aux, void* ux, int ux_u32, size_t ld_ux,
                                                    size_t n, uint8_t* err) {
     if (c && P && P->H.kind == CP_MSM) {
-        // (follow-up: this entry point has no slot for q, which the MSM's table additions read)
-        set_error("the constraint-block pass does not support the MSM program yet (its signature has no slot for q)");
+        set_error("the constraint-block pass of the MSM program reads q, and this signature has no slot for q: call "
+                  "p2e_curve_msm_ux_witness_batch (u64 matrices) or p2e_curve_program_ux_witness_compact_batch");
         return P2E_E_INVALID;
     }
     if (bad_common(c, n, ld) || !curve_inputs_ok(P, msg32, r32, s32, pkx32, pky32) || !cols || !aux || !ux || !err || ld_aux < n || ld_ux < n) {
@@ -898,52 +979,42 @@ extern "C" long p2e_curve_program_ux_witness_batch(p2e_ctx* c, const p2e_curve_p
         return P2E_E_INVALID;
     }
     if (n == 0) return 0;
-    const host::ScheduleBuilder& sb = P->H.sb;
-    Staged S(c);
-    msg32 = S.in(msg32, 32 * n);
-    if (r32) r32 = S.in(r32, 32 * n);
-    if (s32) s32 = S.in(s32, 32 * n);
-    if (pkx32) pkx32 = S.in(pkx32, 32 * n);
-    if (pky32) pky32 = S.in(pky32, 32 * n);
-    cols = S.in(cols, (size_t)sb.prog.num_cols * ld * 8);
-    aux = S.in(aux, (size_t)sb.aux_tab.num_aux_cols * ld_aux * 8);
-    ux = S.out((char*)ux, (size_t)sb.num_ux_cols * ld_ux * (ux_u32 ? 4 : 8));
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    if (int rc = ensure_scratch(c, n * sizeof(u32))) return S.done(rc);
-    ZERO_COUNTER(c);
-    u32* err32 = (u32*)c->scratch;
-    HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
-    UxArgs A{};
-    A.cols = cols;
-    A.ld = ld;
-    A.aux = aux;
-    A.ald = ld_aux;
-    A.ux = ux;
-    A.uld = ld_ux;
-    A.n = n;
-    A.in[INPUT_PY] = pky32;
-    A.in[INPUT_PX] = pkx32;
-    A.in[INPUT_MSG] = msg32;
-    A.in[INPUT_R] = r32 ? r32 : msg32;
-    A.in[INPUT_S] = s32 ? s32 : msg32;
-    A.consts = P->d_constv;
-    A.items = P->d_ux_items;
-    A.err = err32;
-    const unsigned gx = (unsigned)((n + BS - 1) / BS), items = (unsigned)sb.ux_items.size();
-    const bool wide_ok = (ld_ux % 2 == 0) && ((reinterpret_cast<uintptr_t>(ux) & (ux_u32 ? 7 : 15)) == 0) && !getenv("P2E_NARROW_STORES");
-    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
-    const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
-    if (ux_u32) {
-        if (n_wide) hipLaunchKernelGGL(kc_ux<3>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
-        if (n > n_wide) hipLaunchKernelGGL(kc_ux<2>, gt, dim3(BS), 0, c->stream, A, n_wide);
-    } else {
-        if (n_wide) hipLaunchKernelGGL(kc_ux<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
-        if (n > n_wide) hipLaunchKernelGGL(kc_ux<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
+    return run_curve_ux_u64(c, curve_ux_call(P, msg32, r32, s32, pkx32, pky32, nullptr, nullptr, ux, ux_u32, ld_ux, n, err), cols, ld, aux,
+                            ld_aux);
+}
+// the MSM program's pass on the u64 matrices: its table additions read q (P2E_SRC_INPUT slots 5 and 6)
+extern "C" long p2e_curve_msm_ux_witness_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* px32, const uint8_t* py32,
+                                               const uint8_t* qx32, const uint8_t* qy32, const uint8_t* n32, const uint8_t* m32,
+                                               const uint64_t* cols, size_t ld, const uint64_t* aux, size_t ld_aux, void* ux, int ux_u32,
+                                               size_t ld_ux, size_t n, uint8_t* err) {
+    if (bad_common(c, n, ld) || !P || !cols || !aux || !ux || !err || ld_aux < n || ld_ux < n) {
+        if (c && ld >= n && (ld_aux < n || ld_ux < n)) set_error("ld_aux / ld_ux < n");
+        return P2E_E_INVALID;
     }
-    hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, err32, (const uint8_t*)nullptr, err, (uint8_t*)nullptr, n, c->d_counter);
-    c->have_phases = false;
-    return S.done(finish_call(c));
+    if (!curve_msm_args_ok(P) || !curve_msm_ux_inputs_ok(px32, py32, qx32, qy32, n32, m32)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    return run_curve_ux_u64(c, curve_ux_call(P, n32, m32, nullptr, px32, py32, qx32, qy32, ux, ux_u32, ld_ux, n, err), cols, ld, aux, ld_aux);
+}
+// every program kind inside the compact container; qx32 / qy32 are read by the MSM program alone
+extern "C" long p2e_curve_program_ux_witness_compact_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg32, const uint8_t* r32,
+                                                           const uint8_t* s32, const uint8_t* pkx32, const uint8_t* pky32,
+                                                           const uint8_t* qx32, const uint8_t* qy32, const uint32_t* narrow, size_t ld_narrow,
+                                                           const uint32_t* aux32, size_t ld_aux, void* ux, int ux_u32, size_t ld_ux, size_t n,
+                                                           uint8_t* err) {
+    if (bad_common(c, n, ld_narrow) || !curve_inputs_ok(P, msg32, r32, s32, pkx32, pky32) || !narrow || !aux32 || !ux || !err || ld_aux < n ||
+        ld_ux < n) {
+        if (c && (ld_aux < n || ld_ux < n)) set_error("ld_aux / ld_ux < n");
+        return P2E_E_INVALID;
+    }
+    if (P->H.kind == CP_MSM && !curve_msm_ux_inputs_ok(pkx32, pky32, qx32, qy32, msg32, r32)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    UxCall U = curve_ux_call(P, msg32, r32, s32, pkx32, pky32, qx32, qy32, ux, ux_u32, ld_ux, n, err);
+    U.narrow = narrow;
+    U.ldn = ld_narrow;
+    U.aux = aux32;
+    U.ld_aux = ld_aux;
+    static const UxKernel kern[4] = {kc_ux_compact<0>, kc_ux_compact<1>, kc_ux_compact<2>, kc_ux_compact<3>};
+    return run_ux(c, U, kern);
 }
 // wire-matrix assembly (SURVEY.md 8(f) rank 3) for a curve program's four matrices: the map of p2e_wire_map_create with this
 // program's column counts as limits; p2e_assemble_wires / p2e_wire_map_destroy take the result as they are
@@ -952,7 +1023,7 @@ extern "C" int p2e_curve_program_wire_map_create(p2e_ctx* c, const p2e_curve_pro
     if (!P) return P2E_E_INVALID;
     const host::ScheduleBuilder& sb = P->H.sb;
     const u32 limit[4] = {(u32)sb.prog.num_cols, sb.aux_tab.num_aux_cols, sb.num_ux_cols, sb.num_gate_cols};
-    return make_wire_map(c, limit, entries, count, num_wires, degree, out);
+    return make_wire_map(c, limit, P->compact_map, P->num_narrow, P->num_wide, entries, count, num_wires, degree, out);
 }
 // synthetic valid signatures on a curve (host side; tests and benches)
 extern "C" int p2e_synth_signatures_curve(int curve, uint64_t seed, size_t first, size_t n, uint8_t* msg32, uint8_t* r32, uint8_t* s32,

@@ -20,6 +20,7 @@
 #include "curve_program.hpp"
 
 using namespace p2e;
+using host::COMPACT_WIDE;
 
 // The library is ONE source compiled as four translation units in parallel (plonky2_ecdsa_amd.build: -DP2E_PART=0..3),
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
@@ -179,6 +180,18 @@ template <int MODE>
 __global__ __launch_bounds__(BS) void k_ux(UxArgs A, size_t first) {
     size_t i = lane_sig<(MODE & 1) != 0>(first);
     if ((MODE & 1) || i < A.n) body_ux<typename AuxEmitOf<MODE>::type>(A, (int)blockIdx.y, i);
+}
+// the same two passes inside the compact container: witness columns from the u32 narrow matrix, aux columns from the
+// u32 aux matrix (kernels of their own, so that the u64-source ones stay the code they were)
+template <int MODE>
+__global__ __launch_bounds__(BS) void k_gate_compact(GateArgs A, size_t first) {
+    size_t i = lane_sig<(MODE & 1) != 0>(first);
+    if ((MODE & 1) || i < A.n) body_gate<typename AuxEmitOf<MODE>::type, true>(A, (int)blockIdx.y, i);
+}
+template <int MODE>
+__global__ __launch_bounds__(BS) void k_ux_compact(UxArgs A, size_t first) {
+    size_t i = lane_sig<(MODE & 1) != 0>(first);
+    if ((MODE & 1) || i < A.n) body_ux<typename AuxEmitOf<MODE>::type, true>(A, (int)blockIdx.y, i);
 }
 #endif   // P2E_HAS(0)
 // err words -> caller's err bytes, valid bytes, flagged count (every part launches it: internal linkage)
@@ -362,8 +375,17 @@ struct AssembleArgs {
     size_t count;
     u64* wires;
     size_t stride, n;
+    // compact sources (k_assemble_compact): src then holds witness entries in compact coordinates (WIRE_CSRC_WIDE | wide
+    // row, or the narrow row), aux entries index aux32
+    const u32* nar;
+    size_t ldn;
+    const u64* wide;
+    size_t ldw;
+    const u32* aux32;
 };
-__global__ __launch_bounds__(BS) void k_assemble(AssembleArgs A) {
+constexpr u32 WIRE_CSRC_WIDE = 0x20000000u;   // a witness entry of the compact source table that names a wide row
+template <bool CS>
+__device__ __forceinline__ void assemble_tile(const AssembleArgs& A) {
     __shared__ u64 tile[64][65];
     const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const size_t s0 = (size_t)blockIdx.x * 64, e0 = (size_t)blockIdx.y * 64;
@@ -373,10 +395,15 @@ __global__ __launch_bounds__(BS) void k_assemble(AssembleArgs A) {
         if (e < A.count && sg < A.n) {
             const u32 s = A.src[e], c = s & 0x3FFFFFFFu;
             u64 v;
-            if ((s >> 30) == 0)
-                v = A.cols[(size_t)c * A.ld + sg];
-            else if ((s >> 30) == 1)
-                v = A.aux[(size_t)c * A.ald + sg];
+            if ((s >> 30) == 0) {
+                if (!CS)
+                    v = A.cols[(size_t)c * A.ld + sg];
+                else if (c & WIRE_CSRC_WIDE)
+                    v = A.wide[(size_t)(c & ~WIRE_CSRC_WIDE) * A.ldw + sg];
+                else
+                    v = A.nar[(size_t)c * A.ldn + sg];
+            } else if ((s >> 30) == 1)
+                v = CS ? (u64)A.aux32[(size_t)c * A.ald + sg] : A.aux[(size_t)c * A.ald + sg];
             else if ((s >> 30) == 2)
                 v = A.ux_u32 ? (u64) static_cast<const u32*>(A.ux)[(size_t)c * A.uld + sg] : static_cast<const u64*>(A.ux)[(size_t)c * A.uld + sg];
             else
@@ -393,12 +420,13 @@ __global__ __launch_bounds__(BS) void k_assemble(AssembleArgs A) {
         if (sg < A.n && e < A.count) A.wires[sg * A.stride + d] = tile[lane][r];
     }
 }
+__global__ __launch_bounds__(BS) void k_assemble(AssembleArgs A) { assemble_tile<false>(A); }
+__global__ __launch_bounds__(BS) void k_assemble_compact(AssembleArgs A) { assemble_tile<true>(A); }
 
 // Compact container for transfers (p2e_columns_compact): every column whose values are < 2^32 by construction
 // (29-bit limbs, overflow words, flags: 57 % of the columns) is repacked as u32, the check_sum / carry columns of
 // the mul generators stay u64.  map[c] = index of column c in its matrix | P2E_COMPACT_WIDE.  One lane moves two
 // adjacent signatures (16-byte loads, 8- or 16-byte stores); blockIdx.y walks groups of 32 columns.
-constexpr u32 COMPACT_WIDE = 0x80000000u;
 constexpr int COMPACT_GROUP = 32;
 __global__ __launch_bounds__(BS) void k_compact(const u64* __restrict__ cols, size_t ld, size_t n, u32 ncols,
                                                 const u32* __restrict__ map, u32* __restrict__ narrow, size_t ldn,
@@ -502,6 +530,7 @@ struct DeviceProgram {
     std::vector<u32> ux_first, ux_count;
     u32 num_ux_cols = 0;
     UxItem* d_ux_items = nullptr;
+    UxItem* d_ux_items_compact = nullptr;   // the same table in compact coordinates (host::ux_items_compact)
     std::vector<GateItem> gate_items;
     u32 num_gate_cols = 0;
     GateItem* d_gate_items = nullptr;
@@ -619,18 +648,12 @@ struct p2e_ctx {
 };
 
 #if P2E_HAS(0)
-// wide = the 33 check_sum / carry columns of every mul generator (Goldilocks residues of signed sums, carries offset
-// by 2^33: gates/mul_nonnative.rs:305-322,518-527); everything else on the path is < 2^32 by construction
 static void build_compact_map(DeviceProgram& P) {
-    P.compact_map.assign((size_t)P.prog.num_cols, 0);
-    for (const auto& g : P.gens)
-        for (u32 k = 0; k < g.ncols; k++) {
-            const bool wide = g.kind == host::GEN_MUL && k >= 2 * NL;
-            P.compact_map[g.col + k] = wide ? (COMPACT_WIDE | P.num_wide++) : P.num_narrow++;
-        }
-    P.wide_before.assign((size_t)P.prog.num_cols + 1, 0);
-    for (size_t col = 0; col < P.compact_map.size(); col++)
-        P.wide_before[col + 1] = P.wide_before[col] + ((P.compact_map[col] & COMPACT_WIDE) ? 1u : 0u);
+    host::CompactLayout L = host::compact_layout(P.gens, (size_t)P.prog.num_cols);
+    P.compact_map = std::move(L.map);
+    P.wide_before = std::move(L.wide_before);
+    P.num_narrow = L.num_narrow;
+    P.num_wide = L.num_wide;
 }
 static const DeviceProgram& host_program(int program) {
     static DeviceProgram P[2];
@@ -718,6 +741,14 @@ extern "C" size_t p2e_scratch_bytes(int program, size_t n) {
 
 extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx** out) {
     if (!out) return P2E_E_INVALID;
+    // host-only check of the compact layout the compact-source ux pass walks, before anything is allocated
+    for (int p = 0; p < 2; p++) {
+        std::string why;
+        if (!host::ux_items_compact_ok(host_program(p).ux_items, host_program(p).compact_map, why)) {
+            set_error(why);
+            return P2E_E_INVALID;
+        }
+    }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
         set_error("no HIP device visible: libp2e_hip needs a gfx950 GPU (there is no CPU fallback)");
@@ -830,6 +861,9 @@ extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx*
         c->progs[p].num_ux_cols = HP.num_ux_cols;
         HIP_TRY(hipMalloc(&c->progs[p].d_ux_items, sizeof(UxItem) * HP.ux_items.size()));
         HIP_TRY(hipMemcpy(c->progs[p].d_ux_items, HP.ux_items.data(), sizeof(UxItem) * HP.ux_items.size(), hipMemcpyHostToDevice));
+        const std::vector<UxItem> cux = host::ux_items_compact(HP.ux_items, HP.compact_map);
+        HIP_TRY(hipMalloc(&c->progs[p].d_ux_items_compact, sizeof(UxItem) * cux.size()));
+        HIP_TRY(hipMemcpy(c->progs[p].d_ux_items_compact, cux.data(), sizeof(UxItem) * cux.size(), hipMemcpyHostToDevice));
         c->progs[p].gate_items = HP.gate_items;
         c->progs[p].num_gate_cols = HP.num_gate_cols;
         HIP_TRY(hipMalloc(&c->progs[p].d_gate_items, sizeof(GateItem) * HP.gate_items.size()));
@@ -971,6 +1005,7 @@ extern "C" void p2e_ctx_destroy(p2e_ctx* c) {
         (void)hipFree(p.d_aux_tab);
         (void)hipFree(p.d_compact_map);
         (void)hipFree(p.d_wide_before);
+        (void)hipFree(p.d_ux_items_compact);
     }
     (void)hipFree(c->scratch);
     (void)hipFree(c->d_counter);
@@ -1957,13 +1992,17 @@ extern "C" long p2e_aux_witness_compact_batch(p2e_ctx* c, int program, const uin
 struct p2e_wire_map {
     u32 limit[4] = {0, 0, 0, 0};   // column counts of the four source matrices (witness, aux, ux, gate) of the map's program
     u32* d_src = nullptr;
+    u32* d_csrc = nullptr;   // the same entries with the witness columns in compact coordinates (narrow row, or WIRE_CSRC_WIDE | wide row)
     u32* d_dst = nullptr;
     size_t count = 0;
     u32 num_wires = 0, degree = 0;
     bool uses[4] = {false, false, false, false};
+    u32 num_narrow = 0, num_wide = 0;   // rows of the program's compact container
+    bool uses_narrow = false, uses_wide = false;
 };
-static int make_wire_map(p2e_ctx* c, const u32 limit[4], const p2e_wire_map_entry* entries, size_t count, uint32_t num_wires,
-                         uint32_t degree, p2e_wire_map** out) {
+// cmap: the program's compact layout (p2e_compact_layout)
+static int make_wire_map(p2e_ctx* c, const u32 limit[4], const std::vector<u32>& cmap, u32 num_narrow, u32 num_wide,
+                         const p2e_wire_map_entry* entries, size_t count, uint32_t num_wires, uint32_t degree, p2e_wire_map** out) {
     if (!c || !out || (!entries && count) || !num_wires || !degree) return P2E_E_INVALID;
     const u64 cells = (u64)num_wires * degree;
     std::vector<p2e_wire_map_entry> v(entries, entries + count);
@@ -1980,21 +2019,32 @@ static int make_wire_map(p2e_ctx* c, const u32 limit[4], const p2e_wire_map_entr
         }
         m->uses[kind] = true;
     }
-    std::vector<u32> src(count), dst(count);
+    std::vector<u32> src(count), csrc(count), dst(count);
     for (size_t k = 0; k < count; k++) {
-        src[k] = v[k].src;
+        src[k] = csrc[k] = v[k].src;
         dst[k] = v[k].dst;
+        if ((v[k].src >> 30) == 0) {
+            const u32 slot = cmap[v[k].src];
+            const bool wide = (slot & COMPACT_WIDE) != 0;
+            csrc[k] = wide ? (WIRE_CSRC_WIDE | (slot & ~COMPACT_WIDE)) : slot;
+            (wide ? m->uses_wide : m->uses_narrow) = true;
+        }
     }
     DeviceGuard guard(c->device);
     for (int k = 0; k < 4; k++) m->limit[k] = limit[k];
     m->count = count;
     m->num_wires = num_wires;
     m->degree = degree;
-    if (hipMalloc(&m->d_src, sizeof(u32) * (count ? count : 1)) != hipSuccess || hipMalloc(&m->d_dst, sizeof(u32) * (count ? count : 1)) != hipSuccess ||
+    m->num_narrow = num_narrow;
+    m->num_wide = num_wide;
+    const size_t bytes = sizeof(u32) * (count ? count : 1);
+    if (hipMalloc(&m->d_src, bytes) != hipSuccess || hipMalloc(&m->d_csrc, bytes) != hipSuccess || hipMalloc(&m->d_dst, bytes) != hipSuccess ||
         hipMemcpy(m->d_src, src.data(), sizeof(u32) * count, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(m->d_csrc, csrc.data(), sizeof(u32) * count, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(m->d_dst, dst.data(), sizeof(u32) * count, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(m->d_src);
+        (void)hipFree(m->d_csrc);
         (void)hipFree(m->d_dst);
         delete m;
         set_error("wire map: device allocation failed");
@@ -2008,7 +2058,7 @@ extern "C" int p2e_wire_map_create(p2e_ctx* c, int program, const p2e_wire_map_e
     if (program < 0 || program > 1) return P2E_E_INVALID;
     const DeviceProgram& HP = host_program(program);
     const u32 limit[4] = {(u32)HP.prog.num_cols, HP.aux_tab.num_aux_cols, HP.num_ux_cols, HP.num_gate_cols};
-    return make_wire_map(c, limit, entries, count, num_wires, degree, out);
+    return make_wire_map(c, limit, HP.compact_map, HP.num_narrow, HP.num_wide, entries, count, num_wires, degree, out);
 }
 extern "C" void p2e_wire_map_destroy(p2e_ctx* c, p2e_wire_map* m) {
     if (!m) return;
@@ -2016,9 +2066,36 @@ extern "C" void p2e_wire_map_destroy(p2e_ctx* c, p2e_wire_map* m) {
         DeviceGuard guard(c->device);
         (void)hipStreamSynchronize(c->stream);
         (void)hipFree(m->d_src);
+        (void)hipFree(m->d_csrc);
         (void)hipFree(m->d_dst);
     }
     delete m;
+}
+// the launch of both assemblies: A holds the (staged) sources; the wire matrix is an in-out buffer
+static long run_assemble(p2e_ctx* c, Staged& S, const p2e_wire_map* m, AssembleArgs A, bool compact, uint64_t* wires, size_t wire_stride,
+                         size_t n) {
+    uint64_t* const host_wires = wires;
+    if (S.host) {   // in-out buffer: positions no entry names keep the caller's values
+        void* d_stage = S.stage(n * wire_stride * 8);
+        if (d_stage && hipMemcpyAsync(d_stage, host_wires, n * wire_stride * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) S.rc = P2E_E_HIP;
+        if (d_stage) S.outs.push_back({host_wires, d_stage, n * wire_stride * 8});
+        wires = (uint64_t*)d_stage;
+    }
+    if (S.rc) return S.done(S.rc);
+    ZERO_COUNTER(c);
+    A.src = compact ? m->d_csrc : m->d_src;
+    A.dst = m->d_dst;
+    A.count = m->count;
+    A.wires = wires;
+    A.stride = wire_stride;
+    A.n = n;
+    dim3 grid((unsigned)((n + 63) / 64), (unsigned)((m->count + 63) / 64));
+    if (compact)
+        hipLaunchKernelGGL(k_assemble_compact, grid, dim3(BS), 0, c->stream, A);
+    else
+        hipLaunchKernelGGL(k_assemble, grid, dim3(BS), 0, c->stream, A);
+    c->have_phases = false;
+    return S.done(finish_call(c));
 }
 extern "C" long p2e_assemble_wires(p2e_ctx* c, const p2e_wire_map* m, const uint64_t* cols, size_t ld, const uint64_t* aux,
                                    size_t ld_aux, const void* ux, int ux_u32, size_t ld_ux, const uint64_t* gate, size_t ld_gate,
@@ -2034,21 +2111,50 @@ extern "C" long p2e_assemble_wires(p2e_ctx* c, const p2e_wire_map* m, const uint
     if (aux) aux = S.in(aux, (size_t)m->limit[1] * ld_aux * 8);
     if (ux) ux = S.in((const char*)ux, (size_t)m->limit[2] * ld_ux * (ux_u32 ? 4 : 8));
     if (gate) gate = S.in(gate, (size_t)m->limit[3] * ld_gate * 8);
-    uint64_t* const host_wires = wires;
-    void* d_stage = nullptr;
-    if (S.host) {   // in-out buffer: positions no entry names keep the caller's values
-        d_stage = S.stage(n * wire_stride * 8);
-        if (d_stage && hipMemcpyAsync(d_stage, host_wires, n * wire_stride * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) S.rc = P2E_E_HIP;
-        if (d_stage) S.outs.push_back({host_wires, d_stage, n * wire_stride * 8});
-        wires = (uint64_t*)d_stage;
+    AssembleArgs A{};
+    A.cols = cols;
+    A.ld = ld;
+    A.aux = aux;
+    A.ald = ld_aux;
+    A.ux = ux;
+    A.uld = ld_ux;
+    A.ux_u32 = ux_u32;
+    A.gate = gate;
+    A.gld = ld_gate;
+    return run_assemble(c, S, m, A, false, wires, wire_stride, n);
+}
+// the same scatter from the compact container and the u32 aux matrix (the map keeps its witness sources in both
+// coordinates: a map made for one container works for the other)
+extern "C" long p2e_assemble_wires_compact(p2e_ctx* c, const p2e_wire_map* m, const uint32_t* narrow, size_t ld_narrow,
+                                           const uint64_t* wide, size_t ld_wide, const uint32_t* aux32, size_t ld_aux, const void* ux,
+                                           int ux_u32, size_t ld_ux, const uint64_t* gate, size_t ld_gate, uint64_t* wires,
+                                           size_t wire_stride, size_t n) {
+    if (!c || !m || !wires || wire_stride < (size_t)m->num_wires * m->degree || (m->uses_narrow && (!narrow || ld_narrow < n)) ||
+        (m->uses_wide && (!wide || ld_wide < n)) || (m->uses[1] && (!aux32 || ld_aux < n)) || (m->uses[2] && (!ux || ld_ux < n)) ||
+        (m->uses[3] && (!gate || ld_gate < n))) {
+        set_error("p2e_assemble_wires_compact: null matrix the map reads, ld < n, or wire_stride < num_wires * degree");
+        return P2E_E_INVALID;
     }
-    if (S.rc) return S.done(S.rc);
-    ZERO_COUNTER(c);
-    AssembleArgs A{cols, ld, aux, ld_aux, ux, ld_ux, ux_u32, gate, ld_gate, m->d_src, m->d_dst, m->count, wires, wire_stride, n};
-    dim3 grid((unsigned)((n + 63) / 64), (unsigned)((m->count + 63) / 64));
-    hipLaunchKernelGGL(k_assemble, grid, dim3(BS), 0, c->stream, A);
-    c->have_phases = false;
-    return S.done(finish_call(c));
+    if (n == 0 || m->count == 0) return 0;
+    Staged S(c);
+    if (narrow) narrow = S.in(narrow, (size_t)m->num_narrow * ld_narrow * 4);
+    if (wide) wide = S.in(wide, (size_t)m->num_wide * ld_wide * 8);
+    if (aux32) aux32 = S.in(aux32, (size_t)m->limit[1] * ld_aux * 4);
+    if (ux) ux = S.in((const char*)ux, (size_t)m->limit[2] * ld_ux * (ux_u32 ? 4 : 8));
+    if (gate) gate = S.in(gate, (size_t)m->limit[3] * ld_gate * 8);
+    AssembleArgs A{};
+    A.nar = narrow;
+    A.ldn = ld_narrow;
+    A.wide = wide;
+    A.ldw = ld_wide;
+    A.aux32 = aux32;
+    A.ald = ld_aux;
+    A.ux = ux;
+    A.uld = ld_ux;
+    A.ux_u32 = ux_u32;
+    A.gate = gate;
+    A.gld = ld_gate;
+    return run_assemble(c, S, m, A, true, wires, wire_stride, n);
 }
 
 static u64 gl_pow_host(u64 a, u64 e) {
@@ -2060,6 +2166,39 @@ static u64 gl_pow_host(u64 a, u64 e) {
     }
     return r;
 }
+// the gate-internal pass of any program: aux is the u64 aux matrix, or (aux_u32) the u32 one of the compact aux pass
+static long run_gate(p2e_ctx* c, const void* aux, bool aux_u32, size_t ld_aux, uint64_t* gate, size_t ld_gate, size_t n,
+                     u32 num_aux_cols, u32 num_gate_cols, const GateItem* d_items, unsigned items) {
+    Staged S(c);
+    aux = S.in((const char*)aux, (size_t)num_aux_cols * ld_aux * (aux_u32 ? 4 : 8));
+    gate = S.out(gate, (size_t)num_gate_cols * ld_gate * 8);
+    if (S.rc) return S.done(S.rc);
+    ZERO_COUNTER(c);
+    GateArgs A{};
+    if (aux_u32)
+        A.aux32 = (const u32*)aux;
+    else
+        A.aux = (const u64*)aux;
+    A.ald = ld_aux;
+    A.gate = gate;
+    A.gld = ld_gate;
+    A.n = n;
+    A.items = d_items;
+    A.inv16[0] = 0;
+    for (u64 d = 1; d < 16; d++) A.inv16[d] = gl_pow_host(d, P_GL - 2);
+    const bool wide_ok = (ld_gate % 2 == 0) && ((reinterpret_cast<uintptr_t>(gate) & 15) == 0) && !getenv("P2E_NARROW_STORES");
+    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
+    const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
+    if (aux_u32) {
+        if (n_wide) hipLaunchKernelGGL(k_gate_compact<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
+        if (n > n_wide) hipLaunchKernelGGL(k_gate_compact<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
+    } else {
+        if (n_wide) hipLaunchKernelGGL(k_gate<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
+        if (n > n_wide) hipLaunchKernelGGL(k_gate<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
+    }
+    c->have_phases = false;
+    return S.done(finish_call(c));
+}
 extern "C" long p2e_gate_internal_batch(p2e_ctx* c, int program, const uint64_t* aux, size_t ld_aux, uint64_t* gate, size_t ld_gate,
                                         size_t n) {
     if (bad_common(c, n, ld_aux) || program < 0 || program > 1 || !aux || !gate || ld_gate < n) {
@@ -2068,34 +2207,124 @@ extern "C" long p2e_gate_internal_batch(p2e_ctx* c, int program, const uint64_t*
     }
     if (n == 0) return 0;
     const DeviceProgram& DP = c->progs[program];
-    Staged S(c);
-    aux = S.in(aux, (size_t)DP.aux_tab.num_aux_cols * ld_aux * 8);
-    gate = S.out(gate, (size_t)DP.num_gate_cols * ld_gate * 8);
-    if (S.rc) return S.done(S.rc);
-    ZERO_COUNTER(c);
-    GateArgs A{};
-    A.aux = aux;
-    A.ald = ld_aux;
-    A.gate = gate;
-    A.gld = ld_gate;
-    A.n = n;
-    A.items = DP.d_gate_items;
-    A.inv16[0] = 0;
-    for (u64 d = 1; d < 16; d++) A.inv16[d] = gl_pow_host(d, P_GL - 2);
-    const unsigned items = (unsigned)DP.gate_items.size();
-    const bool wide_ok = (ld_gate % 2 == 0) && ((reinterpret_cast<uintptr_t>(gate) & 15) == 0) && !getenv("P2E_NARROW_STORES");
-    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
-    const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
-    if (n_wide) hipLaunchKernelGGL(k_gate<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
-    if (n > n_wide) hipLaunchKernelGGL(k_gate<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
-    c->have_phases = false;
-    return S.done(finish_call(c));
+    return run_gate(c, aux, false, ld_aux, gate, ld_gate, n, DP.aux_tab.num_aux_cols, DP.num_gate_cols, DP.d_gate_items,
+                    (unsigned)DP.gate_items.size());
+}
+extern "C" long p2e_gate_internal_compact_batch(p2e_ctx* c, int program, const uint32_t* aux32, size_t ld_aux, uint64_t* gate,
+                                                size_t ld_gate, size_t n) {
+    if (bad_common(c, n, ld_aux) || program < 0 || program > 1 || !aux32 || !gate || ld_gate < n) {
+        if (c && ld_gate < n) set_error("ld_gate < n");
+        return P2E_E_INVALID;
+    }
+    if (n == 0) return 0;
+    const DeviceProgram& DP = c->progs[program];
+    return run_gate(c, aux32, true, ld_aux, gate, ld_gate, n, DP.aux_tab.num_aux_cols, DP.num_gate_cols, DP.d_gate_items,
+                    (unsigned)DP.gate_items.size());
 }
 extern "C" long p2e_gate_internal_num_cols(int program) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
     return (long)host_program(program).num_gate_cols;
 }
 
+// The constraint-block pass of any program.  Source: the u64 matrices cols / aux, or (cols == nullptr) the compact
+// container's narrow matrix and the u32 aux matrix.  kern[MODE]: the program family's kernels for that source
+// (AuxEmitOf<MODE>: bit 0 = paired stores, bit 1 = u32 output).
+typedef void (*UxKernel)(UxArgs, size_t);
+struct UxCall {
+    const uint8_t* in[7] = {};   // packed inputs by INPUT_* slot; null where the program has none
+    const uint64_t* cols = nullptr;
+    size_t ld = 0;
+    const uint32_t* narrow = nullptr;
+    size_t ldn = 0;
+    const void* aux = nullptr;
+    size_t ld_aux = 0;
+    void* ux = nullptr;
+    int ux_u32 = 0;
+    size_t ld_ux = 0, n = 0;
+    uint8_t* err = nullptr;
+    // the program's
+    u32 num_cols = 0, num_narrow = 0, num_aux_cols = 0, num_ux_cols = 0;
+    const U256* d_consts = nullptr;
+    const UxItem* d_items = nullptr;           // u64 source
+    const UxItem* d_items_compact = nullptr;   // compact source: the table in compact coordinates
+    unsigned items = 0;
+};
+static long run_ux(p2e_ctx* c, UxCall U, const UxKernel kern[4]) {
+    const bool compact = U.cols == nullptr;
+    const size_t n = U.n;
+    Staged S(c);
+    for (int k = 0; k < 7; k++)
+        if (U.in[k]) U.in[k] = S.in(U.in[k], 32 * n);
+    if (compact) {
+        U.narrow = S.in(U.narrow, (size_t)U.num_narrow * U.ldn * 4);
+        U.aux = S.in((const char*)U.aux, (size_t)U.num_aux_cols * U.ld_aux * 4);
+    } else {
+        U.cols = S.in(U.cols, (size_t)U.num_cols * U.ld * 8);
+        U.aux = S.in((const char*)U.aux, (size_t)U.num_aux_cols * U.ld_aux * 8);
+    }
+    void* ux = S.out((char*)U.ux, (size_t)U.num_ux_cols * U.ld_ux * (U.ux_u32 ? 4 : 8));
+    uint8_t* err = S.out(U.err, n);
+    if (S.rc) return S.done(S.rc);
+    if (int rc = ensure_scratch(c, n * sizeof(u32))) return S.done(rc);
+    ZERO_COUNTER(c);
+    u32* err32 = (u32*)c->scratch;
+    HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
+    UxArgs A{};
+    A.cols = U.cols;
+    A.ld = U.ld;
+    A.ald = U.ld_aux;
+    if (compact) {
+        A.nar = U.narrow;
+        A.ldn = U.ldn;
+        A.aux32 = (const u32*)U.aux;
+    } else {
+        A.aux = (const u64*)U.aux;
+    }
+    A.ux = ux;
+    A.uld = U.ld_ux;
+    A.n = n;
+    for (int k = 0; k < 7; k++) A.in[k] = U.in[k];
+    if (!A.in[INPUT_R]) A.in[INPUT_R] = A.in[INPUT_MSG];
+    if (!A.in[INPUT_S]) A.in[INPUT_S] = A.in[INPUT_MSG];
+    A.consts = U.d_consts;
+    A.items = compact ? U.d_items_compact : U.d_items;
+    A.err = err32;
+    const unsigned gx = (unsigned)((n + BS - 1) / BS);
+    const bool wide_ok = (U.ld_ux % 2 == 0) && ((reinterpret_cast<uintptr_t>(ux) & (U.ux_u32 ? 7 : 15)) == 0) && !getenv("P2E_NARROW_STORES");
+    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
+    const dim3 gw((unsigned)(n_wide / BS), U.items), gt((unsigned)((n - n_wide + BS - 1) / BS), U.items);
+    const int u32_bit = U.ux_u32 ? 2 : 0;
+    if (n_wide) hipLaunchKernelGGL(kern[u32_bit | 1], gw, dim3(BS), 0, c->stream, A, (size_t)0);
+    if (n > n_wide) hipLaunchKernelGGL(kern[u32_bit], gt, dim3(BS), 0, c->stream, A, n_wide);
+    hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, err32, (const uint8_t*)nullptr, err, (uint8_t*)nullptr, n,
+                       c->d_counter);
+    c->have_phases = false;
+    return S.done(finish_call(c));
+}
+static UxCall builtin_ux_call(p2e_ctx* c, int program, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32, const uint8_t* pkx32,
+                              const uint8_t* pky32, void* ux, int ux_u32, size_t ld_ux, size_t n, uint8_t* err) {
+    const DeviceProgram& DP = c->progs[program];
+    UxCall U;
+    U.in[INPUT_PY] = pky32;
+    U.in[INPUT_PX] = pkx32;
+    U.in[INPUT_MSG] = msg32;
+    U.in[INPUT_R] = r32;
+    U.in[INPUT_S] = s32;
+    U.ux = ux;
+    U.ux_u32 = ux_u32;
+    U.ld_ux = ld_ux;
+    U.n = n;
+    U.err = err;
+    U.num_cols = (u32)DP.prog.num_cols;
+    U.num_narrow = DP.num_narrow;
+    U.num_aux_cols = DP.aux_tab.num_aux_cols;
+    U.num_ux_cols = DP.num_ux_cols;
+    U.d_consts = c->d_constv;
+    U.d_items = DP.d_ux_items;
+    U.d_items_compact = DP.d_ux_items_compact;
+    U.items = (unsigned)DP.ux_items.size();
+    return U;
+}
 extern "C" long p2e_ux_witness_batch(p2e_ctx* c, int program, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
                                      const uint8_t* pkx32, const uint8_t* pky32, const uint64_t* cols, size_t ld,
                                      const uint64_t* aux, size_t ld_aux, void* ux, int ux_u32, size_t ld_ux, size_t n, uint8_t* err) {
@@ -2105,53 +2334,31 @@ extern "C" long p2e_ux_witness_batch(p2e_ctx* c, int program, const uint8_t* msg
         return P2E_E_INVALID;
     }
     if (n == 0) return 0;
-    const DeviceProgram& DP = c->progs[program];
-    Staged S(c);
-    msg32 = S.in(msg32, 32 * n);
-    if (r32) r32 = S.in(r32, 32 * n);
-    if (s32) s32 = S.in(s32, 32 * n);
-    pkx32 = S.in(pkx32, 32 * n);
-    pky32 = S.in(pky32, 32 * n);
-    cols = S.in(cols, (size_t)DP.prog.num_cols * ld * 8);
-    aux = S.in(aux, (size_t)DP.aux_tab.num_aux_cols * ld_aux * 8);
-    ux = S.out((char*)ux, (size_t)DP.num_ux_cols * ld_ux * (ux_u32 ? 4 : 8));
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    if (int rc = ensure_scratch(c, n * sizeof(u32))) return S.done(rc);
-    ZERO_COUNTER(c);
-    u32* err32 = (u32*)c->scratch;
-    HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
-    UxArgs A{};
-    A.cols = cols;
-    A.ld = ld;
-    A.aux = aux;
-    A.ald = ld_aux;
-    A.ux = ux;
-    A.uld = ld_ux;
-    A.n = n;
-    A.in[INPUT_PY] = pky32;
-    A.in[INPUT_PX] = pkx32;
-    A.in[INPUT_MSG] = msg32;
-    A.in[INPUT_R] = r32 ? r32 : msg32;
-    A.in[INPUT_S] = s32 ? s32 : msg32;
-    A.consts = c->d_constv;
-    A.items = DP.d_ux_items;
-    A.err = err32;
-    const unsigned gx = (unsigned)((n + BS - 1) / BS), items = (unsigned)DP.ux_items.size();
-    const bool wide_ok = (ld_ux % 2 == 0) && ((reinterpret_cast<uintptr_t>(ux) & (ux_u32 ? 7 : 15)) == 0) && !getenv("P2E_NARROW_STORES");
-    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
-    const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
-    if (ux_u32) {
-        if (n_wide) hipLaunchKernelGGL(k_ux<3>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
-        if (n > n_wide) hipLaunchKernelGGL(k_ux<2>, gt, dim3(BS), 0, c->stream, A, n_wide);
-    } else {
-        if (n_wide) hipLaunchKernelGGL(k_ux<1>, gw, dim3(BS), 0, c->stream, A, (size_t)0);
-        if (n > n_wide) hipLaunchKernelGGL(k_ux<0>, gt, dim3(BS), 0, c->stream, A, n_wide);
+    UxCall U = builtin_ux_call(c, program, msg32, r32, s32, pkx32, pky32, ux, ux_u32, ld_ux, n, err);
+    U.cols = cols;
+    U.ld = ld;
+    U.aux = aux;
+    U.ld_aux = ld_aux;
+    static const UxKernel kern[4] = {k_ux<0>, k_ux<1>, k_ux<2>, k_ux<3>};
+    return run_ux(c, U, kern);
+}
+extern "C" long p2e_ux_witness_compact_batch(p2e_ctx* c, int program, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
+                                             const uint8_t* pkx32, const uint8_t* pky32, const uint32_t* narrow, size_t ld_narrow,
+                                             const uint32_t* aux32, size_t ld_aux, void* ux, int ux_u32, size_t ld_ux, size_t n,
+                                             uint8_t* err) {
+    if (bad_common(c, n, ld_narrow) || program < 0 || program > 1 || !msg32 || !pkx32 || !pky32 || (program == 0 && (!r32 || !s32)) ||
+        !narrow || !aux32 || !ux || !err || ld_aux < n || ld_ux < n) {
+        if (c && (ld_aux < n || ld_ux < n)) set_error("ld_aux / ld_ux < n");
+        return P2E_E_INVALID;
     }
-    hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, err32, (const uint8_t*)nullptr, err, (uint8_t*)nullptr, n,
-                       c->d_counter);
-    c->have_phases = false;
-    return S.done(finish_call(c));
+    if (n == 0) return 0;
+    UxCall U = builtin_ux_call(c, program, msg32, r32, s32, pkx32, pky32, ux, ux_u32, ld_ux, n, err);
+    U.narrow = narrow;
+    U.ldn = ld_narrow;
+    U.aux = aux32;
+    U.ld_aux = ld_aux;
+    static const UxKernel kern[4] = {k_ux_compact<0>, k_ux_compact<1>, k_ux_compact<2>, k_ux_compact<3>};
+    return run_ux(c, U, kern);
 }
 
 // ====================================================================================================

@@ -769,5 +769,62 @@ private:
     }
 };
 
+// ---- compact container (include/p2e.h p2e_compact_layout) --------------------------------------------------------------
+// wide = the 33 check_sum / carry columns of every mul generator (Goldilocks residues of signed sums, carries offset
+// by 2^33: gates/mul_nonnative.rs:305-322,518-527); everything else on the path is < 2^32 by construction.
+// map[c] = row of witness column c in the u32 narrow matrix, or COMPACT_WIDE | row in the u64 wide one, both advancing in
+// generator registration order; wide_before[c] = wide columns before column c (the emitters' second cursor).
+constexpr u32 COMPACT_WIDE = 0x80000000u;
+struct CompactLayout {
+    std::vector<u32> map, wide_before;
+    u32 num_narrow = 0, num_wide = 0;
+};
+inline CompactLayout compact_layout(const std::vector<GenOp>& gens, size_t num_cols) {
+    CompactLayout L;
+    L.map.assign(num_cols, 0);
+    for (const auto& g : gens)
+        for (u32 k = 0; k < g.ncols; k++) {
+            const bool wide = g.kind == GEN_MUL && k >= 2 * NL;
+            L.map[g.col + k] = wide ? (COMPACT_WIDE | L.num_wide++) : L.num_narrow++;
+        }
+    L.wide_before.assign(num_cols + 1, 0);
+    for (size_t col = 0; col < num_cols; col++) L.wide_before[col + 1] = L.wide_before[col] + ((L.map[col] & COMPACT_WIDE) ? 1u : 0u);
+    return L;
+}
+// The compact-source constraint-block pass (ux.hpp ux_narrow) is given the narrow row of the FIRST column of a limb group
+// (ux_items_compact below) and walks the rows behind it: every group it reads -- a wired operand's limbs, a generator's result limbs with the overflow
+// word (add / sub / add_many) or the div limbs (inv) behind them -- must be narrow columns on consecutive rows.  Checked
+// when a context or a curve program is created, which fails loudly otherwise.
+inline bool ux_items_compact_ok(const std::vector<UxItem>& items, const std::vector<u32>& cmap, std::string& why) {
+    auto run_ok = [&](u32 col, u32 count) {
+        for (u32 k = 0; k < count; k++)
+            if ((size_t)col + k >= cmap.size() || (cmap[col + k] & COMPACT_WIDE) || cmap[col + k] != cmap[col] + k) return false;
+        return true;
+    };
+    for (const UxItem& it : items) {
+        const u32 behind = it.kind == UX_INV ? (u32)NL : it.kind == UX_MUL ? 0u : 1u;
+        bool ok = run_ok(it.res_col, NL + behind);
+        for (int k = 0; k < it.nops && k < 4 && ok; k++)
+            if ((it.src[k] & AUX_SRC_KIND_MASK) == 0) ok = run_ok(it.src[k], it.nl[k]);
+        if (!ok) {
+            why = "compact layout: the generator at witness column " + std::to_string(it.res_col) +
+                  " reads limbs that are not consecutive narrow columns";
+            return false;
+        }
+    }
+    return true;
+}
+// the item table of the compact-source pass: res_col and every witness source as narrow rows (no dependent load in the
+// kernel); call after ux_items_compact_ok
+inline std::vector<UxItem> ux_items_compact(const std::vector<UxItem>& items, const std::vector<u32>& cmap) {
+    std::vector<UxItem> out(items);
+    for (UxItem& it : out) {
+        it.res_col = cmap[it.res_col];
+        for (int k = 0; k < it.nops && k < 4; k++)
+            if ((it.src[k] & AUX_SRC_KIND_MASK) == 0) it.src[k] = cmap[it.src[k]];
+    }
+    return out;
+}
+
 }  // namespace host
 }  // namespace p2e

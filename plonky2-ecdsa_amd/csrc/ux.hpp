@@ -36,13 +36,25 @@ struct UxArgs {
     size_t ald;
     void* ux;   // u64 or u32 column matrix, by the emitter type
     size_t uld, n;
-    const uint8_t* in[5];   // packed inputs by INPUT_* slot: pk.y, pk.x, msg (glv_mul: k), r, s
+    const uint8_t* in[7];   // packed inputs by INPUT_* slot: pk.y, pk.x, msg (glv_mul: k), r, s; the MSM program: q.x, q.y
     const U256* consts;     // [NUM_CONSTV]: circuit constants by id (AUX_SRC_CONST | id)
     const UxItem* items;
     u32* err;
+    // compact source (the CS variants of the bodies): the container's narrow matrix with its stride and the u32 aux matrix
+    // (stride ald); `items` is then the table in compact coordinates (host::ux_items_compact): res_col and every witness
+    // source are narrow ROWS.  Every column this pass reads is a limb, an overflow word or a flag.
+    const u32* nar;
+    size_t ldn;
+    const u32* aux32;
 };
 
-// the limbs of a target (zero beyond the limbs it has); flags limbs that are no U29 values
+// narrow row r of the compact source.  The limbs of a target, and a generator's result limbs with its overflow word or
+// div limbs behind them, are consecutive witness columns with no wide column between them, so their narrow rows are
+// consecutive too: the host translates the first column of each group when it builds the compact item table, and checks
+// that property there (host::ux_items_compact_ok)
+P2E_HD const u32* ux_narrow(const UxArgs& A, u32 r) { return A.nar + (size_t)r * A.ldn; }
+// the limbs of a target (zero beyond the limbs it has); flags limbs that are no U29 values.  CS: compact source
+template <bool CS = false>
 P2E_HD void ux_load(const UxArgs& A, u32 src, int nl, size_t i, u32* l, bool& bad) {
     const u32 kind = src & AUX_SRC_KIND_MASK;
     if (kind == AUX_SRC_CONST) {
@@ -53,6 +65,15 @@ P2E_HD void ux_load(const UxArgs& A, u32 src, int nl, size_t i, u32* l, bool& ba
         P2E_UNROLL
         for (int k = 0; k < 8; k++) v.w[k] = p[k];
         split29(v, l);
+    } else if (CS) {
+        const u32* base = kind == AUX_SRC_AUX ? A.aux32 + (size_t)(src & ~AUX_SRC_KIND_MASK) * A.ald : ux_narrow(A, src);
+        const size_t ld = kind == AUX_SRC_AUX ? A.ald : A.ldn;
+        P2E_UNROLL
+        for (int k = 0; k < NL; k++) {
+            const u32 v = k < nl ? base[(size_t)k * ld + i] : 0;
+            bad = bad || (v >> BITS) != 0;
+            l[k] = v;
+        }
     } else {
         const u64* base = kind == AUX_SRC_AUX ? A.aux + (size_t)(src & ~AUX_SRC_KIND_MASK) * A.ald : A.cols + (size_t)src * A.ld;
         const size_t ld = kind == AUX_SRC_AUX ? A.ald : A.ld;
@@ -154,18 +175,18 @@ P2E_HD void ux_finish(E& e, const UxItem& it, const u32* res) {
         e.flush();
     }
 }
-template <class MOD, class E>
+template <class MOD, class E, bool CS = false>
 P2E_HD void ux_block(E e, const UxArgs& A, const UxItem& it, size_t i, bool& bad) {
     u32 m[NL];
     P2E_UNROLL
     for (int k = 0; k < NL; k++) m[k] = MOD::m29(k);
     u32 res[NL];
-    ux_load(A, it.res_col, NL, i, res, bad);
+    ux_load<CS>(A, it.res_col, NL, i, res, bad);
     if (it.kind == UX_ADD || it.kind == UX_SUB) {
         u32 a[NL], b[NL], t[NL + 2], mto[NL + 1];
-        ux_load(A, it.src[0], it.nl[0], i, a, bad);
-        ux_load(A, it.src[1], it.nl[1], i, b, bad);
-        const u64 ov = A.cols[(size_t)(it.res_col + NL) * A.ld + i];
+        ux_load<CS>(A, it.src[0], it.nl[0], i, a, bad);
+        ux_load<CS>(A, it.src[1], it.nl[1], i, b, bad);
+        const u64 ov = CS ? (u64)ux_narrow(A, it.res_col + NL)[i] : A.cols[(size_t)(it.res_col + NL) * A.ld + i];
         if (it.kind == UX_ADD) {
             ux_add_biguint<NL, NL>(e, a, b, t);                      // sum_expected (limbs beyond an operand's count are zero_ux)
             P2E_UNROLL
@@ -189,22 +210,22 @@ P2E_HD void ux_block(E e, const UxArgs& A, const UxItem& it, size_t i, bool& bad
     } else if (it.kind == UX_ADD_MANY) {
         // the fold over the summands from zero_biguint() (no limbs): accumulator grows by one limb per add
         u32 x0[NL], x1[NL], x2[NL], x3[NL], a1[NL + 1], a2[NL + 2], a3[NL + 3], a4[NL + 4], z0[1] = {0};
-        ux_load(A, it.src[0], it.nl[0], i, x0, bad);
-        ux_load(A, it.src[1], it.nl[1], i, x1, bad);
-        ux_load(A, it.src[2], it.nl[2], i, x2, bad);
-        ux_load(A, it.src[3], it.nl[3], i, x3, bad);
+        ux_load<CS>(A, it.src[0], it.nl[0], i, x0, bad);
+        ux_load<CS>(A, it.src[1], it.nl[1], i, x1, bad);
+        ux_load<CS>(A, it.src[2], it.nl[2], i, x2, bad);
+        ux_load<CS>(A, it.src[3], it.nl[3], i, x3, bad);
         ux_add_biguint<0, NL>(e, z0, x0, a1);
         ux_add_biguint<NL + 1, NL>(e, a1, x1, a2);
         ux_add_biguint<NL + 2, NL>(e, a2, x2, a3);
         ux_add_biguint<NL + 3, NL>(e, a3, x3, a4);
-        u32 ovl[1] = {(u32)A.cols[(size_t)(it.res_col + NL) * A.ld + i]}, mto[NL + 2], t[NL + 3];
+        u32 ovl[1] = {CS ? ux_narrow(A, it.res_col + NL)[i] : (u32)A.cols[(size_t)(it.res_col + NL) * A.ld + i]}, mto[NL + 2], t[NL + 3];
         ux_mul_biguint<NL, 1>(e, m, ovl, mto);                       // 11 limbs
         ux_add_biguint<NL, NL + 2>(e, res, mto, t);
         ux_finish<MOD>(e, it, res);
     } else if (it.kind == UX_INV) {
         u32 x[NL], div[NL], prod[2 * NL + 1], mtd[2 * NL + 1], one[1] = {1}, t[2 * NL + 2];
-        ux_load(A, it.src[0], it.nl[0], i, x, bad);
-        ux_load(A, it.res_col + NL, NL, i, div, bad);
+        ux_load<CS>(A, it.src[0], it.nl[0], i, x, bad);
+        ux_load<CS>(A, it.res_col + NL, NL, i, div, bad);
         ux_mul_biguint<NL, NL>(e, x, res, prod);                     // x * inv
         ux_mul_biguint<NL, NL>(e, m, div, mtd);                      // modulus * div
         ux_add_biguint<2 * NL + 1, 1>(e, mtd, one, t);               // + 1
@@ -214,33 +235,33 @@ P2E_HD void ux_block(E e, const UxArgs& A, const UxItem& it, size_t i, bool& bad
     }
 }
 
-template <class E>
+template <class E, bool CS = false>
 P2E_HD void body_ux(const UxArgs& A, int item, size_t i) {
     const UxItem it = A.items[item];
     E e = E::at(static_cast<typename E::elem*>(A.ux), A.uld, i, it.ux_col);
     bool bad = false;
     if (it.field == 0)
-        ux_block<ModP>(e, A, it, i, bad);
+        ux_block<ModP, E, CS>(e, A, it, i, bad);
     else
-        ux_block<ModN>(e, A, it, i, bad);
+        ux_block<ModN, E, CS>(e, A, it, i, bad);
     if (bad) err_or(&A.err[i], ERR_LIMB_RANGE);
 }
 
 // curve programs (curves.hpp): field 0 / 1 = secp256k1 base / scalar, 2 / 3 = P-256 base / scalar; A.consts is the
 // program's constant array indexed by source id (points at 2c / 2c + 1, scalar constants from AUX_GCONST_BASE)
-template <class E>
+template <class E, bool CS = false>
 P2E_HD void body_ux_cv(const UxArgs& A, int item, size_t i) {
     const UxItem it = A.items[item];
     E e = E::at(static_cast<typename E::elem*>(A.ux), A.uld, i, it.ux_col);
     bool bad = false;
     if (it.field == 0)
-        ux_block<ModP>(e, A, it, i, bad);
+        ux_block<ModP, E, CS>(e, A, it, i, bad);
     else if (it.field == 1)
-        ux_block<ModN>(e, A, it, i, bad);
+        ux_block<ModN, E, CS>(e, A, it, i, bad);
     else if (it.field == 2)
-        ux_block<ModP256>(e, A, it, i, bad);
+        ux_block<ModP256, E, CS>(e, A, it, i, bad);
     else
-        ux_block<ModN256>(e, A, it, i, bad);
+        ux_block<ModN256, E, CS>(e, A, it, i, bad);
     if (bad) err_or(&A.err[i], ERR_LIMB_RANGE);
 }
 

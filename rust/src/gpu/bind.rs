@@ -75,7 +75,8 @@ pub fn fill_partial_witnesses<F: RichField>(
     Ok(())
 }
 
-/// The wire map of `p2e_assemble_wires` from the same binding: a target that is a gate wire lands at
+/// The wire map of `p2e_assemble_wires` / `p2e_assemble_wires_compact` from the same binding (one map serves the u64
+/// matrices and the compact container): a target that is a gate wire lands at
 /// `wire * degree + row` of the proof's wire matrix; virtual targets are reached through the copies plonky2
 /// records for them and are left to `generate_partial_witness`.
 pub fn wire_map_of(binding: &HotPathBinding, degree: usize) -> Vec<P2eWireMapEntry> {

@@ -159,6 +159,15 @@ extern "C" {
     pub fn p2e_gate_internal_batch(ctx: *mut P2eCtx, program: i32, aux: *const u64, ld_aux: usize, gate: *mut u64,
         ld_gate: usize, n: usize) -> i64;
     pub fn p2e_gate_internal_num_cols(program: i32) -> i64;
+    // ---- the same passes inside the compact container (u32 narrow matrix, u32 aux matrix)
+    pub fn p2e_ux_witness_compact_batch(ctx: *mut P2eCtx, program: i32, msg32: *const u8, r32: *const u8, s32: *const u8,
+        pkx32: *const u8, pky32: *const u8, narrow: *const u32, ld_narrow: usize, aux32: *const u32, ld_aux: usize,
+        ux: *mut c_void, ux_u32: i32, ld_ux: usize, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_gate_internal_compact_batch(ctx: *mut P2eCtx, program: i32, aux32: *const u32, ld_aux: usize, gate: *mut u64,
+        ld_gate: usize, n: usize) -> i64;
+    pub fn p2e_assemble_wires_compact(ctx: *mut P2eCtx, map: *const P2eWireMap, narrow: *const u32, ld_narrow: usize,
+        wide: *const u64, ld_wide: usize, aux32: *const u32, ld_aux: usize, ux: *const c_void, ux_u32: i32, ld_ux: usize,
+        gate: *const u64, ld_gate: usize, wires: *mut u64, wire_stride: usize, n: usize) -> i64;
 
     // ---- column maps (host only)
     pub fn p2e_schedule_describe(program: i32, out: *mut P2eGenDesc, cap: usize) -> i64;
@@ -229,4 +238,16 @@ extern "C" {
         ld_wide: usize, n: usize, err: *mut u8, valid: *mut u8) -> i64;
     pub fn p2e_curve_program_compact_layout(prog: *const P2eCurveProgram, col_map: *mut u32, cap: usize, num_narrow: *mut u32,
         num_wide: *mut u32) -> i64;
+    pub fn p2e_curve_msm_ux_witness_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, px32: *const u8, py32: *const u8,
+        qx32: *const u8, qy32: *const u8, n32: *const u8, m32: *const u8, cols: *const u64, ld: usize, aux: *const u64,
+        ld_aux: usize, ux: *mut c_void, ux_u32: i32, ld_ux: usize, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_curve_program_aux_witness_compact_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, msg32: *const u8,
+        r32: *const u8, s32: *const u8, pkx32: *const u8, pky32: *const u8, narrow: *const u32, ld_narrow: usize,
+        aux32: *mut u32, ld_aux: usize, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_curve_program_gate_internal_compact_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, aux32: *const u32,
+        ld_aux: usize, gate: *mut u64, ld_gate: usize, n: usize) -> i64;
+    pub fn p2e_curve_program_ux_witness_compact_batch(ctx: *mut P2eCtx, prog: *const P2eCurveProgram, msg32: *const u8,
+        r32: *const u8, s32: *const u8, pkx32: *const u8, pky32: *const u8, qx32: *const u8, qy32: *const u8,
+        narrow: *const u32, ld_narrow: usize, aux32: *const u32, ld_aux: usize, ux: *mut c_void, ux_u32: i32, ld_ux: usize,
+        n: usize, err: *mut u8) -> i64;
 }
