@@ -52,6 +52,7 @@ extern "C" {
 #define P2E_ERR_CARRY_RANGE 8      /* gates/mul_nonnative.rs:527 carry not < 2^34                              */
 #define P2E_ERR_DIVISION_BY_ZERO 32 /* BigUintDivRemGenerator: b == 0 (BigUint::div_rem panics)                        */
 #define P2E_ERR_QUOTIENT_RANGE 16  /* x*y/m does not fit the gate's nine q wires (x, y far above the modulus)  */
+#define P2E_ERR_POINT_AT_INFINITY 64 /* p2e_ecdsa_public_key_batch: sk = 0 (mod n), AffinePoint::ZERO has no 64-byte form */
 
 /* status codes (negative returns) */
 #define P2E_E_INVALID (-1)   /* null pointer, ld < n, bad field id ...      */
@@ -494,6 +495,34 @@ long p2e_p256_verify_batch(p2e_ctx *ctx, const p2e_curve_program *prog, const ui
 /* synthetic valid signatures on a curve (host only; P2E_CURVE_*), same stream layout as p2e_synth_signatures */
 int p2e_synth_signatures_curve(int curve, uint64_t seed, size_t first, size_t n, uint8_t *msg32, uint8_t *r32, uint8_t *s32,
                                uint8_t *pkx32, uint8_t *pky32);
+
+/* ---- key derivation and signing: the other two functions of the crate's native front end (curve/ecdsa.rs), for a
+ * batch, on either curve (P2E_CURVE_*).  sk32, msg32 and k32 are n x 32-byte little-endian values, each taken modulo the
+ * group order n with one conditional subtraction (the reference's arguments are field elements; this is what
+ * from_noncanonical_biguint yields below 2^256) -- a value >= n is reduced, not flagged.  Outputs are n x 32 bytes each.
+ * plan: P2E_SIGN_PLAN_LANE = one lane per scalar (a 64-deep chain of mixed additions through the generator's fixed-base
+ * table), P2E_SIGN_PLAN_QUAD = four lanes per scalar (16 windows each, then two levels of general additions),
+ * P2E_SIGN_PLAN_AUTO = the library's choice by batch size.  Same results, bit for bit.
+ * The calls run one kernel on the context's caller stream (no internal streams, no scratch).  Return value: number of
+ * flagged elements; P2E_E_INVALID on a null pointer, an unknown curve or an unknown plan; n == 0 returns 0.
+ *
+ * p2e_ecdsa_public_key_batch   ECDSASecretKey::to_public (curve/ecdsa.rs:16-20): (pkx, pky) = affine sk G.
+ *     sk = 0 (mod n): the reference returns AffinePoint::ZERO (curve/curve_types.rs:163-171); zeros are written and
+ *     err[i] = P2E_ERR_POINT_AT_INFINITY.
+ * p2e_ecdsa_sign_batch         sign_message (curve/ecdsa.rs:25-40) with the nonce as an input: R = k G,
+ *     r = R.x mod n, s = k^-1 (msg + r sk) mod n.  k = 0 (mod n), where the reference redraws its nonce (:29-32):
+ *     zeros are written and err[i] = P2E_ERR_INVERSE_OF_ZERO.  r = 0 or s = 0 are returned as computed and NOT flagged,
+ *     as sign_message returns them; such a signature does not verify.
+ * A zero Z of a non-empty sum (impossible for k < n, see csrc/sign.hpp) would set P2E_ERR_INVERSE_OF_ZERO too. */
+#define P2E_SIGN_PLAN_AUTO 0
+#define P2E_SIGN_PLAN_LANE 1
+#define P2E_SIGN_PLAN_QUAD 2
+/* curve/ecdsa.rs:16-20 to_public */
+long p2e_ecdsa_public_key_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *sk32, uint8_t *pkx32, uint8_t *pky32,
+                                size_t n, uint8_t *err);
+/* curve/ecdsa.rs:25-40 sign_message, with the nonce as an input */
+long p2e_ecdsa_sign_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *msg32, const uint8_t *sk32,
+                          const uint8_t *k32, uint8_t *r32, uint8_t *s32, size_t n, uint8_t *err);
 
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */

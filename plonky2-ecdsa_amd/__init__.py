@@ -36,6 +36,8 @@ FIELD_SCALAR = 1  # plonky2 Secp256K1Scalar
 FIELD_P256_BASE, FIELD_P256_SCALAR = 2, 3   # the crate's P256Base / P256Scalar (single-generator entry points)
 ERR_LIMB_RANGE, ERR_VALUE_GE_2_256, ERR_INVERSE_OF_ZERO, ERR_CARRY_RANGE, ERR_QUOTIENT_RANGE = 1, 2, 4, 8, 16
 ERR_DIVISION_BY_ZERO = 32
+ERR_POINT_AT_INFINITY = 64   # ecdsa_public_key_batch: sk = 0 (mod n)
+SIGN_PLAN_AUTO, SIGN_PLAN_LANE, SIGN_PLAN_QUAD = 0, 1, 2   # include/p2e.h P2E_SIGN_PLAN_*
 CTX_HOST_POINTERS, CTX_ASYNC, CTX_PHASE_TIMING = 1, 2, 4
 VERIFY_COLS = 82615
 GLV_MUL_COLS = 65243
@@ -74,6 +76,7 @@ EXPORTS = (
     "p2e_ux_witness_compact_batch", "p2e_gate_internal_compact_batch", "p2e_assemble_wires_compact",
     "p2e_curve_program_aux_witness_compact_batch", "p2e_curve_program_gate_internal_compact_batch",
     "p2e_curve_program_ux_witness_compact_batch", "p2e_curve_msm_ux_witness_batch",
+    "p2e_ecdsa_public_key_batch", "p2e_ecdsa_sign_batch",
 )
 
 
@@ -996,6 +999,36 @@ class Context:
         bad = self._check(self._L.p2e_ecdsa_verify_batch(self._h, _ptr(msg), _ptr(r), _ptr(s), _ptr(pkx), _ptr(pky),
                                                          C.c_size_t(n), _ptr(err), _ptr(valid)))
         return err, valid, bad
+
+    # ---- key derivation and signing (include/p2e.h p2e_ecdsa_public_key_batch / p2e_ecdsa_sign_batch) ----------------
+    def _packed(self, n):
+        if self.host_pointers:
+            return np.zeros((n, 32), dtype=np.uint8)
+        import torch
+        return torch.empty((n, 32), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def ecdsa_public_key_batch(self, sk, curve=CURVE_SECP256K1, plan=SIGN_PLAN_AUTO, pkx=None, pky=None, err=None):
+        """ECDSASecretKey::to_public (curve/ecdsa.rs:16-20) of (n, 32) little-endian secret keys, each taken modulo the group
+        order: (pkx, pky, err, flagged count).  sk = 0 (mod n): zeros and ERR_POINT_AT_INFINITY."""
+        n = self._shape(sk)[0]
+        pkx = pkx if pkx is not None else self._packed(n)
+        pky = pky if pky is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_ecdsa_public_key_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(sk), _ptr(pkx), _ptr(pky),
+                                                             C.c_size_t(n), _ptr(err)))
+        return pkx, pky, err, bad
+
+    def ecdsa_sign_batch(self, msg, sk, k, curve=CURVE_SECP256K1, plan=SIGN_PLAN_AUTO, r=None, s=None, err=None):
+        """sign_message (curve/ecdsa.rs:25-40) with the nonces k as an input; msg, sk, k are (n, 32) little-endian, each taken
+        modulo the group order: (r, s, err, flagged count).  k = 0 (mod n): zeros and ERR_INVERSE_OF_ZERO; r = 0 or s = 0 are
+        returned unflagged (they do not verify)."""
+        n = self._shape(msg)[0]
+        r = r if r is not None else self._packed(n)
+        s = s if s is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_ecdsa_sign_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(msg), _ptr(sk), _ptr(k), _ptr(r),
+                                                       _ptr(s), C.c_size_t(n), _ptr(err)))
+        return r, s, err, bad
 
     def _compact_out(self, program, n, narrow, wide, ld_narrow, ld_wide):
         _m, nn, nw = compact_layout(program)

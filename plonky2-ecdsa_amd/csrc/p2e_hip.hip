@@ -18,6 +18,7 @@
 #include "quad.hpp"
 #include "schedule.hpp"
 #include "curve_program.hpp"
+#include "sign.hpp"
 
 using namespace p2e;
 using host::COMPACT_WIDE;
@@ -635,6 +636,10 @@ struct p2e_ctx {
     unsigned expand_lds = 0;   // the same knob for the large-batch plan
     Aff* d_cpts = nullptr;
     Aff* d_fbtab = nullptr;
+    Aff* d_fbtab_p256 = nullptr;   // P-256 generator table of the key-derivation / signing calls: built and uploaded on first use
+    // p2e_ecdsa_public_key_batch / p2e_ecdsa_sign_batch with P2E_SIGN_PLAN_AUTO: four lanes per scalar up to this batch
+    // size, one lane per scalar above it (MEASUREMENTS.md, "Batch key derivation and signing")
+    size_t sign_quad_max_n = 65536;
     U256* d_constv = nullptr;   // circuit constants by id (AUX_SRC_CONST | id), for the constraint-block pass
     DeviceProgram progs[2];
     void* scratch = nullptr;
@@ -993,6 +998,7 @@ extern "C" void p2e_ctx_destroy(p2e_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipFree(c->d_cpts);
     (void)hipFree(c->d_fbtab);
+    (void)hipFree(c->d_fbtab_p256);
     (void)hipFree(c->d_constv);
     for (auto& p : c->progs) {
         (void)hipFree(p.d_ux_items);
@@ -2456,6 +2462,132 @@ extern "C" int p2e_synth_signatures(uint64_t seed, size_t first, size_t n, uint8
         std::memcpy(pky32 + 32 * i, pk.y.w, 32);
     }
     return 0;
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// key derivation and signing (sign.hpp): curve/ecdsa.rs:16-20 to_public, :25-40 sign_message
+// ====================================================================================================
+// one launch on the caller's stream; msg == nullptr: the key kernel (out1 / out2 = pk.x / pk.y), else the signer (r / s).
+// Defined (and explicitly instantiated) where the curve's chain code lives: secp256k1 in part 2, P-256 in part 3.
+template <class CV>
+void launch_sign(p2e_ctx* c, int plan, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* k, uint8_t* out1,
+                 uint8_t* out2, size_t n, uint8_t* err);
+#if P2E_HAS(2) || P2E_HAS(3)
+template <class CV>
+void launch_sign(p2e_ctx* c, int plan, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* k, uint8_t* out1,
+                 uint8_t* out2, size_t n, uint8_t* err) {
+    const bool quad = plan == SIGN_PLAN_QUAD;
+    const dim3 grid = grid1(quad ? 4 * n : n);
+    if (!msg) {
+        if (quad)
+            hipLaunchKernelGGL((k_public_key<CV, SIGN_PLAN_QUAD>), grid, dim3(BS), 0, c->stream, table, sk, out1, out2, n, err, c->d_counter);
+        else
+            hipLaunchKernelGGL((k_public_key<CV, SIGN_PLAN_LANE>), grid, dim3(BS), 0, c->stream, table, sk, out1, out2, n, err, c->d_counter);
+    } else if (quad) {
+        hipLaunchKernelGGL((k_sign<CV, SIGN_PLAN_QUAD>), grid, dim3(BS), 0, c->stream, table, msg, sk, k, out1, out2, n, err, c->d_counter);
+    } else {
+        hipLaunchKernelGGL((k_sign<CV, SIGN_PLAN_LANE>), grid, dim3(BS), 0, c->stream, table, msg, sk, k, out1, out2, n, err, c->d_counter);
+    }
+}
+#if P2E_PART < 0 || P2E_PART == 2
+template void launch_sign<Secp256k1>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, size_t,
+                                     uint8_t*);
+#endif
+#if P2E_PART < 0 || P2E_PART == 3
+template void launch_sign<P256>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, size_t,
+                                uint8_t*);
+#endif
+#endif   // P2E_HAS(2) || P2E_HAS(3)
+
+#if P2E_HAS(0)
+// curve / plan checks shared by the two calls, and the curve's generator table (P-256: made on first use, kept)
+static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Aff** table, int* chosen) {
+    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
+        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
+        return P2E_E_INVALID;
+    }
+    if (plan != P2E_SIGN_PLAN_AUTO && plan != P2E_SIGN_PLAN_LANE && plan != P2E_SIGN_PLAN_QUAD) {
+        set_error("unknown plan (P2E_SIGN_PLAN_AUTO, P2E_SIGN_PLAN_LANE or P2E_SIGN_PLAN_QUAD)");
+        return P2E_E_INVALID;
+    }
+    if (n > ((size_t)1 << 31)) {
+        set_error("batch too large for one launch");
+        return P2E_E_INVALID;
+    }
+    *chosen = plan == P2E_SIGN_PLAN_AUTO ? (n <= c->sign_quad_max_n ? SIGN_PLAN_QUAD : SIGN_PLAN_LANE) : (int)plan;
+    if (curve == P2E_CURVE_SECP256K1) {
+        *table = c->d_fbtab;
+        return 0;
+    }
+    if (!c->d_fbtab_p256 && n) {
+        DeviceGuard guard(c->device);
+        static const std::vector<Aff> t = host::fixed_base_table_cv<P256>(host::generator_cv<P256>());
+        Aff* d = nullptr;
+        HIP_TRY(hipMalloc(&d, sizeof(Aff) * t.size()));
+        hipError_t e = hipMemcpy(d, t.data(), sizeof(Aff) * t.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            (void)hipGetLastError();
+            set_error(std::string("upload of the P-256 generator table failed: ") + hipGetErrorString(e));
+            return P2E_E_HIP;
+        }
+        c->d_fbtab_p256 = d;
+    }
+    *table = c->d_fbtab_p256;
+    return 0;
+}
+extern "C" long p2e_ecdsa_public_key_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* sk32, uint8_t* pkx32, uint8_t* pky32,
+                                           size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!sk32 || !pkx32 || !pky32 || !err) {
+        set_error("null pointer (sk32, pkx32, pky32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    int chosen = 0;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    sk32 = S.in(sk32, n * 32);
+    pkx32 = S.out(pkx32, n * 32);
+    pky32 = S.out(pky32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (curve == P2E_CURVE_P256)
+        launch_sign<P256>(c, chosen, table, nullptr, sk32, nullptr, pkx32, pky32, n, err);
+    else
+        launch_sign<Secp256k1>(c, chosen, table, nullptr, sk32, nullptr, pkx32, pky32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_ecdsa_sign_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* k32,
+                                     uint8_t* r32, uint8_t* s32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !sk32 || !k32 || !r32 || !s32 || !err) {
+        set_error("null pointer (msg32, sk32, k32, r32, s32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    int chosen = 0;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    msg32 = S.in(msg32, n * 32);
+    sk32 = S.in(sk32, n * 32);
+    k32 = S.in(k32, n * 32);
+    r32 = S.out(r32, n * 32);
+    s32 = S.out(s32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (curve == P2E_CURVE_P256)
+        launch_sign<P256>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
+    else
+        launch_sign<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
+    return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)
 

@@ -91,6 +91,46 @@ pub fn wire_map_of(binding: &HotPathBinding, degree: usize) -> Vec<P2eWireMapEnt
         .collect()
 }
 
+/// `ECDSASecretKey::to_public` (curve/ecdsa.rs:16-20) for a batch, on `P2E_CURVE_SECP256K1` or `P2E_CURVE_P256`: affine
+/// `(x, y)` of `sk * G` per key.  A key that is 0 modulo the group order has no affine public key (the reference returns
+/// `AffinePoint::ZERO`): surfaced as `Err`.  `ctx` was created with `P2E_CTX_HOST_POINTERS`.
+pub fn public_keys(ctx: *mut P2eCtx, curve: i32, sks: &[BigUint]) -> Result<Vec<(BigUint, BigUint)>> {
+    let n = sks.len();
+    let sk = pack32(sks.iter().cloned(), n);
+    let (mut px, mut py, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_ecdsa_public_key_batch(ctx, curve, P2E_SIGN_PLAN_AUTO, sk.as_ptr(), px.as_mut_ptr(), py.as_mut_ptr(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    (0..n)
+        .map(|i| {
+            ensure!(err[i] == 0, "secret key {i}: no affine public key (error bits {:#x})", err[i]);
+            Ok((BigUint::from_bytes_le(&px[32 * i..32 * i + 32]), BigUint::from_bytes_le(&py[32 * i..32 * i + 32])))
+        })
+        .collect()
+}
+
+/// `sign_message` (curve/ecdsa.rs:25-40) for a batch with the caller's nonces: `(r, s)` per `(msg, sk, k)`.  A nonce that
+/// is 0 modulo the group order (where the reference draws another one) is surfaced as `Err`; `r == 0` or `s == 0` are
+/// returned as computed, as the reference returns them.
+pub fn sign_messages(ctx: *mut P2eCtx, curve: i32, msgs: &[BigUint], sks: &[BigUint], nonces: &[BigUint]) -> Result<Vec<(BigUint, BigUint)>> {
+    let n = msgs.len();
+    ensure!(sks.len() == n && nonces.len() == n);
+    let (msg, sk, k) = (pack32(msgs.iter().cloned(), n), pack32(sks.iter().cloned(), n), pack32(nonces.iter().cloned(), n));
+    let (mut r, mut s, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_ecdsa_sign_batch(ctx, curve, P2E_SIGN_PLAN_AUTO, msg.as_ptr(), sk.as_ptr(), k.as_ptr(), r.as_mut_ptr(), s.as_mut_ptr(), n,
+                             err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    (0..n)
+        .map(|i| {
+            ensure!(err[i] == 0, "signature {i}: unusable nonce (error bits {:#x})", err[i]);
+            Ok((BigUint::from_bytes_le(&r[32 * i..32 * i + 32]), BigUint::from_bytes_le(&s[32 * i..32 * i + 32])))
+        })
+        .collect()
+}
+
 /// One built circuit of `verify_p256_message_circuit` (gadgets/ecdsa.rs:55-78): its hot-path output targets in
 /// registration order (len == 115 557 = `p2e_curve_program_num_cols`) and the library's program object, which carries
 /// the point `precompute_window` drew with `rand()` while THIS circuit was built (gadgets/curve_windowed_mul.rs:57).

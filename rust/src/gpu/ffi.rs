@@ -78,6 +78,10 @@ pub struct P2eCurveProgram {
 }
 pub const P2E_CURVE_SECP256K1: i32 = 0;
 pub const P2E_CURVE_P256: i32 = 1;
+pub const P2E_SIGN_PLAN_AUTO: u32 = 0;
+pub const P2E_SIGN_PLAN_LANE: u32 = 1;
+pub const P2E_SIGN_PLAN_QUAD: u32 = 2;
+pub const P2E_ERR_POINT_AT_INFINITY: u8 = 64;
 pub const P2E_CP_WINDOWED_MUL: i32 = 1;
 pub const P2E_CP_SCALAR_MUL: i32 = 2;
 pub const P2E_CP_VERIFY: i32 = 3;
@@ -183,6 +187,12 @@ extern "C" {
         ld_narrow: usize, wide: *mut u64, ld_wide: usize, err: *mut u8) -> i64;
     pub fn p2e_compact_to_rows(ctx: *mut P2eCtx, program: i32, narrow: *const u32, ld_narrow: usize, wide: *const u64,
         ld_wide: usize, n: usize, rows_narrow: *mut u32, row_ld_narrow: usize, rows_wide: *mut u64, row_ld_wide: usize) -> i64;
+
+    // ---- key derivation and signing on either curve: curve/ecdsa.rs:16-20 to_public, :25-40 sign_message (nonce as an input)
+    pub fn p2e_ecdsa_public_key_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, sk32: *const u8, pkx32: *mut u8, pky32: *mut u8,
+        n: usize, err: *mut u8) -> i64;
+    pub fn p2e_ecdsa_sign_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, msg32: *const u8, sk32: *const u8, k32: *const u8,
+        r32: *mut u8, s32: *mut u8, n: usize, err: *mut u8) -> i64;
 
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
