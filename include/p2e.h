@@ -53,6 +53,7 @@ extern "C" {
 #define P2E_ERR_DIVISION_BY_ZERO 32 /* BigUintDivRemGenerator: b == 0 (BigUint::div_rem panics)                        */
 #define P2E_ERR_QUOTIENT_RANGE 16  /* x*y/m does not fit the gate's nine q wires (x, y far above the modulus)  */
 #define P2E_ERR_POINT_AT_INFINITY 64 /* p2e_ecdsa_public_key_batch: sk = 0 (mod n), AffinePoint::ZERO has no 64-byte form */
+#define P2E_ERR_NOT_RECOVERABLE 128  /* p2e_ecdsa_recover_batch: (r, s, v) names no curve point R (the last free bit) */
 
 /* status codes (negative returns) */
 #define P2E_E_INVALID (-1)   /* null pointer, ld < n, bad field id ...      */
@@ -523,6 +524,29 @@ long p2e_ecdsa_public_key_batch(p2e_ctx *ctx, int curve, unsigned plan, const ui
 /* curve/ecdsa.rs:25-40 sign_message, with the nonce as an input */
 long p2e_ecdsa_sign_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *msg32, const uint8_t *sk32,
                           const uint8_t *k32, uint8_t *r32, uint8_t *s32, size_t n, uint8_t *err);
+
+/* ---- public-key recovery: (msg, r, s, v) -> pk, the form in which Ethereum-style batches arrive (no key, one byte v),
+ * on either curve (P2E_CURVE_*).  All 32-byte values little-endian, element i at +32 i; v[i] is one byte:
+ *     bit 0 = the parity of R.y,   bit 1 = "R.x = r + n" (the abscissa was >= n before base_to_scalar reduced it).
+ * The caller subtracts Ethereum's 27 or the EIP-155 offset; the library does not guess.  msg32 is taken modulo n with one
+ * conditional subtraction, exactly as p2e_ecdsa_sign_batch takes it (reduced, not flagged); r32 and s32 are not reduced.
+ *
+ * p2e_ecdsa_recover_batch      pk = r^-1 (s R - msg G) = u1 G + u2 R, u1 = -msg r^-1, u2 = s r^-1 (mod n), R the curve
+ *     point with x = r + n (v >> 1) and y = v & 1 (mod 2); (pkx, pky) = its canonical affine coordinates.
+ *     Flagged elements (zeros are written to both outputs):
+ *     P2E_ERR_NOT_RECOVERABLE    r = 0, r >= n, s = 0, s >= n, v > 3, x >= p, or x^3 + a x + b is not a square;
+ *     P2E_ERR_POINT_AT_INFINITY  u1 G + u2 R is the neutral element (s R = msg G).
+ *     A recoverable signature of "someone else" is not an error: any well-formed (r, s, v) names some key.
+ * p2e_ecdsa_sign_recoverable_batch   p2e_ecdsa_sign_batch plus v[i] = (R.y & 1) | (R.x >= n ? 2 : 0), 0 where flagged;
+ *     r, s and err are bit for bit those of p2e_ecdsa_sign_batch for the same inputs and plan.
+ * One kernel per call on the context's caller stream, one lane per signature in the recovery (no internal streams, no
+ * scratch, no LDS).  Return value: number of flagged elements; P2E_E_INVALID on a null pointer, an unknown curve (or
+ * plan); n == 0 returns 0.  Host pointers, async mode and the current device behave as for the signing calls.
+ * A zero Z at the end of the walk (impossible, see csrc/recover.hpp) would set P2E_ERR_INVERSE_OF_ZERO. */
+long p2e_ecdsa_recover_batch(p2e_ctx *ctx, int curve, const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32,
+                             const uint8_t *v, uint8_t *pkx32, uint8_t *pky32, size_t n, uint8_t *err);
+long p2e_ecdsa_sign_recoverable_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *msg32, const uint8_t *sk32,
+                                      const uint8_t *k32, uint8_t *r32, uint8_t *s32, uint8_t *v, size_t n, uint8_t *err);
 
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */

@@ -37,6 +37,7 @@ FIELD_P256_BASE, FIELD_P256_SCALAR = 2, 3   # the crate's P256Base / P256Scalar 
 ERR_LIMB_RANGE, ERR_VALUE_GE_2_256, ERR_INVERSE_OF_ZERO, ERR_CARRY_RANGE, ERR_QUOTIENT_RANGE = 1, 2, 4, 8, 16
 ERR_DIVISION_BY_ZERO = 32
 ERR_POINT_AT_INFINITY = 64   # ecdsa_public_key_batch: sk = 0 (mod n)
+ERR_NOT_RECOVERABLE = 128    # ecdsa_recover_batch: (r, s, v) names no curve point
 SIGN_PLAN_AUTO, SIGN_PLAN_LANE, SIGN_PLAN_QUAD = 0, 1, 2   # include/p2e.h P2E_SIGN_PLAN_*
 CTX_HOST_POINTERS, CTX_ASYNC, CTX_PHASE_TIMING = 1, 2, 4
 VERIFY_COLS = 82615
@@ -77,6 +78,7 @@ EXPORTS = (
     "p2e_curve_program_aux_witness_compact_batch", "p2e_curve_program_gate_internal_compact_batch",
     "p2e_curve_program_ux_witness_compact_batch", "p2e_curve_msm_ux_witness_batch",
     "p2e_ecdsa_public_key_batch", "p2e_ecdsa_sign_batch",
+    "p2e_ecdsa_recover_batch", "p2e_ecdsa_sign_recoverable_batch",
 )
 
 
@@ -1029,6 +1031,30 @@ class Context:
         bad = self._check(self._L.p2e_ecdsa_sign_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(msg), _ptr(sk), _ptr(k), _ptr(r),
                                                        _ptr(s), C.c_size_t(n), _ptr(err)))
         return r, s, err, bad
+
+    def ecdsa_sign_recoverable_batch(self, msg, sk, k, curve=CURVE_SECP256K1, plan=SIGN_PLAN_AUTO, r=None, s=None, v=None, err=None):
+        """ecdsa_sign_batch plus the recovery byte v (n,): bit 0 = parity of R.y, bit 1 = R.x >= n; 0 where flagged:
+        (r, s, v, err, flagged count).  r, s, err are bit for bit those of ecdsa_sign_batch."""
+        n = self._shape(msg)[0]
+        r = r if r is not None else self._packed(n)
+        s = s if s is not None else self._packed(n)
+        v = v if v is not None else self._vec(n, np.uint8)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_ecdsa_sign_recoverable_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(msg), _ptr(sk), _ptr(k),
+                                                                   _ptr(r), _ptr(s), _ptr(v), C.c_size_t(n), _ptr(err)))
+        return r, s, v, err, bad
+
+    def ecdsa_recover_batch(self, msg, r, s, v, curve=CURVE_SECP256K1, pkx=None, pky=None, err=None):
+        """The public key of every (msg, r, s, v): pk = r^-1 (s R - msg G), R the point with x = r + n (v >> 1) and
+        y = v & 1 (mod 2); v (n,) uint8 carries no offset (subtract Ethereum's 27 / the EIP-155 term first).
+        (pkx, pky, err, flagged count); zeros and ERR_NOT_RECOVERABLE / ERR_POINT_AT_INFINITY where there is no key."""
+        n = self._shape(msg)[0]
+        pkx = pkx if pkx is not None else self._packed(n)
+        pky = pky if pky is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_ecdsa_recover_batch(self._h, C.c_int(curve), _ptr(msg), _ptr(r), _ptr(s), _ptr(v), _ptr(pkx),
+                                                          _ptr(pky), C.c_size_t(n), _ptr(err)))
+        return pkx, pky, err, bad
 
     def _compact_out(self, program, n, narrow, wide, ld_narrow, ld_wide):
         _m, nn, nw = compact_layout(program)

@@ -19,6 +19,7 @@
 #include "schedule.hpp"
 #include "curve_program.hpp"
 #include "sign.hpp"
+#include "recover.hpp"
 
 using namespace p2e;
 using host::COMPACT_WIDE;
@@ -2473,6 +2474,12 @@ extern "C" int p2e_synth_signatures(uint64_t seed, size_t first, size_t n, uint8
 template <class CV>
 void launch_sign(p2e_ctx* c, int plan, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* k, uint8_t* out1,
                  uint8_t* out2, size_t n, uint8_t* err);
+template <class CV>
+void launch_sign_recoverable(p2e_ctx* c, int plan, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* k, uint8_t* r,
+                             uint8_t* s, uint8_t* v, size_t n, uint8_t* err);
+template <class CV>
+void launch_recover(p2e_ctx* c, const Aff* table, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* v, uint8_t* pkx,
+                    uint8_t* pky, size_t n, uint8_t* err);
 #if P2E_HAS(2) || P2E_HAS(3)
 template <class CV>
 void launch_sign(p2e_ctx* c, int plan, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* k, uint8_t* out1,
@@ -2490,11 +2497,35 @@ void launch_sign(p2e_ctx* c, int plan, const Aff* table, const uint8_t* msg, con
         hipLaunchKernelGGL((k_sign<CV, SIGN_PLAN_LANE>), grid, dim3(BS), 0, c->stream, table, msg, sk, k, out1, out2, n, err, c->d_counter);
     }
 }
+// the signer with the recovery byte, and the recovery itself (recover.hpp): one lane per signature, one launch
+template <class CV>
+void launch_sign_recoverable(p2e_ctx* c, int plan, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* k, uint8_t* r,
+                             uint8_t* s, uint8_t* v, size_t n, uint8_t* err) {
+    if (plan == SIGN_PLAN_QUAD)
+        hipLaunchKernelGGL((k_sign_recoverable<CV, SIGN_PLAN_QUAD>), grid1(4 * n), dim3(BS), 0, c->stream, table, msg, sk, k, r, s, v, n, err,
+                           c->d_counter);
+    else
+        hipLaunchKernelGGL((k_sign_recoverable<CV, SIGN_PLAN_LANE>), grid1(n), dim3(BS), 0, c->stream, table, msg, sk, k, r, s, v, n, err,
+                           c->d_counter);
+}
+template <class CV>
+void launch_recover(p2e_ctx* c, const Aff* table, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* v, uint8_t* pkx,
+                    uint8_t* pky, size_t n, uint8_t* err) {
+    hipLaunchKernelGGL((k_recover<CV>), grid1(n), dim3(BS), 0, c->stream, table, msg, r, s, v, pkx, pky, n, err, c->d_counter);
+}
 #if P2E_PART < 0 || P2E_PART == 2
+template void launch_sign_recoverable<Secp256k1>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*,
+                                                 uint8_t*, size_t, uint8_t*);
+template void launch_recover<Secp256k1>(p2e_ctx*, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*,
+                                        uint8_t*, size_t, uint8_t*);
 template void launch_sign<Secp256k1>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, size_t,
                                      uint8_t*);
 #endif
 #if P2E_PART < 0 || P2E_PART == 3
+template void launch_sign_recoverable<P256>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, uint8_t*,
+                                            size_t, uint8_t*);
+template void launch_recover<P256>(p2e_ctx*, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*,
+                                   size_t, uint8_t*);
 template void launch_sign<P256>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, size_t,
                                 uint8_t*);
 #endif
@@ -2587,6 +2618,63 @@ extern "C" long p2e_ecdsa_sign_batch(p2e_ctx* c, int curve, unsigned plan, const
         launch_sign<P256>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
     else
         launch_sign<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
+    return S.done(finish_call(c));
+}
+// sign_message with the recovery byte, and the recovery of the public key from (msg, r, s, v) (recover.hpp)
+extern "C" long p2e_ecdsa_sign_recoverable_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32,
+                                                 const uint8_t* k32, uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !sk32 || !k32 || !r32 || !s32 || !v || !err) {
+        set_error("null pointer (msg32, sk32, k32, r32, s32, v and err are all required)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    int chosen = 0;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    msg32 = S.in(msg32, n * 32);
+    sk32 = S.in(sk32, n * 32);
+    k32 = S.in(k32, n * 32);
+    r32 = S.out(r32, n * 32);
+    s32 = S.out(s32, n * 32);
+    v = S.out(v, n);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (curve == P2E_CURVE_P256)
+        launch_sign_recoverable<P256>(c, chosen, table, msg32, sk32, k32, r32, s32, v, n, err);
+    else
+        launch_sign_recoverable<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, v, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_ecdsa_recover_batch(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32, const uint8_t* v,
+                                        uint8_t* pkx32, uint8_t* pky32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !r32 || !s32 || !v || !pkx32 || !pky32 || !err) {
+        set_error("null pointer (msg32, r32, s32, v, pkx32, pky32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    int chosen = 0;
+    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &chosen)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    msg32 = S.in(msg32, n * 32);
+    r32 = S.in(r32, n * 32);
+    s32 = S.in(s32, n * 32);
+    v = S.in(v, n);
+    pkx32 = S.out(pkx32, n * 32);
+    pky32 = S.out(pky32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (curve == P2E_CURVE_P256)
+        launch_recover<P256>(c, table, msg32, r32, s32, v, pkx32, pky32, n, err);
+    else
+        launch_recover<Secp256k1>(c, table, msg32, r32, s32, v, pkx32, pky32, n, err);
     return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)

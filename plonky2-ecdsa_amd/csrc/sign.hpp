@@ -68,6 +68,7 @@ struct SignArith<CV, false> {
     }
     P2E_HD static Pt add_mixed(const Pt& p, const Pt& q) { return jac_add_cv<CV, false, true>(p, q).p; }
     P2E_HD static Pt add(const Pt& p, const Pt& q) { return jac_add_cv<CV, false, false>(p, q).p; }
+    P2E_HD static Pt dbl(const Pt& p) { return jac_dbl_cv<CV>(p).p; }   // (recover.hpp; nothing in this file doubles)
     P2E_HD static Pt select(bool c, const Pt& t, const Pt& f) {
         Pt r;
         r.X = u256_select(c, t.X, f.X);
@@ -112,6 +113,7 @@ struct SignArith<CV, true> {
     // (operands and results: tight limbs -- X3, Y3 leave jac_add29 through f29_norm, Z3 through a multiplication)
     P2E_HD static Pt add_mixed(const Pt& p, const Pt& q) { return jac_add29<false, true>(p, q).p; }
     P2E_HD static Pt add(const Pt& p, const Pt& q) { return jac_add29<false, false>(p, q).p; }
+    P2E_HD static Pt dbl(const Pt& p) { return jac_dbl29(p).p; }
     P2E_HD static Pt select(bool c, const Pt& t, const Pt& f) {
         Pt r;
         r.X = f29_select(c, t.X, f.X);
@@ -289,10 +291,11 @@ P2E_HD uint8_t body_public_key(const Aff* T, const uint8_t* sk32, uint8_t* pkx32
     return e;
 }
 
-// sign_message of element i with nonce k32[i]
-template <class CV, int PLAN>
+// sign_message of element i with nonce k32[i].  RECOVERABLE: also v8[i] = (R.y & 1) | (R.x >= n ? 2 : 0), what
+// recover.hpp needs to find R again (0 where flagged); r, s and the err byte are those of the plain form.
+template <class CV, int PLAN, bool RECOVERABLE = false>
 P2E_HD uint8_t body_sign(const Aff* T, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* k32, uint8_t* r32, uint8_t* s32,
-                         size_t i, int role) {
+                         size_t i, int role, uint8_t* v8 = nullptr) {
     typedef typename CV::Fn Fn;
     const U256 k = sign_scalar<CV>(k32, i);
     const SignSum<CV> R = sign_base_mul<CV, PLAN>(T, k, role);
@@ -300,17 +303,20 @@ P2E_HD uint8_t body_sign(const Aff* T, const uint8_t* msg32, const uint8_t* sk32
     uint8_t e = 0;
     U256 r = u256_zero(), s = u256_zero(), x, y;
     U256 kinv;
+    u32 v = 0;
     if (!R.have || !fe_inv_safegcd<Fn>(k, kinv)) {   // k = 0 (mod n): both at once
         e = ERR_INVERSE_OF_ZERO;
-    } else if (!sign_to_affine<CV, false>(R, x, y)) {
+    } else if (!sign_to_affine<CV, RECOVERABLE>(R, x, y)) {
         e = ERR_INVERSE_OF_ZERO;
     } else {
         const U256 sk = sign_scalar<CV>(sk32, i), msg = sign_scalar<CV>(msg32, i);
         r = fe_canon<Fn>(x);   // base_to_scalar (curve/curve_types.rs:280-282): x < p < 2 n
         s = fe_mul<Fn>(kinv, fe_add<Fn>(msg, fe_mul<Fn>(r, sk)));
+        if (RECOVERABLE) v = (y.w[0] & 1u) | (geq_mod<Fn>(x.w) ? 2u : 0u);
     }
     store_packed(r32, i, r);
     store_packed(s32, i, s);
+    if (RECOVERABLE) v8[i] = (uint8_t)v;
     return e;
 }
 
@@ -343,6 +349,21 @@ __global__ __launch_bounds__(256) void k_sign(const Aff* T, const uint8_t* msg32
     uint8_t e = 0;
     if (i < n) {
         e = body_sign<CV, PLAN>(T, msg32, sk32, k32, r32, s32, i, role);
+        if (role == 0) err[i] = e;
+    }
+    sign_count_err(e, counter);
+}
+// k_sign with the recovery byte (body_sign<CV, PLAN, true>)
+template <class CV, int PLAN>
+__global__ __launch_bounds__(256) void k_sign_recoverable(const Aff* T, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* k32,
+                                                          uint8_t* r32, uint8_t* s32, uint8_t* v8, size_t n, uint8_t* err,
+                                                          unsigned long long* counter) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = PLAN == SIGN_PLAN_QUAD ? g >> 2 : g;
+    const int role = PLAN == SIGN_PLAN_QUAD ? (int)(g & 3) : 0;
+    uint8_t e = 0;
+    if (i < n) {
+        e = body_sign<CV, PLAN, true>(T, msg32, sk32, k32, r32, s32, i, role, v8);
         if (role == 0) err[i] = e;
     }
     sign_count_err(e, counter);

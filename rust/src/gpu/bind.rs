@@ -131,6 +131,47 @@ pub fn sign_messages(ctx: *mut P2eCtx, curve: i32, msgs: &[BigUint], sks: &[BigU
         .collect()
 }
 
+/// Public keys of a batch of `(msg, r, s, v)` signatures (`p2e_ecdsa_recover_batch`, host-pointer context): `v` without any
+/// offset (bit 0 = parity of R.y, bit 1 = R.x >= n).  `None` where the signature names no key (error bits in the library's
+/// err byte: not recoverable, or the neutral element).
+pub fn recover_public_keys(ctx: *mut P2eCtx, curve: i32, msgs: &[BigUint], sigs: &[(BigUint, BigUint, u8)]) -> Result<Vec<Option<(BigUint, BigUint)>>> {
+    let n = msgs.len();
+    ensure!(sigs.len() == n);
+    let msg = pack32(msgs.iter().cloned(), n);
+    let (r, s) = (pack32(sigs.iter().map(|t| t.0.clone()), n), pack32(sigs.iter().map(|t| t.1.clone()), n));
+    let v: Vec<u8> = sigs.iter().map(|t| t.2).collect();
+    let (mut pkx, mut pky, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_ecdsa_recover_batch(ctx, curve, msg.as_ptr(), r.as_ptr(), s.as_ptr(), v.as_ptr(), pkx.as_mut_ptr(), pky.as_mut_ptr(), n,
+                                err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n)
+        .map(|i| {
+            (err[i] == 0).then(|| (BigUint::from_bytes_le(&pkx[32 * i..32 * i + 32]), BigUint::from_bytes_le(&pky[32 * i..32 * i + 32])))
+        })
+        .collect())
+}
+
+/// `sign_messages` with the recovery byte: `(r, s, v)` per message (`p2e_ecdsa_sign_recoverable_batch`).
+pub fn sign_messages_recoverable(ctx: *mut P2eCtx, curve: i32, msgs: &[BigUint], sks: &[BigUint], nonces: &[BigUint]) -> Result<Vec<(BigUint, BigUint, u8)>> {
+    let n = msgs.len();
+    ensure!(sks.len() == n && nonces.len() == n);
+    let (msg, sk, k) = (pack32(msgs.iter().cloned(), n), pack32(sks.iter().cloned(), n), pack32(nonces.iter().cloned(), n));
+    let (mut r, mut s, mut v, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_ecdsa_sign_recoverable_batch(ctx, curve, P2E_SIGN_PLAN_AUTO, msg.as_ptr(), sk.as_ptr(), k.as_ptr(), r.as_mut_ptr(),
+                                         s.as_mut_ptr(), v.as_mut_ptr(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    (0..n)
+        .map(|i| {
+            ensure!(err[i] == 0, "signature {i}: unusable nonce (error bits {:#x})", err[i]);
+            Ok((BigUint::from_bytes_le(&r[32 * i..32 * i + 32]), BigUint::from_bytes_le(&s[32 * i..32 * i + 32]), v[i]))
+        })
+        .collect()
+}
+
 /// One built circuit of `verify_p256_message_circuit` (gadgets/ecdsa.rs:55-78): its hot-path output targets in
 /// registration order (len == 115 557 = `p2e_curve_program_num_cols`) and the library's program object, which carries
 /// the point `precompute_window` drew with `rand()` while THIS circuit was built (gadgets/curve_windowed_mul.rs:57).

@@ -193,6 +193,11 @@ extern "C" {
         n: usize, err: *mut u8) -> i64;
     pub fn p2e_ecdsa_sign_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, msg32: *const u8, sk32: *const u8, k32: *const u8,
         r32: *mut u8, s32: *mut u8, n: usize, err: *mut u8) -> i64;
+    // ---- public-key recovery from (msg, r, s, v), and the signer that also writes v (bit 0: parity of R.y, bit 1: R.x >= n)
+    pub fn p2e_ecdsa_recover_batch(ctx: *mut P2eCtx, curve: i32, msg32: *const u8, r32: *const u8, s32: *const u8, v: *const u8,
+        pkx32: *mut u8, pky32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_ecdsa_sign_recoverable_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, msg32: *const u8, sk32: *const u8,
+        k32: *const u8, r32: *mut u8, s32: *mut u8, v: *mut u8, n: usize, err: *mut u8) -> i64;
 
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
