@@ -97,23 +97,16 @@ __global__ __launch_bounds__(BS) void kc_ux_compact(UxArgs A, size_t first) {
 
 struct p2e_curve_program {
     host::CurveProgramHost H;
-    int device = 0;
-    OpDesc* d_ops = nullptr;        // every op expanded on its own
-    OpDesc* d_ops_runs = nullptr;   // with the run marks (F_NO_AFFINE) of CP_RUN_ITERS and of the fixed-base windows
-    Aff* d_cpts = nullptr;
-    Aff* d_fbtab = nullptr;
-    AuxItem* d_aux_items = nullptr;
-    AuxTables* d_aux_tab = nullptr;
-    GateItem* d_gate_items = nullptr;
-    UxItem* d_ux_items = nullptr;
-    UxItem* d_ux_items_compact = nullptr;   // in compact coordinates (host::ux_items_compact)
-    U256* d_constv = nullptr;   // constants by source id: points at 2c / 2c + 1, scalar constants from AUX_GCONST_BASE
     // compact container (include/p2e.h p2e_curve_program_compact_layout): per column its slot in the u32 narrow matrix
     // or COMPACT_WIDE | slot in the u64 wide matrix (the check_sum / carry columns of the mul generators), in
     // registration order; wide_before[c] = wide columns before column c (the emitters' second cursor)
-    std::vector<u32> compact_map, wide_before;
-    u32 num_narrow = 0, num_wide = 0;
-    u32* d_wide_before = nullptr;
+    host::CompactLayout compact;
+    int device = 0;
+    DeviceArray<OpDesc> d_ops;        // every op expanded on its own
+    DeviceArray<OpDesc> d_ops_runs;   // with the run marks (F_NO_AFFINE) of CP_RUN_ITERS and of the fixed-base windows
+    DeviceArray<Aff> d_cpts, d_fbtab;
+    PassTables tab;
+    DeviceArray<U256> d_constv;   // constants by source id: points at 2c / 2c + 1, scalar constants from AUX_GCONST_BASE
 };
 constexpr int CP_PIECE_OPS = 32;
 constexpr int CP_PIECE_OPS_QUAD = 45;   // four-lane plan: 9 windows of the windowed loop per piece
@@ -168,73 +161,34 @@ extern "C" int p2e_curve_program_create(p2e_ctx* c, int kind, int curve, const u
             return P2E_E_INVALID;
         }
     }
-    p2e_curve_program* P = new p2e_curve_program();
+    DeviceGuard guard(c->device);
+    std::unique_ptr<p2e_curve_program> P(new p2e_curve_program());   // a failure below frees what was uploaded before it
     if (!host::make_curve_program(P->H, kind, curve, blind)) {
-        delete P;
         set_error("unknown curve program (kind 1..5, curve 0..1; the verifier program is P-256 only)");
         return P2E_E_INVALID;
     }
+    const host::ScheduleBuilder& sb = P->H.sb;
     // the aux pass (p2e_curve_program_aux_witness_batch) has no argument for the MSM program's q: no aux item may read it
-    if (aux_reads_q(P->H.sb)) {
-        delete P;
+    if (aux_reads_q(sb)) {
         set_error("curve program: an aux item reads q (input slot 5 / 6), which the aux pass has no argument for");
         return P2E_E_INVALID;
     }
-    {   // compact container layout (as build_compact_map of the built-in programs), and the host-only check of what the
+    {   // compact container layout (as host_program of the built-in programs), and the host-only check of what the
         // compact-source ux pass walks: before anything is allocated on the device
-        host::CompactLayout L = host::compact_layout(P->H.sb.gens, (size_t)P->H.sb.prog.num_cols);
-        P->compact_map = std::move(L.map);
-        P->wide_before = std::move(L.wide_before);
-        P->num_narrow = L.num_narrow;
-        P->num_wide = L.num_wide;
+        P->compact = host::compact_layout(sb.gens, (size_t)sb.prog.num_cols);
         std::string why;
-        if (!host::ux_items_compact_ok(P->H.sb.ux_items, P->compact_map, why)) {
-            delete P;
+        if (!host::ux_items_compact_ok(sb.ux_items, P->compact.map, why)) {
             set_error(why);
             return P2E_E_INVALID;
         }
     }
-    DeviceGuard guard(c->device);
     P->device = c->device;
-    struct Cleanup {
-        p2e_ctx* c;
-        p2e_curve_program* p;
-        ~Cleanup() {
-            if (p) p2e_curve_program_destroy(c, p);
-        }
-    } cleanup{c, P};
-    host::ScheduleBuilder& sb = P->H.sb;
-    HIP_TRY(hipMalloc(&P->d_ops, sizeof(OpDesc) * sb.ops.size()));
-    HIP_TRY(hipMemcpy(P->d_ops, sb.ops.data(), sizeof(OpDesc) * sb.ops.size(), hipMemcpyHostToDevice));
-    if (sb.prog.msm_loop_iters > 0 || kind == CP_FIXED_BASE_MUL) {
-        sb.mark_runs(cp_run_iters(sb.prog));
-        HIP_TRY(hipMalloc(&P->d_ops_runs, sizeof(OpDesc) * sb.ops.size()));
-        HIP_TRY(hipMemcpy(P->d_ops_runs, sb.ops.data(), sizeof(OpDesc) * sb.ops.size(), hipMemcpyHostToDevice));
-        sb.mark_runs(0);
-    }
-    HIP_TRY(hipMalloc(&P->d_cpts, sizeof(Aff) * sb.gpts.size()));
-    HIP_TRY(hipMemcpy(P->d_cpts, sb.gpts.data(), sizeof(Aff) * sb.gpts.size(), hipMemcpyHostToDevice));
-    if (!sb.gfbtab.empty()) {
-        HIP_TRY(hipMalloc(&P->d_fbtab, sizeof(Aff) * sb.gfbtab.size()));
-        HIP_TRY(hipMemcpy(P->d_fbtab, sb.gfbtab.data(), sizeof(Aff) * sb.gfbtab.size(), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&P->d_aux_items, sizeof(AuxItem) * sb.aux_items.size()));
-    HIP_TRY(hipMemcpy(P->d_aux_items, sb.aux_items.data(), sizeof(AuxItem) * sb.aux_items.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&P->d_aux_tab, sizeof(AuxTables)));
-    HIP_TRY(hipMemcpy(P->d_aux_tab, &sb.aux_tab, sizeof(AuxTables), hipMemcpyHostToDevice));
-    if (!sb.gate_items.empty()) {
-        HIP_TRY(hipMalloc(&P->d_gate_items, sizeof(GateItem) * sb.gate_items.size()));
-        HIP_TRY(hipMemcpy(P->d_gate_items, sb.gate_items.data(), sizeof(GateItem) * sb.gate_items.size(), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&P->d_ux_items, sizeof(UxItem) * sb.ux_items.size()));
-    HIP_TRY(hipMemcpy(P->d_ux_items, sb.ux_items.data(), sizeof(UxItem) * sb.ux_items.size(), hipMemcpyHostToDevice));
-    {
-        const std::vector<UxItem> cux = host::ux_items_compact(sb.ux_items, P->compact_map);
-        HIP_TRY(hipMalloc(&P->d_ux_items_compact, sizeof(UxItem) * cux.size()));
-        HIP_TRY(hipMemcpy(P->d_ux_items_compact, cux.data(), sizeof(UxItem) * cux.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&P->d_wide_before, sizeof(u32) * P->wide_before.size()));
-        HIP_TRY(hipMemcpy(P->d_wide_before, P->wide_before.data(), sizeof(u32) * P->wide_before.size(), hipMemcpyHostToDevice));
-    }
+    HIP_TRY(P->d_ops.upload(sb.ops));
+    if (sb.prog.msm_loop_iters > 0 || kind == CP_FIXED_BASE_MUL)
+        HIP_TRY(P->d_ops_runs.upload(sb.ops_with_runs(cp_run_iters(sb.prog))));
+    HIP_TRY(P->d_cpts.upload(sb.gpts));
+    HIP_TRY(P->d_fbtab.upload(sb.gfbtab));
+    HIP_TRY(P->tab.upload(sb, P->compact, false));
     {
         std::vector<U256> cv(AUX_GCONST_BASE + sb.gvals.size(), u256_zero());
         for (size_t k = 0; k < sb.gpts.size(); k++) {
@@ -242,28 +196,15 @@ extern "C" int p2e_curve_program_create(p2e_ctx* c, int kind, int curve, const u
             cv[2 * k + 1] = sb.gpts[k].y;
         }
         for (size_t j = 0; j < sb.gvals.size(); j++) cv[AUX_GCONST_BASE + j] = sb.gvals[j];
-        HIP_TRY(hipMalloc(&P->d_constv, sizeof(U256) * cv.size()));
-        HIP_TRY(hipMemcpy(P->d_constv, cv.data(), sizeof(U256) * cv.size(), hipMemcpyHostToDevice));
+        HIP_TRY(P->d_constv.upload(cv));
     }
-    cleanup.p = nullptr;
-    *out = P;
+    *out = P.release();
     return 0;
 }
 extern "C" void p2e_curve_program_destroy(p2e_ctx* c, p2e_curve_program* P) {
     if (!P) return;
     DeviceGuard guard(P->device);
     if (c && c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(P->d_ops);
-    (void)hipFree(P->d_ops_runs);
-    (void)hipFree(P->d_cpts);
-    (void)hipFree(P->d_fbtab);
-    (void)hipFree(P->d_aux_items);
-    (void)hipFree(P->d_aux_tab);
-    (void)hipFree(P->d_gate_items);
-    (void)hipFree(P->d_ux_items);
-    (void)hipFree(P->d_ux_items_compact);
-    (void)hipFree(P->d_constv);
-    (void)hipFree(P->d_wide_before);
     delete P;
 }
 extern "C" long p2e_curve_program_num_cols(const p2e_curve_program* P) { return P ? P->H.sb.prog.num_cols : P2E_E_INVALID; }
@@ -351,8 +292,8 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
     qx = S.in(qx, n * 32);
     qy = S.in(qy, n * 32);
     if (compact) {
-        narrow = S.out(narrow, (size_t)P->num_narrow * ldn * 4);
-        wide = S.out(wide, (size_t)P->num_wide * ldw * 8);
+        narrow = S.out(narrow, (size_t)P->compact.num_narrow * ldn * 4);
+        wide = S.out(wide, (size_t)P->compact.num_wide * ldw * 8);
     } else if (!verify_only) {
         cols = S.out(cols, (size_t)G.num_cols * ld * 8);
     }
@@ -362,7 +303,6 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
     ScratchLayout L = scratch_layout(G, n);
     int rc = ensure_scratch(c, L.total);
     if (rc) return S.done(rc);
-    char* base = (char*)c->scratch;
     Buffers B{};
     B.msg = msg;
     B.r = r;
@@ -371,25 +311,12 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
     B.pky = pky;
     B.qx = qx;
     B.qy = qy;
-    B.sink = Sink{cols, ld, narrow, ldn, wide, ldw, P->d_wide_before};
+    B.sink = Sink{cols, ld, narrow, ldn, wide, ldw, P->tab.wide_before.get()};
     B.n = n;
-    B.err = (u32*)(base + L.err32);
-    B.valid = (uint8_t*)(base + L.valid8);
-    B.PX = (U256*)(base + L.px);
-    B.PY = (U256*)(base + L.py);
-    B.PZ = (U256*)(base + L.pz);
-    B.PW = (U256*)(base + L.pw);
-    B.PREF = (U256*)(base + L.pref);
-    B.AX = (U256*)(base + L.ax);
-    B.AY = (U256*)(base + L.ay);
-    B.dig4 = (uint8_t*)(base + L.dig4);
-    B.dig2 = (uint8_t*)(base + L.dig2);
-    B.msrc = (uint16_t*)(base + L.msrc);
-    B.dyn = (uint16_t*)(base + L.dyn);
-    B.src = (uint16_t*)(base + L.src);
-    B.cpts = P->d_cpts;
-    B.fbtab = P->d_fbtab;
-    B.ops = P->d_ops;
+    L.bind(B, (char*)c->scratch);
+    B.cpts = P->d_cpts.get();
+    B.fbtab = P->d_fbtab.get();
+    B.ops = P->d_ops.get();
     ZERO_COUNTER(c);
     c->seg_blocks.clear();
     const unsigned gx = (unsigned)((n + BS - 1) / BS);
@@ -412,7 +339,7 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
         return S.done(finish_call(c));
     }
     // paired stores need full workgroups, even column strides and matrices aligned to two elements
-    const bool wide_ok = !getenv("P2E_NARROW_STORES") &&
+    const bool wide_ok = !narrow_stores_forced() &&
                          (compact ? (ldn % 2 == 0 && ldw % 2 == 0 && (reinterpret_cast<uintptr_t>(narrow) & 7) == 0 &&
                                      (reinterpret_cast<uintptr_t>(wide) & 15) == 0)
                                   : (ld % 2 == 0 && (reinterpret_cast<uintptr_t>(cols) & 15) == 0));
@@ -459,8 +386,8 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
     // them, every inversion batch is cut into 2^binv_split_log2 sub-ranges, and the expansion kernels ask for dynamic LDS
     // they do not use so that one workgroup per CU leaves the register file to the chain waves (as the built-in programs'
     // four-lane plan, DESIGN.md section 5a)
-    const bool runs = P->d_ops_runs && n >= c->cp_runs_min_n && !getenv("P2E_CP_NO_RUNS");
-    const bool quad = !runs && n <= c->cp_quad_max_n && !getenv("P2E_CP_NO_QUAD");
+    const bool runs = P->d_ops_runs.get() && n >= c->tune.cp_runs_min_n && !getenv("P2E_CP_NO_RUNS");
+    const bool quad = !runs && n <= c->tune.cp_quad_max_n && !getenv("P2E_CP_NO_QUAD");
     // ops per piece: the expansions are nowhere near the critical path of a small batch (the chain is), so its pieces are
     // longer: fewer launches and inversion batches on the chain's way
     int piece_ops = quad ? CP_PIECE_OPS_QUAD : CP_PIECE_OPS, tail_ops_quad = CP_TAIL_OPS_QUAD;
@@ -489,14 +416,14 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
     const int stride = G.loop_dbls + 1, run_iters = cp_run_iters(G);   // ops per loop iteration, iterations per run
     if (runs && G.msm_loop_iters == 0) {
         // the fixed-base program: its windows as one run per signature, then the unblinding add (one piece)
-        B.ops = P->d_ops_runs;
+        B.ops = P->d_ops_runs.get();
         add(Piece{G.fb_begin, G.num_ops, c->st_msm, false, false, true, 0, 0, G.fb_begin + G.fb_windows, G.num_ops});
         if (overflow || G.fb_begin != 0 || np != 1) {
             set_error("curve program does not have the shape the run plan expects");
             return S.done(P2E_E_INVALID);
         }
     } else if (runs) {
-        B.ops = P->d_ops_runs;
+        B.ops = P->d_ops_runs.get();
         const int lb = G.msm_loop_begin, iters = G.msm_loop_iters, le = lb + stride * iters;
         int fb_end = 0;
         if (G.fb_begin >= 0) {   // verifier: fixed-base windows + unblinding add, one piece on the second chain stream
@@ -588,7 +515,7 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
         // verifier's first windowed pieces would queue behind that 67-op chain)
         // (op-by-op plan: the inversion batches of consecutive pieces alternate between two streams, as in the mid-size plan
         // of the built-in programs -- they are latency-bound and would otherwise queue behind each other)
-        const bool alt = !runs && n < c->binv_alt_max_n && !getenv("P2E_CP_NO_ALT_B");
+        const bool alt = !runs && n < c->tune.binv_alt_max_n && !getenv("P2E_CP_NO_ALT_B");
         // (fixed-base chain beside the windowed one: st_fixed carries chain pieces, so the inversion batches alternate
         // between the inversion stream and the otherwise idle second expansion stream)
         // (four-lane plan: the table's batch goes to the second expansion stream, which has nothing queued yet -- the first
@@ -599,9 +526,9 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
                            : !runs ? ((alt && (k & 1)) ? c->st_binv : c->st_fixed)
                            : pc.chain == c->st_fixed ? c->st_fixed : c->st_binv;
         if (st_b != pc.chain) HIP_TRY(hipStreamWaitEvent(st_b, c->ev_piece[k], 0));
-        if (quad && c->binv_split_log2 > 0)
-            hipLaunchKernelGGL((kc_batch_inv_split<CV>), dim3((unsigned)(((n << c->binv_split_log2) + BS - 1) / BS)), dim3(BS), 0, st_b, G, B,
-                               pc.lo, pc.hi, c->binv_split_log2);
+        if (quad && c->tune.binv_split_log2 > 0)
+            hipLaunchKernelGGL((kc_batch_inv_split<CV>), dim3((unsigned)(((n << c->tune.binv_split_log2) + BS - 1) / BS)), dim3(BS), 0, st_b, G, B,
+                               pc.lo, pc.hi, c->tune.binv_split_log2);
         else
             hipLaunchKernelGGL((kc_batch_inv<CV>), dim3(gx), dim3(BS), 0, st_b, G, B, pc.lo, pc.hi);
         HIP_TRY(hipEventRecord(c->ev_binv[k], st_b));
@@ -613,7 +540,7 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
     // the expansions run on the library's own first expansion stream when the stream layout has one (p2e_ctx_create)
     hipStream_t st_x = c->st_c1 ? c->st_c1 : c->stream;
     if (c->st_c1) HIP_TRY(hipStreamWaitEvent(c->st_c1, c->ev_fork, 0));
-    emit_lds = quad ? c->expand_lds_small : 0;
+    emit_lds = quad ? c->tune.expand_lds_small : 0;
     // phase C by readiness: the table first, the fixed-base run after the first loop piece (its chain is 67 ops long)
     int order[p2e_ctx::MAX_SEG];
     int no = 0;
@@ -817,10 +744,10 @@ extern "C" long p2e_p256_verify_witness_compact_batch(p2e_ctx* c, const p2e_curv
 extern "C" long p2e_curve_program_compact_layout(const p2e_curve_program* P, uint32_t* col_map, size_t cap, uint32_t* num_narrow,
                                                  uint32_t* num_wide) {
     if (!P) return P2E_E_INVALID;
-    for (size_t k = 0; col_map && k < P->compact_map.size() && k < cap; k++) col_map[k] = P->compact_map[k];
-    if (num_narrow) *num_narrow = P->num_narrow;
-    if (num_wide) *num_wide = P->num_wide;
-    return (long)P->compact_map.size();
+    for (size_t k = 0; col_map && k < P->compact.map.size() && k < cap; k++) col_map[k] = P->compact.map[k];
+    if (num_narrow) *num_narrow = P->compact.num_narrow;
+    if (num_wide) *num_wide = P->compact.num_wide;
+    return (long)P->compact.map.size();
 }
 // ---- the other targets of a curve program's circuit (SURVEY.md 8(f) ranks 1 and 2 for the rank-4 gadgets) ---------------
 // Inputs as for the program's fill (multiplication programs: the scalar in msg32; r32 / s32 may be NULL there; the MSM
@@ -847,7 +774,7 @@ static long run_curve_aux(p2e_ctx* c, const p2e_curve_program* P, const uint8_t*
     if (pkx32) pkx32 = S.in(pkx32, 32 * n);
     if (pky32) pky32 = S.in(pky32, 32 * n);
     if (compact)
-        narrow = S.in(narrow, (size_t)P->num_narrow * ldn * 4);
+        narrow = S.in(narrow, (size_t)P->compact.num_narrow * ldn * 4);
     else
         cols = S.in(cols, (size_t)sb.prog.num_cols * ld * 8);
     aux = S.out((char*)aux, (size_t)sb.aux_tab.num_aux_cols * ld_aux * (compact ? 4 : 8));
@@ -857,8 +784,8 @@ static long run_curve_aux(p2e_ctx* c, const p2e_curve_program* P, const uint8_t*
     ZERO_COUNTER(c);
     u32* err32 = (u32*)c->scratch;
     HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
-    AuxArgs A{cols, ld, aux, ld_aux, n, pky32, P->d_cpts, P->d_fbtab, P->d_aux_items, P->d_aux_tab, err32, narrow, ldn,
-              compact ? P->d_wide_before : nullptr, {}};
+    AuxArgs A{cols, ld, aux, ld_aux, n, pky32, P->d_cpts.get(), P->d_fbtab.get(), P->tab.aux_items.get(), P->tab.aux_tab.get(),
+              err32, narrow, ldn, compact ? P->tab.wide_before.get() : nullptr, {}};
     A.in[INPUT_PY] = pky32;
     A.in[INPUT_PX] = pkx32;
     A.in[INPUT_MSG] = msg32;
@@ -866,7 +793,7 @@ static long run_curve_aux(p2e_ctx* c, const p2e_curve_program* P, const uint8_t*
     A.in[INPUT_S] = s32 ? s32 : msg32;
     // (A.in[INPUT_QX / INPUT_QY] stay null: p2e_curve_program_create refuses a program whose aux items would read q)
     const unsigned gx = (unsigned)((n + BS - 1) / BS), items = (unsigned)sb.aux_items.size();
-    const bool wide_ok = (ld_aux % 2 == 0) && ((reinterpret_cast<uintptr_t>(aux) & (compact ? 7 : 15)) == 0) && !getenv("P2E_NARROW_STORES");
+    const bool wide_ok = (ld_aux % 2 == 0) && ((reinterpret_cast<uintptr_t>(aux) & (compact ? 7 : 15)) == 0) && !narrow_stores_forced();
     const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
     const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
     if (compact) {
@@ -916,7 +843,7 @@ extern "C" long p2e_curve_program_gate_internal_batch(p2e_ctx* c, const p2e_curv
     if (!curve_gate_args_ok(c, P, aux, ld_aux, gate, ld_gate, n)) return P2E_E_INVALID;
     if (n == 0) return 0;
     const host::ScheduleBuilder& sb = P->H.sb;
-    return run_gate(c, aux, false, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, P->d_gate_items,
+    return run_gate(c, aux, false, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, P->tab.gate_items.get(),
                     (unsigned)sb.gate_items.size());
 }
 extern "C" long p2e_curve_program_gate_internal_compact_batch(p2e_ctx* c, const p2e_curve_program* P, const uint32_t* aux32, size_t ld_aux,
@@ -924,7 +851,7 @@ extern "C" long p2e_curve_program_gate_internal_compact_batch(p2e_ctx* c, const 
     if (!curve_gate_args_ok(c, P, aux32, ld_aux, gate, ld_gate, n)) return P2E_E_INVALID;
     if (n == 0) return 0;
     const host::ScheduleBuilder& sb = P->H.sb;
-    return run_gate(c, aux32, true, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, P->d_gate_items,
+    return run_gate(c, aux32, true, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, P->tab.gate_items.get(),
                     (unsigned)sb.gate_items.size());
 }
 // constraint-block (U29 gate) values from the finished witness and aux matrices: ux[num_ux_cols][ld_ux], u32 or u64
@@ -948,12 +875,12 @@ static UxCall curve_ux_call(const p2e_curve_program* P, const uint8_t* msg32, co
     U.n = n;
     U.err = err;
     U.num_cols = (u32)sb.prog.num_cols;
-    U.num_narrow = P->num_narrow;
+    U.num_narrow = P->compact.num_narrow;
     U.num_aux_cols = sb.aux_tab.num_aux_cols;
     U.num_ux_cols = sb.num_ux_cols;
-    U.d_consts = P->d_constv;
-    U.d_items = P->d_ux_items;
-    U.d_items_compact = P->d_ux_items_compact;
+    U.d_consts = P->d_constv.get();
+    U.d_items = P->tab.ux_items.get();
+    U.d_items_compact = P->tab.ux_items_compact.get();
     U.items = (unsigned)sb.ux_items.size();
     return U;
 }
@@ -1023,7 +950,7 @@ extern "C" int p2e_curve_program_wire_map_create(p2e_ctx* c, const p2e_curve_pro
     if (!P) return P2E_E_INVALID;
     const host::ScheduleBuilder& sb = P->H.sb;
     const u32 limit[4] = {(u32)sb.prog.num_cols, sb.aux_tab.num_aux_cols, sb.num_ux_cols, sb.num_gate_cols};
-    return make_wire_map(c, limit, P->compact_map, P->num_narrow, P->num_wide, entries, count, num_wires, degree, out);
+    return make_wire_map(c, limit, P->compact, entries, count, num_wires, degree, out);
 }
 // synthetic valid signatures on a curve (host side; tests and benches)
 extern "C" int p2e_synth_signatures_curve(int curve, uint64_t seed, size_t first, size_t n, uint8_t* msg32, uint8_t* r32, uint8_t* s32,

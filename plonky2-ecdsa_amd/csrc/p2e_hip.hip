@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -13,6 +14,8 @@
 #include "../../include/p2e.h"
 #include "aux.hpp"
 #include "consts.hpp"
+#include "device_array.hpp"
+#include "knobs.hpp"
 #include "pipeline.hpp"
 #include "prims.hpp"
 #include "quad.hpp"
@@ -488,14 +491,16 @@ thread_local std::string g_last_error;
 extern thread_local std::string g_last_error;
 #endif
 static void set_error(const std::string& s) { g_last_error = s; }
-#define HIP_TRY(expr)                                                                        \
+// what: the text that names the failing call (HIP_TRY: the expression itself)
+#define HIP_TRY_AS(what, expr)                                                               \
     do {                                                                                     \
         hipError_t _e = (expr);                                                              \
         if (_e != hipSuccess) {                                                              \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
+            set_error(std::string(what) + ": " + hipGetErrorString(_e));                     \
             return P2E_E_HIP;                                                                \
         }                                                                                    \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
 
 // Entry points run on the context's device and leave the caller's current device as they found it (a multi-GPU
 // process, or torch, keeps its own notion of "current device").
@@ -513,35 +518,40 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// What a program IS (host side, immutable, shared by every context): the built schedule and its compact-container layout
+struct HostProgram {
+    host::ScheduleBuilder sb;
+    host::CompactLayout compact;
+};
+// device tables of the passes behind a fill, the same set for a built-in program and a curve program
+struct PassTables {
+    DeviceArray<AuxItem> aux_items;   // built-in-generator columns (aux.hpp)
+    DeviceArray<AuxTables> aux_tab;
+    DeviceArray<GateItem> gate_items;
+    DeviceArray<UxItem> ux_items;           // constraint-block columns (ux.hpp)
+    DeviceArray<UxItem> ux_items_compact;   // the same table in compact coordinates (host::ux_items_compact)
+    DeviceArray<u32> wide_before;   // [num_cols + 1]: wide columns before column c (Sink::wide_before)
+    DeviceArray<u32> compact_map;   // per-column slot (p2e_columns_compact: built-in programs only)
+    hipError_t upload(const host::ScheduleBuilder& sb, const host::CompactLayout& L, bool with_compact_map) {
+        hipError_t e = aux_items.upload(sb.aux_items);
+        if (e == hipSuccess) e = aux_tab.upload(&sb.aux_tab, 1);
+        if (e == hipSuccess) e = gate_items.upload(sb.gate_items);
+        if (e == hipSuccess) e = ux_items.upload(sb.ux_items);
+        if (e == hipSuccess) e = ux_items_compact.upload(host::ux_items_compact(sb.ux_items, L.map));
+        if (e == hipSuccess) e = wide_before.upload(L.wide_before);
+        if (e == hipSuccess && with_compact_map) e = compact_map.upload(L.map);
+        return e;
+    }
+};
+// A built-in program inside one context: everything about the program itself is read through `host`
 struct DeviceProgram {
-    Program prog;
-    OpDesc* d_ops = nullptr;        // with the run marks of ctx->run_iters (F_NO_AFFINE)
-    OpDesc* d_ops_plain = nullptr;  // without: every op expanded on its own (small batches)
-    OpDesc* d_ops_mid = nullptr;    // with the run marks of ctx->run_iters_mid (mid-size batches)
-    OpDesc* d_ops_small = nullptr;  // with the run marks of ctx->run_iters_small (four-lane plan)
-    std::vector<OpDesc> h_ops;
-    std::vector<host::GenOp> gens;
-    // built-in-generator columns (aux.hpp)
-    std::vector<AuxItem> aux_items;
-    std::vector<host::AuxGen> aux_gens;
-    AuxTables aux_tab{};
-    AuxItem* d_aux_items = nullptr;
-    AuxTables* d_aux_tab = nullptr;
-    // constraint-block columns (ux.hpp)
-    std::vector<UxItem> ux_items;
-    std::vector<u32> ux_first, ux_count;
-    u32 num_ux_cols = 0;
-    UxItem* d_ux_items = nullptr;
-    UxItem* d_ux_items_compact = nullptr;   // the same table in compact coordinates (host::ux_items_compact)
-    std::vector<GateItem> gate_items;
-    u32 num_gate_cols = 0;
-    GateItem* d_gate_items = nullptr;
-    // compact container (p2e_columns_compact): per-column slot, narrow / wide column counts
-    std::vector<u32> compact_map;
-    u32 num_narrow = 0, num_wide = 0;
-    u32* d_compact_map = nullptr;
-    std::vector<u32> wide_before;   // [num_cols + 1]: wide columns before column c (Sink::wide_before)
-    u32* d_wide_before = nullptr;
+    const HostProgram* host = nullptr;
+    PassTables tab;
+    DeviceArray<OpDesc> d_ops;        // with the run marks of tune.run_iters (F_NO_AFFINE)
+    DeviceArray<OpDesc> d_ops_plain;  // without: every op expanded on its own (small batches)
+    DeviceArray<OpDesc> d_ops_mid;    // with the run marks of tune.run_iters_mid (mid-size batches)
+    DeviceArray<OpDesc> d_ops_small;  // with the run marks of tune.run_iters_small (four-lane plan)
+    std::vector<OpDesc> h_ops;        // host copy of d_ops
 };
 
 struct p2e_ctx {
@@ -553,7 +563,7 @@ struct p2e_ctx {
     // ALU and all of the HBM bandwidth idle; the witness expansion is HBM-bound.  So the chains run on
     // their own high-priority streams, cut into pieces, and phases B/C of every finished piece run on the
     // caller's stream underneath the following pieces.
-    static constexpr int MAX_PIECES = 16;
+    static constexpr int MAX_PIECES = Tuning::MAX_PIECES;
     static constexpr int MAX_SEG = 2 * MAX_PIECES + 2;
     // st_binv, st_c2: second phase-B and second phase-C stream of the small-batch plan
     hipStream_t st_msm = nullptr, st_fixed = nullptr, st_binv = nullptr, st_c2 = nullptr;
@@ -579,69 +589,10 @@ struct p2e_ctx {
         int ev;
     };
     std::vector<SegBlock> seg_blocks;
-    int msm_pieces = 8, fixed_pieces = 2;   // one Montgomery inversion batch per piece
-    int msm_pieces_small = 5, fixed_pieces_small = 1;   // ... of the small-batch plan (fewer launches and inversions)
-    int run_iters = 9;                      // MSM-loop iterations per expansion run (0: expand op by op)
-    // with runs: the fixed-base windows as one run per signature (k_expand_fb_run).  OFF by default in the built-in
-    // verifier: measured 11.43 / 11.05 ms against 10.86 / 11.28 ms per 2^16 batch (alternating processes on one box) --
-    // the single run has one wave per SIMD and lands in the window where the chains and inversions contend with it
-    // (0.40-0.42 of peak against 0.43-0.47 for the same columns through k_expand); P2E_FB_RUN=1 turns it on.  The
-    // P-256 verifier program uses it (curve_api.inc), where it sits beside a longer windowed chain.
-    bool fb_run = false;
-    // A run is walked by ONE lane, so a launch of r runs has only r * n/64 waves: below this batch size the
-    // 1024 SIMDs are better filled by one workgroup row per op (2^10 glv_mul fills: 3.0 ms against 9.5 ms)
-    size_t runs_min_n = 21505;              // (= every batch the four-lane plan does not take, see quad_max_n)
-    size_t cp_runs_min_n = 49152;           // the same threshold for the curve programs (curve_api.inc), measured there only at 2^13 / 2^16
-    // Below this batch size phases A and B are latency, not throughput: four lanes per signature walk the chains
-    // (k_chains_quad) and every inversion batch is cut into 2^binv_split_log2 sub-ranges (k_batch_inv_split)
-    // (24 576 until phase B of the lane-per-signature plan went onto two streams below binv_alt_max_n: since then that plan
-    // wins from 2^14 up -- 3.94 against 4.60 ms at 16 384, 4.96 against 6.46 ms at 24 576, 3.81 against 3.62 ms at 12 288)
-    // (round 3, with short expansion runs and front-loaded pieces: 3.56-3.76 against 4.10-4.15 ms at 16 384, 4.73 against
-    // 4.5 ms at 20 480, profiles/r03_plan_threshold_resweep.txt -- the threshold moved up from 14 336 and now takes 2^14)
-    // (with the chains on lazy limbs and the safegcd inversion: 3.44-3.52 against 3.96-4.03 ms at 16 384, 4.05-4.28 against
-    // 4.25-4.35 at 20 480, 5.01-5.04 against 4.72-4.73 at 24 576, profiles/r03_plan_threshold_lazy_limbs.txt: 17 408 -> 21 504)
-    size_t quad_max_n = 21504;
-    size_t cp_quad_max_n = 17408;   // the curve programs' own threshold (P-256 keeps canonical words: measured with those)
-    // Between the two plans (lane per signature, but fewer than one chain wave per SIMD) phase B is the serial resource:
-    // its kernels are latency-bound (half a wave per SIMD at 2^15) and queue on one stream from the first piece to the
-    // last, with every expansion waiting behind them.  Below this batch size the inversion batches of consecutive pieces
-    // alternate between two streams -- and are cut into 2^binv_mid_split_log2 sub-ranges each -- so that they overlap.
-    size_t binv_alt_max_n = 49152;
-    // ... and the loop is cut into fewer pieces of longer runs there (5 pieces of 12-iteration runs instead of 8 of 9:
-    // 5.96 against 6.45 ms at 2^15, 7.65 against 7.95 ms at 40 960, 9.15 against 9.53 ms at 48 896)
-    int msm_pieces_mid = 5, run_iters_mid = 12;
-    // four-lane plan: the loop expanded as SHORT runs (4 iterations = 12 ops, two of them keep their affine form): phase B
-    // then does 3 instead of 8 multiplications for the other ten, and a piece of 5 runs still launches 5 * n/64 waves.
-    // 2.35 / 2.27 against 2.42 ms at 2^13, 2.88 / 2.96 against 3.05 ms at 12 288 (profiles/r03_quad_plan_run_expansion_sweep.txt;
-    // R = 2, 3, 6 and 7 pieces are slower).  0: every op expanded on its own, as in round 2.
-    int run_iters_small = 4;
-    int binv_mid_split_log2 = 1;   // 2^15 per call: 7.03-7.08 ms on one stream, 6.76-6.83 alternating, 6.68-6.72 alternating and split in two
-    int binv_split_log2 = 2;
-    // small-batch plan: dynamic LDS bytes requested by the expansion kernels (they do not use it): caps how many of
-    // their workgroups share a CU, so that the register file keeps room for the chain waves queued behind them
-    // small-batch plan: runs per loop piece (front-loaded: the LAST piece's inversion batch and expansion are the
-    // exposed tail of the call, so it is the shortest), 0-terminated; empty = equal pieces.  And the split of the last
-    // piece's inversion batch (latency matters there; the earlier ones only need throughput: fewer inversions).
-    int small_takes[p2e_ctx::MAX_PIECES + 1] = {0};
-    int binv_split_log2_last = 3;
-    // the fixed-base chain's batch: 67 ops that all keep their affine form, the longest walk, and its expansion is the largest
-    // single launch of the call -- eight sub-ranges: 1.89 against 1.95 ms at 2^13, level at 2^14 (profiles/r03_fixed_base_batch_split.txt)
-    int binv_split_log2_fixed = 3;
-    // small-batch plan: which of the two phase-B streams takes the FIRST batch after the window table's (the fixed-base
-    // chain's).  1: the fixed-base chain's own stream -- the table's batch occupies the other one until ~0.7 ms, and the
-    // fixed-base batch (67 ops that all keep their affine form: the longest) queued behind it used to hold up the second
-    // loop piece's batch in turn.  0: the round-2 order.
-    int quad_b_first_on_fixed = 1;
-    bool quad_few_waits = true;   // P2E_QUAD_FEW_WAITS=0: one wait per earlier piece, as before
-    unsigned expand_lds_small = 54000;   // (160 000 -- one expansion workgroup per CU -- while the chains were the bottleneck; with lazy-limb chains 54 000 is 3-4 % faster at 2^13, profiles/r03_quad_plan_lazy_limbs_sweeps.txt)
-    unsigned expand_lds = 0;   // the same knob for the large-batch plan
-    Aff* d_cpts = nullptr;
-    Aff* d_fbtab = nullptr;
-    Aff* d_fbtab_p256 = nullptr;   // P-256 generator table of the key-derivation / signing calls: built and uploaded on first use
-    // p2e_ecdsa_public_key_batch / p2e_ecdsa_sign_batch with P2E_SIGN_PLAN_AUTO: four lanes per scalar up to this batch
-    // size, one lane per scalar above it (MEASUREMENTS.md, "Batch key derivation and signing")
-    size_t sign_quad_max_n = 65536;
-    U256* d_constv = nullptr;   // circuit constants by id (AUX_SRC_CONST | id), for the constraint-block pass
+    Tuning tune;   // knobs.hpp: filled from the environment once, when the context is created
+    DeviceArray<Aff> d_cpts, d_fbtab;
+    DeviceArray<Aff> d_fbtab_p256;   // P-256 generator table of the key-derivation / signing calls: built and uploaded on first use
+    DeviceArray<U256> d_constv;   // circuit constants by id (AUX_SRC_CONST | id), for the constraint-block pass
     DeviceProgram progs[2];
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -654,61 +605,38 @@ struct p2e_ctx {
 };
 
 #if P2E_HAS(0)
-static void build_compact_map(DeviceProgram& P) {
-    host::CompactLayout L = host::compact_layout(P.gens, (size_t)P.prog.num_cols);
-    P.compact_map = std::move(L.map);
-    P.wide_before = std::move(L.wide_before);
-    P.num_narrow = L.num_narrow;
-    P.num_wide = L.num_wide;
-}
-static const DeviceProgram& host_program(int program) {
-    static DeviceProgram P[2];
+static_assert(Tuning::MAX_RUN_ITERS == MSM_DIGITS, "knobs.hpp: the bound of the P2E_RUN_ITERS* knobs");
+static const HostProgram& host_program(int program) {
+    static HostProgram P[2];
     static std::once_flag once;
     std::call_once(once, [] {
-        host::ScheduleBuilder b0;
-        b0.verify_secp256k1_message_circuit();
-        P[0].prog = b0.prog;
-        P[0].gens = b0.gens;
-        P[0].aux_items = b0.aux_items;
-        P[0].aux_gens = b0.aux_gens;
-        P[0].aux_tab = b0.aux_tab;
-        P[0].ux_items = b0.ux_items;
-        P[0].ux_first = b0.ux_first;
-        P[0].ux_count = b0.ux_count;
-        P[0].num_ux_cols = b0.num_ux_cols;
-        P[0].gate_items = b0.gate_items;
-        P[0].num_gate_cols = b0.num_gate_cols;
-        build_compact_map(P[0]);
-        host::ScheduleBuilder b1;
-        b1.glv_mul_circuit();
-        P[1].prog = b1.prog;
-        P[1].gens = b1.gens;
-        P[1].aux_items = b1.aux_items;
-        P[1].aux_gens = b1.aux_gens;
-        P[1].aux_tab = b1.aux_tab;
-        P[1].ux_items = b1.ux_items;
-        P[1].ux_first = b1.ux_first;
-        P[1].ux_count = b1.ux_count;
-        P[1].num_ux_cols = b1.num_ux_cols;
-        P[1].gate_items = b1.gate_items;
-        P[1].num_gate_cols = b1.num_gate_cols;
-        build_compact_map(P[1]);
+        P[0].sb.verify_secp256k1_message_circuit();
+        P[1].sb.glv_mul_circuit();
+        for (HostProgram& p : P) p.compact = host::compact_layout(p.sb.gens, (size_t)p.sb.prog.num_cols);
     });
     return P[program];
-}
-static std::vector<OpDesc> host_ops(int program, int run_iters, bool fb_run = true) {
-    host::ScheduleBuilder b;
-    if (program == 0)
-        b.verify_secp256k1_message_circuit();
-    else
-        b.glv_mul_circuit();
-    b.mark_runs(run_iters, fb_run);
-    return b.ops;
 }
 #endif   // P2E_HAS(0)
 
 struct ScratchLayout {
     size_t px, py, pz, pw, pref, ax, ay, dig4, dig2, msrc, dyn, src, err32, valid8, total;
+    // the scratch pointers of B inside the block at `base`
+    void bind(Buffers& B, char* base) const {
+        B.err = (u32*)(base + err32);
+        B.valid = (uint8_t*)(base + valid8);
+        B.PX = (U256*)(base + px);
+        B.PY = (U256*)(base + py);
+        B.PZ = (U256*)(base + pz);
+        B.PW = (U256*)(base + pw);
+        B.PREF = (U256*)(base + pref);
+        B.AX = (U256*)(base + ax);
+        B.AY = (U256*)(base + ay);
+        B.dig4 = (uint8_t*)(base + dig4);
+        B.dig2 = (uint8_t*)(base + dig2);
+        B.msrc = (uint16_t*)(base + msrc);
+        B.dyn = (uint16_t*)(base + dyn);
+        B.src = (uint16_t*)(base + src);
+    }
 };
 static ScratchLayout scratch_layout(const Program& G, size_t n) {
     ScratchLayout L{};
@@ -737,12 +665,39 @@ static ScratchLayout scratch_layout(const Program& G, size_t n) {
     return L;
 }
 
+// Every internal stream of a context: its letter in the layout string (0: not made from the layout) and its priority
+// class (+1 high, 0 normal, -1 low).  Creation, p2e_ctx_destroy and Staged::release all walk this one list.
+template <class F>
+static void each_internal_stream(p2e_ctx* c, F&& f) {
+    f(c->st_msm, 'M', 1);
+    f(c->st_fixed, 'F', 1);
+    f(c->st_binv, 'B', 1);
+    f(c->st_c2, '2', -1);
+    f(c->st_c1, '1', 0);
+    f(c->st_c1q, '\0', 0);
+    f(c->st_c2q, '\0', 0);
+    for (hipStream_t& st : c->st_pad) f(st, 'P', 0);
+}
+
 #if P2E_HAS(0)
 extern "C" const char* p2e_last_error(void) { return g_last_error.c_str(); }
 
 extern "C" size_t p2e_scratch_bytes(int program, size_t n) {
     if (program < 0 || program > 1) return 0;
-    return scratch_layout(host_program(program).prog, n).total;
+    return scratch_layout(host_program(program).sb.prog, n).total;
+}
+
+// every event of a context with its creation flags (timed: only a P2E_CTX_PHASE_TIMING context pays for timestamps)
+template <class F>
+static void each_event(p2e_ctx* c, F&& f) {
+    const unsigned timed = (c->flags & P2E_CTX_PHASE_TIMING) ? hipEventDefault : hipEventDisableTiming;
+    // ev[1] closes the scalar phase's column block (p2e_segments_*): it exists either way, with a timestamp only on request
+    for (auto& e : c->ev) f(e, timed);
+    for (hipEvent_t* e : {&c->ev_c1join, &c->ev_c2, &c->ev_fork, &c->ev_fixed}) f(*e, hipEventDisableTiming);
+    for (auto& e : c->ev_binv) f(e, hipEventDisableTiming);
+    for (auto& e : c->ev_piece) f(e, hipEventDisableTiming);
+    for (auto& e : c->ev_c0) f(e, hipEventDefault);
+    for (auto& e : c->ev_c1) f(e, timed);
 }
 
 extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx** out) {
@@ -750,7 +705,7 @@ extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx*
     // host-only check of the compact layout the compact-source ux pass walks, before anything is allocated
     for (int p = 0; p < 2; p++) {
         std::string why;
-        if (!host::ux_items_compact_ok(host_program(p).ux_items, host_program(p).compact_map, why)) {
+        if (!host::ux_items_compact_ok(host_program(p).sb.ux_items, host_program(p).compact.map, why)) {
             set_error(why);
             return P2E_E_INVALID;
         }
@@ -765,16 +720,11 @@ extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx*
         return P2E_E_INVALID;
     }
     DeviceGuard guard(device);
-    p2e_ctx* c = new p2e_ctx();
+    // a failing HIP call below must not leak the context and what it already owns
+    std::unique_ptr<p2e_ctx, void (*)(p2e_ctx*)> holder(new p2e_ctx(), p2e_ctx_destroy);
+    p2e_ctx* c = holder.get();
     c->device = device;
     c->flags = flags;
-    // a failing HIP call below must not leak the context and what it already owns
-    struct Cleanup {
-        p2e_ctx* c;
-        ~Cleanup() {
-            if (c) p2e_ctx_destroy(c);
-        }
-    } cleanup{c};
     if (stream) {
         c->stream = (hipStream_t)stream;
     } else {
@@ -785,117 +735,34 @@ extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx*
         c->own_stream = true;
     }
     const host::Consts& C = host::consts();
-    HIP_TRY(hipMalloc(&c->d_cpts, sizeof(Aff) * NUM_CONST_PTS));
-    HIP_TRY(hipMalloc(&c->d_fbtab, sizeof(Aff) * C.fbtab.size()));
-    HIP_TRY(hipMemcpy(c->d_cpts, C.cpts, sizeof(Aff) * NUM_CONST_PTS, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_fbtab, C.fbtab.data(), sizeof(Aff) * C.fbtab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c->d_cpts.upload(C.cpts, NUM_CONST_PTS));
+    HIP_TRY(c->d_fbtab.upload(C.fbtab));
     {
         U256 cv[NUM_CONSTV];
         for (u32 id = 0; id < NUM_CONSTV; id++) cv[id] = host::ScheduleBuilder::const_value(id);
-        HIP_TRY(hipMalloc(&c->d_constv, sizeof cv));
-        HIP_TRY(hipMemcpy(c->d_constv, cv, sizeof cv, hipMemcpyHostToDevice));
+        HIP_TRY(c->d_constv.upload(cv, NUM_CONSTV));
     }
-    if (const char* env = getenv("P2E_RUN_ITERS")) {
-        int v = atoi(env);
-        if (v >= 0 && v <= MSM_DIGITS) c->run_iters = v;
-    }
-    if (const char* env = getenv("P2E_FB_RUN")) c->fb_run = atoi(env) != 0;
-    if (const char* env = getenv("P2E_RUNS_MIN_N")) c->runs_min_n = (size_t)strtoull(env, nullptr, 10);
-    if (const char* env = getenv("P2E_QUAD_MAX_N")) c->quad_max_n = c->cp_quad_max_n = (size_t)strtoull(env, nullptr, 10);
-    if (const char* env = getenv("P2E_BINV_ALT_MAX_N")) c->binv_alt_max_n = (size_t)strtoull(env, nullptr, 10);
-    if (const char* env = getenv("P2E_CP_RUNS_MIN_N")) c->cp_runs_min_n = (size_t)strtoull(env, nullptr, 10);
-    if (const char* env = getenv("P2E_MSM_PIECES_MID")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= p2e_ctx::MAX_PIECES) c->msm_pieces_mid = v;
-    }
-    if (const char* env = getenv("P2E_RUN_ITERS_SMALL")) {
-        int v = atoi(env);
-        if (v >= 0 && v <= MSM_DIGITS) c->run_iters_small = v;
-    }
-    if (const char* env = getenv("P2E_RUN_ITERS_MID")) {
-        int v = atoi(env);
-        if (v >= 0 && v <= MSM_DIGITS) c->run_iters_mid = v;
-    }
-    if (const char* env = getenv("P2E_BINV_MID_SPLIT_LOG2")) {
-        int v = atoi(env);
-        if (v >= 0 && v <= 3) c->binv_mid_split_log2 = v;
-    }
-    if (const char* env = getenv("P2E_EXPAND_LDS_SMALL")) c->expand_lds_small = (unsigned)strtoul(env, nullptr, 10);
-    if (const char* env = getenv("P2E_EXPAND_LDS")) c->expand_lds = (unsigned)strtoul(env, nullptr, 10);
+    read_tuning(c->tune, getenv);
     {   // never ask for more dynamic LDS than a workgroup may have on this device (160 KB on gfx950)
         int max_lds = 0;
         if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || max_lds <= 0) max_lds = 65536;
         (void)hipGetLastError();
-        if (c->expand_lds_small > (unsigned)max_lds) c->expand_lds_small = (unsigned)max_lds;
-        if (c->expand_lds > (unsigned)max_lds) c->expand_lds = (unsigned)max_lds;
-    }
-    if (const char* env = getenv("P2E_QUAD_B_FIRST_ON_FIXED")) c->quad_b_first_on_fixed = atoi(env) != 0;
-    if (const char* env = getenv("P2E_QUAD_FEW_WAITS")) c->quad_few_waits = atoi(env) != 0;
-    if (const char* env = getenv("P2E_BINV_SPLIT_LOG2_FIXED")) {
-        int v = atoi(env);
-        if (v >= 0 && v <= 4) c->binv_split_log2_fixed = v;
-    }
-    if (const char* env = getenv("P2E_BINV_SPLIT_LOG2_LAST")) {
-        int v = atoi(env);
-        if (v >= 0 && v <= 4) c->binv_split_log2_last = v;
-    }
-    if (const char* env = getenv("P2E_SMALL_TAKES")) {   // e.g. "24,20,16,9,4": loop iterations per piece (op-by-op expansion: any cut)
-        int k = 0;
-        for (const char* p = env; *p && k < p2e_ctx::MAX_PIECES; k++) {
-            c->small_takes[k] = atoi(p);
-            while (*p && *p != ',') p++;
-            if (*p == ',') p++;
-        }
-        c->small_takes[k] = 0;
-    }
-    if (const char* env = getenv("P2E_BINV_SPLIT_LOG2")) {
-        int v = atoi(env);
-        if (v >= 0 && v <= 4) c->binv_split_log2 = v;
+        if (c->tune.expand_lds_small > (unsigned)max_lds) c->tune.expand_lds_small = (unsigned)max_lds;
+        if (c->tune.expand_lds > (unsigned)max_lds) c->tune.expand_lds = (unsigned)max_lds;
     }
     for (int p = 0; p < 2; p++) {
-        c->progs[p].prog = host_program(p).prog;
-        std::vector<OpDesc> ops = host_ops(p, c->run_iters, c->fb_run);
-        c->progs[p].h_ops = ops;
-        HIP_TRY(hipMalloc(&c->progs[p].d_ops, sizeof(OpDesc) * ops.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_ops, ops.data(), sizeof(OpDesc) * ops.size(), hipMemcpyHostToDevice));
-        const DeviceProgram& HP = host_program(p);
-        c->progs[p].aux_tab = HP.aux_tab;
-        c->progs[p].aux_items = HP.aux_items;
-        HIP_TRY(hipMalloc(&c->progs[p].d_aux_items, sizeof(AuxItem) * HP.aux_items.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_aux_items, HP.aux_items.data(), sizeof(AuxItem) * HP.aux_items.size(), hipMemcpyHostToDevice));
-        c->progs[p].ux_items = HP.ux_items;
-        c->progs[p].num_ux_cols = HP.num_ux_cols;
-        HIP_TRY(hipMalloc(&c->progs[p].d_ux_items, sizeof(UxItem) * HP.ux_items.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_ux_items, HP.ux_items.data(), sizeof(UxItem) * HP.ux_items.size(), hipMemcpyHostToDevice));
-        const std::vector<UxItem> cux = host::ux_items_compact(HP.ux_items, HP.compact_map);
-        HIP_TRY(hipMalloc(&c->progs[p].d_ux_items_compact, sizeof(UxItem) * cux.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_ux_items_compact, cux.data(), sizeof(UxItem) * cux.size(), hipMemcpyHostToDevice));
-        c->progs[p].gate_items = HP.gate_items;
-        c->progs[p].num_gate_cols = HP.num_gate_cols;
-        HIP_TRY(hipMalloc(&c->progs[p].d_gate_items, sizeof(GateItem) * HP.gate_items.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_gate_items, HP.gate_items.data(), sizeof(GateItem) * HP.gate_items.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&c->progs[p].d_aux_tab, sizeof(AuxTables)));
-        HIP_TRY(hipMemcpy(c->progs[p].d_aux_tab, &HP.aux_tab, sizeof(AuxTables), hipMemcpyHostToDevice));
-        c->progs[p].num_narrow = HP.num_narrow;
-        c->progs[p].num_wide = HP.num_wide;
-        HIP_TRY(hipMalloc(&c->progs[p].d_compact_map, sizeof(u32) * HP.compact_map.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_compact_map, HP.compact_map.data(), sizeof(u32) * HP.compact_map.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&c->progs[p].d_wide_before, sizeof(u32) * HP.wide_before.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_wide_before, HP.wide_before.data(), sizeof(u32) * HP.wide_before.size(), hipMemcpyHostToDevice));
-        std::vector<OpDesc> mid = host_ops(p, c->run_iters_mid, c->fb_run);
-        HIP_TRY(hipMalloc(&c->progs[p].d_ops_mid, sizeof(OpDesc) * mid.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_ops_mid, mid.data(), sizeof(OpDesc) * mid.size(), hipMemcpyHostToDevice));
-        std::vector<OpDesc> small = host_ops(p, c->run_iters_small, c->fb_run);
-        HIP_TRY(hipMalloc(&c->progs[p].d_ops_small, sizeof(OpDesc) * small.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_ops_small, small.data(), sizeof(OpDesc) * small.size(), hipMemcpyHostToDevice));
-        std::vector<OpDesc> plain = host_ops(p, 0);
-        HIP_TRY(hipMalloc(&c->progs[p].d_ops_plain, sizeof(OpDesc) * plain.size()));
-        HIP_TRY(hipMemcpy(c->progs[p].d_ops_plain, plain.data(), sizeof(OpDesc) * plain.size(), hipMemcpyHostToDevice));
+        DeviceProgram& DP = c->progs[p];
+        const host::ScheduleBuilder& sb = host_program(p).sb;
+        DP.host = &host_program(p);
+        DP.h_ops = sb.ops_with_runs(c->tune.run_iters, c->tune.fb_run);
+        HIP_TRY(DP.d_ops.upload(DP.h_ops));
+        HIP_TRY(DP.tab.upload(sb, DP.host->compact, true));
+        HIP_TRY(DP.d_ops_mid.upload(sb.ops_with_runs(c->tune.run_iters_mid, c->tune.fb_run)));
+        HIP_TRY(DP.d_ops_small.upload(sb.ops_with_runs(c->tune.run_iters_small, c->tune.fb_run)));
+        HIP_TRY(DP.d_ops_plain.upload(sb.ops_with_runs(0)));
     }
     HIP_TRY(hipMalloc(&c->d_counter, sizeof(unsigned long long)));
     HIP_TRY(hipHostMalloc(&c->h_counter, sizeof(unsigned long long)));
-    // ev[1] closes the scalar phase's column block (p2e_segments_*): it exists either way, with a timestamp only on request
-    for (auto& e : c->ev) HIP_TRY(hipEventCreateWithFlags(&e, (c->flags & P2E_CTX_PHASE_TIMING) ? hipEventDefault : hipEventDisableTiming));
     int prio_lo = 0, prio_hi = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
     // Internal streams, created AND bound to their hardware queues (one empty launch each) in the order of the layout
@@ -924,32 +791,31 @@ extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx*
             hipLaunchKernelGGL(k_touch, dim3(1), dim3(64), 0, c->stream);
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        int pads = 0;
-        for (const char* p = layout; *p; p++) {
-            hipStream_t* slot = nullptr;
-            int prio = prio_hi;
-            switch (*p) {
-            case 'M': slot = &c->st_msm; break;
-            case 'F': slot = &c->st_fixed; break;
-            case 'B': slot = &c->st_binv; break;
-            case '2': slot = &c->st_c2; prio = prio_lo; break;
-            case '1': slot = &c->st_c1; prio = 0; break;
-            case 'P': if (pads < 8) slot = &c->st_pad[pads++]; prio = 0; break;
-            default: break;
-            }
-            if (!slot || *slot) continue;
-            HIP_TRY(hipStreamCreateWithPriority(slot, hipStreamNonBlocking, prio));
-            if (touch) {
-                hipLaunchKernelGGL(k_touch, dim3(1), dim3(64), 0, *slot);
-                HIP_TRY(hipStreamSynchronize(*slot));
-            }
+        hipError_t err = hipSuccess;
+        const char* failed = "hipStreamCreateWithPriority";   // the call `err` came from
+        auto create = [&](hipStream_t& st, int cls) {
+            if (err == hipSuccess) err = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, cls > 0 ? prio_hi : cls < 0 ? prio_lo : 0);
+            return err == hipSuccess;
+        };
+        for (const char* p = layout; *p; p++) {   // the first free slot with this letter, if any
+            bool made = false;
+            each_internal_stream(c, [&](hipStream_t& st, char letter, int cls) {
+                if (made || st || letter != *p) return;
+                made = true;
+                if (create(st, cls) && touch) {
+                    hipLaunchKernelGGL(k_touch, dim3(1), dim3(64), 0, st);
+                    err = hipStreamSynchronize(st);
+                    if (err != hipSuccess) failed = "hipStreamSynchronize(internal stream)";
+                }
+            });
+            HIP_TRY_AS(failed, err);
         }
-        if (!c->st_msm) HIP_TRY(hipStreamCreateWithPriority(&c->st_msm, hipStreamNonBlocking, prio_hi));
-        if (!c->st_fixed) HIP_TRY(hipStreamCreateWithPriority(&c->st_fixed, hipStreamNonBlocking, prio_hi));
-        if (!c->st_binv) HIP_TRY(hipStreamCreateWithPriority(&c->st_binv, hipStreamNonBlocking, prio_hi));
-        if (!c->st_c2) HIP_TRY(hipStreamCreateWithPriority(&c->st_c2, hipStreamNonBlocking, prio_lo));
+        // the streams every plan needs, whatever the layout string left out
+        each_internal_stream(c, [&](hipStream_t& st, char letter, int cls) {
+            if (!st && letter && strchr("MFB2", letter)) create(st, cls);
+        });
+        HIP_TRY_AS(failed, err);
     }
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_c1join, hipEventDisableTiming));
     if (const char* env = getenv("P2E_QUAD_EXPAND_CUS")) {
         const int k = atoi(env);
         int ncu = 0;
@@ -965,31 +831,14 @@ extern "C" int p2e_ctx_create(int device, unsigned flags, void* stream, p2e_ctx*
             HIP_TRY(hipExtStreamCreateWithCUMask(&c->st_c2q, (uint32_t)mask.size(), mask.data()));
         }
     }
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_c2, hipEventDisableTiming));
-    for (auto& e : c->ev_binv) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_fixed, hipEventDisableTiming));
-    for (auto& e : c->ev_piece) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : c->ev_c0) HIP_TRY(hipEventCreate(&e));
-    for (auto& e : c->ev_c1) HIP_TRY(hipEventCreateWithFlags(&e, (c->flags & P2E_CTX_PHASE_TIMING) ? hipEventDefault : hipEventDisableTiming));
-    if (const char* env = getenv("P2E_MSM_PIECES")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= p2e_ctx::MAX_PIECES) c->msm_pieces = v;
+    {
+        hipError_t err = hipSuccess;
+        each_event(c, [&](hipEvent_t& e, unsigned opt) {
+            if (err == hipSuccess) err = hipEventCreateWithFlags(&e, opt);
+        });
+        HIP_TRY_AS("hipEventCreateWithFlags", err);
     }
-    if (const char* env = getenv("P2E_FIXED_PIECES")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= p2e_ctx::MAX_PIECES) c->fixed_pieces = v;
-    }
-    if (const char* env = getenv("P2E_MSM_PIECES_SMALL")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= p2e_ctx::MAX_PIECES) c->msm_pieces_small = v;
-    }
-    if (const char* env = getenv("P2E_FIXED_PIECES_SMALL")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= p2e_ctx::MAX_PIECES) c->fixed_pieces_small = v;
-    }
-    cleanup.c = nullptr;
-    *out = c;
+    *out = holder.release();
     return 0;
 }
 
@@ -997,46 +846,19 @@ extern "C" void p2e_ctx_destroy(p2e_ctx* c) {
     if (!c) return;
     DeviceGuard guard(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_cpts);
-    (void)hipFree(c->d_fbtab);
-    (void)hipFree(c->d_fbtab_p256);
-    (void)hipFree(c->d_constv);
-    for (auto& p : c->progs) {
-        (void)hipFree(p.d_ux_items);
-        (void)hipFree(p.d_gate_items);
-        (void)hipFree(p.d_ops);
-        (void)hipFree(p.d_ops_plain);
-        (void)hipFree(p.d_ops_mid);
-        (void)hipFree(p.d_ops_small);
-        (void)hipFree(p.d_aux_items);
-        (void)hipFree(p.d_aux_tab);
-        (void)hipFree(p.d_compact_map);
-        (void)hipFree(p.d_wide_before);
-        (void)hipFree(p.d_ux_items_compact);
-    }
+    each_internal_stream(c, [](hipStream_t& st, char, int) {
+        if (!st) return;
+        (void)hipStreamSynchronize(st);
+        (void)hipStreamDestroy(st);
+    });
+    each_event(c, [](hipEvent_t& e, unsigned) {
+        if (e) (void)hipEventDestroy(e);
+    });
     (void)hipFree(c->scratch);
     (void)hipFree(c->d_counter);
     (void)hipHostFree(c->h_counter);
-    for (auto& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_binv)
-        if (e) (void)hipEventDestroy(e);
-    for (hipStream_t st : {c->st_msm, c->st_fixed, c->st_binv, c->st_c2, c->st_c1, c->st_c1q, c->st_c2q, c->st_pad[0], c->st_pad[1], c->st_pad[2], c->st_pad[3],
-                           c->st_pad[4], c->st_pad[5], c->st_pad[6], c->st_pad[7]})
-        if (st) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-    for (hipEvent_t e : {c->ev_fork, c->ev_fixed, c->ev_c2, c->ev_c1join})
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_piece)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_c0)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_c1)
-        if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // the device tables (DeviceArray members): nothing is running any more
 }
 
 // Which part of the fused pipeline an asynchronous failure (a kernel fault surfaces only when a stream is
@@ -1249,8 +1071,9 @@ struct Staged {
     // it may still be running when the staged buffers are freed or the scratch is reused by the next call.
     void release(bool failed) {
         if (failed) {
-            for (hipStream_t st : {c->st_msm, c->st_fixed, c->st_binv, c->st_c2, c->st_c1, c->st_c1q, c->st_c2q})
+            each_internal_stream(c, [](hipStream_t& st, char, int) {
                 if (st) (void)hipStreamSynchronize(st);
+            });
             (void)hipStreamSynchronize(c->stream);
             (void)hipGetLastError();
         }
@@ -1476,7 +1299,7 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
                         bool verify_only = false) {
     const bool compact = cols == nullptr && !verify_only;
     const DeviceProgram& DP = c->progs[program];
-    const Program& G = DP.prog;
+    const Program& G = DP.host->sb.prog;
     Staged S(c);
     msg = S.in(msg, n * 32);
     r = S.in(r, n * 32);
@@ -1484,8 +1307,8 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
     pkx = S.in(pkx, n * 32);
     pky = S.in(pky, n * 32);
     if (compact) {
-        narrow = S.out(narrow, (size_t)DP.num_narrow * ldn * 4);
-        wide = S.out(wide, (size_t)DP.num_wide * ldw * 8);
+        narrow = S.out(narrow, (size_t)DP.host->compact.num_narrow * ldn * 4);
+        wide = S.out(wide, (size_t)DP.host->compact.num_wide * ldw * 8);
     } else if (!verify_only) {
         cols = S.out(cols, (size_t)G.num_cols * ld * 8);
     }
@@ -1495,43 +1318,29 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
     ScratchLayout L = scratch_layout(G, n);
     int rc = ensure_scratch(c, L.total);
     if (rc) return S.done(rc);
-    char* base = (char*)c->scratch;
     Buffers B{};
     B.msg = msg;
     B.r = r;
     B.s = s;
     B.pkx = pkx;
     B.pky = pky;
-    B.sink = Sink{cols, ld, narrow, ldn, wide, ldw, DP.d_wide_before};
+    B.sink = Sink{cols, ld, narrow, ldn, wide, ldw, DP.tab.wide_before.get()};
     B.n = n;
-    B.err = (u32*)(base + L.err32);
-    B.valid = (uint8_t*)(base + L.valid8);
-    B.PX = (U256*)(base + L.px);
-    B.PY = (U256*)(base + L.py);
-    B.PZ = (U256*)(base + L.pz);
-    B.PW = (U256*)(base + L.pw);
-    B.PREF = (U256*)(base + L.pref);
-    B.AX = (U256*)(base + L.ax);
-    B.AY = (U256*)(base + L.ay);
-    B.dig4 = (uint8_t*)(base + L.dig4);
-    B.dig2 = (uint8_t*)(base + L.dig2);
-    B.msrc = (uint16_t*)(base + L.msrc);
-    B.dyn = (uint16_t*)(base + L.dyn);
-    B.src = (uint16_t*)(base + L.src);
-    B.cpts = c->d_cpts;
-    B.fbtab = c->d_fbtab;
+    L.bind(B, (char*)c->scratch);
+    B.cpts = c->d_cpts.get();
+    B.fbtab = c->d_fbtab.get();
     // three regimes: four lanes per signature (n <= quad_max_n), lane per signature with phase B on two streams and longer
     // runs in fewer pieces (below binv_alt_max_n), and the large-batch plan
-    const bool mid_plan = n > c->quad_max_n && n < c->binv_alt_max_n;
-    const bool quad_plan = n <= c->quad_max_n;
+    const bool mid_plan = n > c->tune.quad_max_n && n < c->tune.binv_alt_max_n;
+    const bool quad_plan = n <= c->tune.quad_max_n;
     int run_iters = 0;
-    B.ops = DP.d_ops_plain;
-    if (n >= c->runs_min_n) {
-        run_iters = mid_plan ? c->run_iters_mid : c->run_iters;
-        if (run_iters > 0) B.ops = mid_plan ? DP.d_ops_mid : DP.d_ops;
-    } else if (quad_plan && c->run_iters_small > 0) {
-        run_iters = c->run_iters_small;
-        B.ops = DP.d_ops_small;
+    B.ops = DP.d_ops_plain.get();
+    if (n >= c->tune.runs_min_n) {
+        run_iters = mid_plan ? c->tune.run_iters_mid : c->tune.run_iters;
+        if (run_iters > 0) B.ops = mid_plan ? DP.d_ops_mid.get() : DP.d_ops.get();
+    } else if (quad_plan && c->tune.run_iters_small > 0) {
+        run_iters = c->tune.run_iters_small;
+        B.ops = DP.d_ops_small.get();
     }
     ZERO_COUNTER(c);
     unsigned gx = (unsigned)((n + BS - 1) / BS);
@@ -1540,7 +1349,7 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
     if (verify_only) {
         // the native verification alone: scalar phase without emission, the two chains side by side in Jacobian
         // coordinates (no batch inversion, no expansion), the final add, r == x on its Jacobian result
-        B.ops = DP.d_ops_plain;
+        B.ops = DP.d_ops_plain.get();
         hipLaunchKernelGGL(k_scalar<4>, dim3(gx), dim3(BS), 0, c->stream, G, B, (size_t)0);
         HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
         HIP_TRY(hipStreamWaitEvent(c->st_fixed, c->ev_fork, 0));
@@ -1556,7 +1365,7 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
     }
     // 16-byte column stores need full workgroups, an even column stride and a 16-byte aligned matrix
     // paired stores need full workgroups, even column strides and matrices aligned to two elements
-    const bool wide_ok = !getenv("P2E_NARROW_STORES") &&
+    const bool wide_ok = !narrow_stores_forced() &&
                          (compact ? (ldn % 2 == 0 && ldw % 2 == 0 && (reinterpret_cast<uintptr_t>(narrow) & 7) == 0 &&
                                      (reinterpret_cast<uintptr_t>(wide) & 15) == 0)
                                   : (ld % 2 == 0 && (reinterpret_cast<uintptr_t>(cols) & 15) == 0));
@@ -1592,12 +1401,12 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
     int ns = 0;
     const bool verify = G.num_chains == 3;
     // small batches: four lanes per signature in phase A, split inversion batches in phase B (quad.hpp)
-    const bool quad = n <= c->quad_max_n;
-    const int msm_pieces = quad ? c->msm_pieces_small : mid_plan ? c->msm_pieces_mid : c->msm_pieces;
+    const bool quad = n <= c->tune.quad_max_n;
+    const int msm_pieces = quad ? c->tune.msm_pieces_small : mid_plan ? c->tune.msm_pieces_mid : c->tune.msm_pieces;
     // with run expansion the fixed-base chain is ONE piece: its windows keep no X, Y / affine form in memory
     // (F_NO_AFFINE), so nothing could resume the chain from scratch in the middle
-    const bool fb_run = run_iters > 0 && verify && c->fb_run && G.fb_begin == G.chain_begin[1];
-    const int fixed_pieces = fb_run ? 1 : quad ? c->fixed_pieces_small : c->fixed_pieces;
+    const bool fb_run = run_iters > 0 && verify && c->tune.fb_run && G.fb_begin == G.chain_begin[1];
+    const int fixed_pieces = fb_run ? 1 : quad ? c->tune.fixed_pieces_small : c->tune.fixed_pieces;
     auto cut = [&](int lo, int hi, int pieces, hipStream_t st) {
         if (pieces > hi - lo) pieces = hi - lo;
         int a = lo;
@@ -1629,7 +1438,7 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
         // batch and expansion are the exposed tail of the call (2.27 / 2.92 against 2.32 / 2.98 ms at 2^13 / 12 288 with
         // equal pieces, profiles/r03_quad_plan_piece_sizes_sweep.txt)
         static const int takes_r4[p2e_ctx::MAX_PIECES + 1] = {6, 5, 5, 2, 0};
-        const int* takes = c->small_takes[0] > 0 ? c->small_takes : (quad && run_iters == 4 && iters == MSM_DIGITS) ? takes_r4 : c->small_takes;
+        const int* takes = c->tune.small_takes[0] > 0 ? c->tune.small_takes : (quad && run_iters == 4 && iters == MSM_DIGITS) ? takes_r4 : c->tune.small_takes;
         if (quad && takes[0] > 0) {
             int sum = 0;
             while (listed < p2e_ctx::MAX_PIECES - 1 && takes[listed] > 0 && sum + takes[listed] < nruns) sum += takes[listed++];
@@ -1661,10 +1470,10 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
     c->n_seg = ns;
 
     const unsigned gx4 = (unsigned)((4 * n + BS - 1) / BS);
-    const bool alt_b = quad || n < c->binv_alt_max_n;   // phase B of consecutive pieces on two streams
+    const bool alt_b = quad || n < c->tune.binv_alt_max_n;   // phase B of consecutive pieces on two streams
     auto launch_binv = [&](hipStream_t st, int lo, int hi, int have_prefix, bool last_piece = false, bool fixed_piece = false) {
-        const int sl = !quad ? (alt_b ? c->binv_mid_split_log2 : 0)
-                             : last_piece ? c->binv_split_log2_last : fixed_piece ? c->binv_split_log2_fixed : c->binv_split_log2;
+        const int sl = !quad ? (alt_b ? c->tune.binv_mid_split_log2 : 0)
+                             : last_piece ? c->tune.binv_split_log2_last : fixed_piece ? c->tune.binv_split_log2_fixed : c->tune.binv_split_log2;
         if ((quad || alt_b) && sl > 0)
             hipLaunchKernelGGL(k_batch_inv_split, dim3((unsigned)(((n << sl) + BS - 1) / BS)), dim3(BS), 0, st, G, B, lo, hi,
                                have_prefix, sl);
@@ -1745,7 +1554,7 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
     c->n_expand = 0;
     bool used_c2 = false;
     int last_b[2] = {-1, quad ? first_msm : -1};   // most recent inversion batch on st_fixed / st_binv (the table's: above)
-    emit_lds = quad ? c->expand_lds_small : c->expand_lds;
+    emit_lds = quad ? c->tune.expand_lds_small : c->tune.expand_lds;
     for (int q = 0; q < ns; q++) {
         const int k = order[q];
         const Seg& sg = segs[k];
@@ -1754,7 +1563,7 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
         // with C.  The fixed-base chain's stream is idle after its first ~1 ms, so phase B lives there.
         // (small-batch plan: phase B of consecutive pieces alternates between two streams, so that an inversion batch
         // does not queue behind the previous one -- there the chains are no slower than phase B)
-        const bool b_odd = (q & 1) != (quad && c->quad_b_first_on_fixed ? 1 : 0);
+        const bool b_odd = (q & 1) != (quad && c->tune.quad_b_first_on_fixed ? 1 : 0);
         hipStream_t st_b = (alt_b && b_odd) ? c->st_binv : c->st_fixed;
         if (k != first_msm) {
             HIP_TRY(hipStreamWaitEvent(st_b, c->ev_piece[k], 0));
@@ -1773,7 +1582,7 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
         // (the inversion batches sit on two in-order streams: the most recent one of each implies every earlier one, so
         // two waits say what q of them used to -- 28 barrier packets less on the expansion streams of a verify call)
         if (quad) {
-            if (c->quad_few_waits) {
+            if (c->tune.quad_few_waits) {
                 for (int sb = 0; sb < 2; sb++)
                     if (last_b[sb] >= 0 && last_b[sb] != k) HIP_TRY(hipStreamWaitEvent(st_c, c->ev_binv[last_b[sb]], 0));
             } else {
@@ -1891,23 +1700,23 @@ extern "C" long p2e_compact_to_rows(p2e_ctx* c, int program, const uint32_t* nar
     if (bad_common(c, n, ld_narrow) || program < 0 || program > 1 || ld_wide < n || !narrow || !wide || !rows_narrow || !rows_wide)
         return P2E_E_INVALID;
     const DeviceProgram& DP = c->progs[program];
-    if (row_ld_narrow < DP.num_narrow || row_ld_wide < DP.num_wide) {
+    if (row_ld_narrow < DP.host->compact.num_narrow || row_ld_wide < DP.host->compact.num_wide) {
         set_error("row stride smaller than the matrix");
         return P2E_E_INVALID;
     }
     if (n == 0) return 0;
     Staged S(c);
-    narrow = S.in(narrow, (size_t)DP.num_narrow * ld_narrow * 4);
-    wide = S.in(wide, (size_t)DP.num_wide * ld_wide * 8);
+    narrow = S.in(narrow, (size_t)DP.host->compact.num_narrow * ld_narrow * 4);
+    wide = S.in(wide, (size_t)DP.host->compact.num_wide * ld_wide * 8);
     rows_narrow = S.out(rows_narrow, n * row_ld_narrow * 4);
     rows_wide = S.out(rows_wide, n * row_ld_wide * 8);
     if (S.rc) return S.done(S.rc);
     ZERO_COUNTER(c);
     const unsigned gx = (unsigned)((n + 63) / 64);
-    hipLaunchKernelGGL(k_transpose<u32>, dim3(gx, (DP.num_narrow + 63) / 64), dim3(BS), 0, c->stream, narrow, ld_narrow, n,
-                       (size_t)DP.num_narrow, rows_narrow, row_ld_narrow);
-    hipLaunchKernelGGL(k_transpose<u64>, dim3(gx, (DP.num_wide + 63) / 64), dim3(BS), 0, c->stream, wide, ld_wide, n,
-                       (size_t)DP.num_wide, rows_wide, row_ld_wide);
+    hipLaunchKernelGGL(k_transpose<u32>, dim3(gx, (DP.host->compact.num_narrow + 63) / 64), dim3(BS), 0, c->stream, narrow, ld_narrow, n,
+                       (size_t)DP.host->compact.num_narrow, rows_narrow, row_ld_narrow);
+    hipLaunchKernelGGL(k_transpose<u64>, dim3(gx, (DP.host->compact.num_wide + 63) / 64), dim3(BS), 0, c->stream, wide, ld_wide, n,
+                       (size_t)DP.host->compact.num_wide, rows_wide, row_ld_wide);
     return S.done(finish_call(c));
 }
 
@@ -1920,9 +1729,9 @@ extern "C" long p2e_columns_compact(p2e_ctx* c, int program, const uint64_t* col
     if (n == 0) return 0;
     const DeviceProgram& DP = c->progs[program];
     Staged S(c);
-    cols = S.in(cols, (size_t)DP.prog.num_cols * ld * 8);
-    narrow = S.out(narrow, (size_t)DP.num_narrow * ld_narrow * 4);
-    wide = S.out(wide, (size_t)DP.num_wide * ld_wide * 8);
+    cols = S.in(cols, (size_t)DP.host->sb.prog.num_cols * ld * 8);
+    narrow = S.out(narrow, (size_t)DP.host->compact.num_narrow * ld_narrow * 4);
+    wide = S.out(wide, (size_t)DP.host->compact.num_wide * ld_wide * 8);
     err = S.out(err, n);
     if (S.rc) return S.done(S.rc);
     if (int rc = ensure_scratch(c, n * sizeof(u32))) return S.done(rc);
@@ -1931,9 +1740,9 @@ extern "C" long p2e_columns_compact(p2e_ctx* c, int program, const uint64_t* col
     HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
     const int pair_ok = ld % 2 == 0 && ld_narrow % 2 == 0 && ld_wide % 2 == 0 && (reinterpret_cast<uintptr_t>(cols) & 15) == 0 &&
                         (reinterpret_cast<uintptr_t>(narrow) & 7) == 0 && (reinterpret_cast<uintptr_t>(wide) & 15) == 0;
-    const u32 ncols = (u32)DP.prog.num_cols;
+    const u32 ncols = (u32)DP.host->sb.prog.num_cols;
     dim3 grid((unsigned)((n + 2 * BS - 1) / (2 * BS)), (ncols + COMPACT_GROUP - 1) / COMPACT_GROUP);
-    hipLaunchKernelGGL(k_compact, grid, dim3(BS), 0, c->stream, cols, ld, n, ncols, DP.d_compact_map, narrow, ld_narrow, wide,
+    hipLaunchKernelGGL(k_compact, grid, dim3(BS), 0, c->stream, cols, ld, n, ncols, DP.tab.compact_map.get(), narrow, ld_narrow, wide,
                        ld_wide, err32, pair_ok);
     hipLaunchKernelGGL(k_finalize, dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, c->stream, err32, (const uint8_t*)nullptr,
                        err, (uint8_t*)nullptr, n, c->d_counter);
@@ -1948,21 +1757,21 @@ static long run_aux(p2e_ctx* c, int program, const uint8_t* pky32, const uint64_
     const DeviceProgram& DP = c->progs[program];
     Staged S(c);
     pky32 = S.in(pky32, 32 * n);
-    if (cols) cols = S.in(cols, (size_t)DP.prog.num_cols * ld * 8);
-    if (narrow) narrow = S.in(narrow, (size_t)DP.num_narrow * ldn * 4);
-    aux = S.out((char*)aux, (size_t)DP.aux_tab.num_aux_cols * ld_aux * (aux_u32 ? 4 : 8));
+    if (cols) cols = S.in(cols, (size_t)DP.host->sb.prog.num_cols * ld * 8);
+    if (narrow) narrow = S.in(narrow, (size_t)DP.host->compact.num_narrow * ldn * 4);
+    aux = S.out((char*)aux, (size_t)DP.host->sb.aux_tab.num_aux_cols * ld_aux * (aux_u32 ? 4 : 8));
     err = S.out(err, n);
     if (S.rc) return S.done(S.rc);
     if (int rc = ensure_scratch(c, n * sizeof(u32))) return S.done(rc);
     ZERO_COUNTER(c);
     u32* err32 = (u32*)c->scratch;
     HIP_TRY(hipMemsetAsync(err32, 0, n * sizeof(u32), c->stream));
-    AuxArgs A{cols, ld, aux, ld_aux, n, pky32, c->d_cpts, c->d_fbtab, DP.d_aux_items, DP.d_aux_tab, err32,
-              narrow, ldn, DP.d_wide_before};
-    const unsigned gx = (unsigned)((n + BS - 1) / BS), items = (unsigned)DP.aux_items.size();
+    AuxArgs A{cols, ld, aux, ld_aux, n, pky32, c->d_cpts.get(), c->d_fbtab.get(), DP.tab.aux_items.get(), DP.tab.aux_tab.get(), err32,
+              narrow, ldn, DP.tab.wide_before.get()};
+    const unsigned gx = (unsigned)((n + BS - 1) / BS), items = (unsigned)DP.host->sb.aux_items.size();
     // paired column stores for the full workgroups, one element per lane for the ragged tail
     const bool wide_ok = (ld_aux % 2 == 0) && ((reinterpret_cast<uintptr_t>(aux) & (aux_u32 ? 7 : 15)) == 0) &&
-                         !getenv("P2E_NARROW_STORES");
+                         !narrow_stores_forced();
     const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
     const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
     if (aux_u32) {
@@ -1997,31 +1806,31 @@ extern "C" long p2e_aux_witness_compact_batch(p2e_ctx* c, int program, const uin
 }
 
 struct p2e_wire_map {
+    int device = 0;
     u32 limit[4] = {0, 0, 0, 0};   // column counts of the four source matrices (witness, aux, ux, gate) of the map's program
-    u32* d_src = nullptr;
-    u32* d_csrc = nullptr;   // the same entries with the witness columns in compact coordinates (narrow row, or WIRE_CSRC_WIDE | wide row)
-    u32* d_dst = nullptr;
+    DeviceArray<u32> d_src;
+    DeviceArray<u32> d_csrc;   // the same entries with the witness columns in compact coordinates (narrow row, or WIRE_CSRC_WIDE | wide row)
+    DeviceArray<u32> d_dst;
     size_t count = 0;
     u32 num_wires = 0, degree = 0;
     bool uses[4] = {false, false, false, false};
     u32 num_narrow = 0, num_wide = 0;   // rows of the program's compact container
     bool uses_narrow = false, uses_wide = false;
 };
-// cmap: the program's compact layout (p2e_compact_layout)
-static int make_wire_map(p2e_ctx* c, const u32 limit[4], const std::vector<u32>& cmap, u32 num_narrow, u32 num_wide,
-                         const p2e_wire_map_entry* entries, size_t count, uint32_t num_wires, uint32_t degree, p2e_wire_map** out) {
+// compact: the program's compact layout (p2e_compact_layout)
+static int make_wire_map(p2e_ctx* c, const u32 limit[4], const host::CompactLayout& compact, const p2e_wire_map_entry* entries,
+                         size_t count, uint32_t num_wires, uint32_t degree, p2e_wire_map** out) {
     if (!c || !out || (!entries && count) || !num_wires || !degree) return P2E_E_INVALID;
     const u64 cells = (u64)num_wires * degree;
     std::vector<p2e_wire_map_entry> v(entries, entries + count);
     std::stable_sort(v.begin(), v.end(), [](const p2e_wire_map_entry& a, const p2e_wire_map_entry& b) { return a.dst < b.dst; });
-    auto m = new p2e_wire_map();
+    std::unique_ptr<p2e_wire_map> m(new p2e_wire_map());
     for (size_t k = 0; k < count; k++) {
         const u32 kind = v[k].src >> 30, col = v[k].src & 0x3FFFFFFFu;
         if (col >= limit[kind] || v[k].dst >= cells || (k && v[k].dst == v[k - 1].dst)) {
             set_error(col >= limit[kind] ? "wire map: source column out of range"
                       : v[k].dst >= cells                          ? "wire map: destination outside num_wires * degree"
                                                                    : "wire map: two entries share a destination");
-            delete m;
             return P2E_E_INVALID;
         }
         m->uses[kind] = true;
@@ -2031,51 +1840,38 @@ static int make_wire_map(p2e_ctx* c, const u32 limit[4], const std::vector<u32>&
         src[k] = csrc[k] = v[k].src;
         dst[k] = v[k].dst;
         if ((v[k].src >> 30) == 0) {
-            const u32 slot = cmap[v[k].src];
+            const u32 slot = compact.map[v[k].src];
             const bool wide = (slot & COMPACT_WIDE) != 0;
             csrc[k] = wide ? (WIRE_CSRC_WIDE | (slot & ~COMPACT_WIDE)) : slot;
             (wide ? m->uses_wide : m->uses_narrow) = true;
         }
     }
     DeviceGuard guard(c->device);
+    m->device = c->device;
     for (int k = 0; k < 4; k++) m->limit[k] = limit[k];
     m->count = count;
     m->num_wires = num_wires;
     m->degree = degree;
-    m->num_narrow = num_narrow;
-    m->num_wide = num_wide;
-    const size_t bytes = sizeof(u32) * (count ? count : 1);
-    if (hipMalloc(&m->d_src, bytes) != hipSuccess || hipMalloc(&m->d_csrc, bytes) != hipSuccess || hipMalloc(&m->d_dst, bytes) != hipSuccess ||
-        hipMemcpy(m->d_src, src.data(), sizeof(u32) * count, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->d_csrc, csrc.data(), sizeof(u32) * count, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->d_dst, dst.data(), sizeof(u32) * count, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(m->d_src);
-        (void)hipFree(m->d_csrc);
-        (void)hipFree(m->d_dst);
-        delete m;
+    m->num_narrow = compact.num_narrow;
+    m->num_wide = compact.num_wide;
+    if (m->d_src.upload(src) != hipSuccess || m->d_csrc.upload(csrc) != hipSuccess || m->d_dst.upload(dst) != hipSuccess) {
         set_error("wire map: device allocation failed");
         return P2E_E_NOMEM;
     }
-    *out = m;
+    *out = m.release();
     return 0;
 }
 extern "C" int p2e_wire_map_create(p2e_ctx* c, int program, const p2e_wire_map_entry* entries, size_t count, uint32_t num_wires,
                                    uint32_t degree, p2e_wire_map** out) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    const DeviceProgram& HP = host_program(program);
-    const u32 limit[4] = {(u32)HP.prog.num_cols, HP.aux_tab.num_aux_cols, HP.num_ux_cols, HP.num_gate_cols};
-    return make_wire_map(c, limit, HP.compact_map, HP.num_narrow, HP.num_wide, entries, count, num_wires, degree, out);
+    const HostProgram& HP = host_program(program);
+    const u32 limit[4] = {(u32)HP.sb.prog.num_cols, HP.sb.aux_tab.num_aux_cols, HP.sb.num_ux_cols, HP.sb.num_gate_cols};
+    return make_wire_map(c, limit, HP.compact, entries, count, num_wires, degree, out);
 }
 extern "C" void p2e_wire_map_destroy(p2e_ctx* c, p2e_wire_map* m) {
     if (!m) return;
-    if (c) {
-        DeviceGuard guard(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(m->d_src);
-        (void)hipFree(m->d_csrc);
-        (void)hipFree(m->d_dst);
-    }
+    DeviceGuard guard(m->device);
+    if (c) (void)hipStreamSynchronize(c->stream);   // (no context: no stream that could still be reading the map)
     delete m;
 }
 // the launch of both assemblies: A holds the (staged) sources; the wire matrix is an in-out buffer
@@ -2090,8 +1886,8 @@ static long run_assemble(p2e_ctx* c, Staged& S, const p2e_wire_map* m, AssembleA
     }
     if (S.rc) return S.done(S.rc);
     ZERO_COUNTER(c);
-    A.src = compact ? m->d_csrc : m->d_src;
-    A.dst = m->d_dst;
+    A.src = compact ? m->d_csrc.get() : m->d_src.get();
+    A.dst = m->d_dst.get();
     A.count = m->count;
     A.wires = wires;
     A.stride = wire_stride;
@@ -2193,7 +1989,7 @@ static long run_gate(p2e_ctx* c, const void* aux, bool aux_u32, size_t ld_aux, u
     A.items = d_items;
     A.inv16[0] = 0;
     for (u64 d = 1; d < 16; d++) A.inv16[d] = gl_pow_host(d, P_GL - 2);
-    const bool wide_ok = (ld_gate % 2 == 0) && ((reinterpret_cast<uintptr_t>(gate) & 15) == 0) && !getenv("P2E_NARROW_STORES");
+    const bool wide_ok = (ld_gate % 2 == 0) && ((reinterpret_cast<uintptr_t>(gate) & 15) == 0) && !narrow_stores_forced();
     const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
     const dim3 gw((unsigned)(n_wide / BS), items), gt((unsigned)((n - n_wide + BS - 1) / BS), items);
     if (aux_u32) {
@@ -2214,8 +2010,9 @@ extern "C" long p2e_gate_internal_batch(p2e_ctx* c, int program, const uint64_t*
     }
     if (n == 0) return 0;
     const DeviceProgram& DP = c->progs[program];
-    return run_gate(c, aux, false, ld_aux, gate, ld_gate, n, DP.aux_tab.num_aux_cols, DP.num_gate_cols, DP.d_gate_items,
-                    (unsigned)DP.gate_items.size());
+    const host::ScheduleBuilder& sb = DP.host->sb;
+    return run_gate(c, aux, false, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, DP.tab.gate_items.get(),
+                    (unsigned)sb.gate_items.size());
 }
 extern "C" long p2e_gate_internal_compact_batch(p2e_ctx* c, int program, const uint32_t* aux32, size_t ld_aux, uint64_t* gate,
                                                 size_t ld_gate, size_t n) {
@@ -2225,12 +2022,13 @@ extern "C" long p2e_gate_internal_compact_batch(p2e_ctx* c, int program, const u
     }
     if (n == 0) return 0;
     const DeviceProgram& DP = c->progs[program];
-    return run_gate(c, aux32, true, ld_aux, gate, ld_gate, n, DP.aux_tab.num_aux_cols, DP.num_gate_cols, DP.d_gate_items,
-                    (unsigned)DP.gate_items.size());
+    const host::ScheduleBuilder& sb = DP.host->sb;
+    return run_gate(c, aux32, true, ld_aux, gate, ld_gate, n, sb.aux_tab.num_aux_cols, sb.num_gate_cols, DP.tab.gate_items.get(),
+                    (unsigned)sb.gate_items.size());
 }
 extern "C" long p2e_gate_internal_num_cols(int program) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    return (long)host_program(program).num_gate_cols;
+    return (long)host_program(program).sb.num_gate_cols;
 }
 
 // The constraint-block pass of any program.  Source: the u64 matrices cols / aux, or (cols == nullptr) the compact
@@ -2297,7 +2095,7 @@ static long run_ux(p2e_ctx* c, UxCall U, const UxKernel kern[4]) {
     A.items = compact ? U.d_items_compact : U.d_items;
     A.err = err32;
     const unsigned gx = (unsigned)((n + BS - 1) / BS);
-    const bool wide_ok = (U.ld_ux % 2 == 0) && ((reinterpret_cast<uintptr_t>(ux) & (U.ux_u32 ? 7 : 15)) == 0) && !getenv("P2E_NARROW_STORES");
+    const bool wide_ok = (U.ld_ux % 2 == 0) && ((reinterpret_cast<uintptr_t>(ux) & (U.ux_u32 ? 7 : 15)) == 0) && !narrow_stores_forced();
     const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
     const dim3 gw((unsigned)(n_wide / BS), U.items), gt((unsigned)((n - n_wide + BS - 1) / BS), U.items);
     const int u32_bit = U.ux_u32 ? 2 : 0;
@@ -2322,14 +2120,14 @@ static UxCall builtin_ux_call(p2e_ctx* c, int program, const uint8_t* msg32, con
     U.ld_ux = ld_ux;
     U.n = n;
     U.err = err;
-    U.num_cols = (u32)DP.prog.num_cols;
-    U.num_narrow = DP.num_narrow;
-    U.num_aux_cols = DP.aux_tab.num_aux_cols;
-    U.num_ux_cols = DP.num_ux_cols;
-    U.d_consts = c->d_constv;
-    U.d_items = DP.d_ux_items;
-    U.d_items_compact = DP.d_ux_items_compact;
-    U.items = (unsigned)DP.ux_items.size();
+    U.num_cols = (u32)DP.host->sb.prog.num_cols;
+    U.num_narrow = DP.host->compact.num_narrow;
+    U.num_aux_cols = DP.host->sb.aux_tab.num_aux_cols;
+    U.num_ux_cols = DP.host->sb.num_ux_cols;
+    U.d_consts = c->d_constv.get();
+    U.d_items = DP.tab.ux_items.get();
+    U.d_items_compact = DP.tab.ux_items_compact.get();
+    U.items = (unsigned)DP.host->sb.ux_items.size();
     return U;
 }
 extern "C" long p2e_ux_witness_batch(p2e_ctx* c, int program, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
@@ -2373,20 +2171,20 @@ extern "C" long p2e_ux_witness_compact_batch(p2e_ctx* c, int program, const uint
 // ====================================================================================================
 extern "C" long p2e_ux_describe(int program, p2e_ux_desc* out, size_t cap) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    const DeviceProgram& P = host_program(program);
-    for (size_t i = 0; i < P.ux_first.size() && i < cap && out; i++) {
-        out[i].first_col = P.ux_first[i];
-        out[i].num_cols = P.ux_count[i];
+    const host::ScheduleBuilder& sb = host_program(program).sb;
+    for (size_t i = 0; i < sb.ux_first.size() && i < cap && out; i++) {
+        out[i].first_col = sb.ux_first[i];
+        out[i].num_cols = sb.ux_count[i];
     }
-    return (long)P.ux_first.size();
+    return (long)sb.ux_first.size();
 }
 extern "C" long p2e_ux_num_cols(int program) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    return (long)host_program(program).num_ux_cols;
+    return (long)host_program(program).sb.num_ux_cols;
 }
 extern "C" long p2e_aux_describe(int program, p2e_aux_desc* out, size_t cap) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    const auto& g = host_program(program).aux_gens;
+    const auto& g = host_program(program).sb.aux_gens;
     for (size_t i = 0; i < g.size() && i < cap && out; i++) {
         out[i].kind = g[i].kind;
         out[i].first_col = g[i].col;
@@ -2398,19 +2196,19 @@ extern "C" long p2e_aux_describe(int program, p2e_aux_desc* out, size_t cap) {
 }
 extern "C" long p2e_compact_layout(int program, uint32_t* col_map, size_t cap, uint32_t* num_narrow, uint32_t* num_wide) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    const DeviceProgram& P = host_program(program);
-    for (size_t i = 0; i < P.compact_map.size() && i < cap && col_map; i++) col_map[i] = P.compact_map[i];
-    if (num_narrow) *num_narrow = P.num_narrow;
-    if (num_wide) *num_wide = P.num_wide;
-    return (long)P.compact_map.size();
+    const host::CompactLayout& L = host_program(program).compact;
+    for (size_t i = 0; i < L.map.size() && i < cap && col_map; i++) col_map[i] = L.map[i];
+    if (num_narrow) *num_narrow = L.num_narrow;
+    if (num_wide) *num_wide = L.num_wide;
+    return (long)L.map.size();
 }
 extern "C" long p2e_aux_num_cols(int program) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    return host_program(program).aux_tab.num_aux_cols;
+    return host_program(program).sb.aux_tab.num_aux_cols;
 }
 extern "C" long p2e_schedule_describe(int program, p2e_gen_desc* out, size_t cap) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    const auto& g = host_program(program).gens;
+    const auto& g = host_program(program).sb.gens;
     for (size_t i = 0; i < g.size() && i < cap && out; i++) {
         out[i].kind = g[i].kind;
         out[i].field = g[i].field;
@@ -2423,7 +2221,7 @@ extern "C" long p2e_schedule_describe(int program, p2e_gen_desc* out, size_t cap
 }
 extern "C" long p2e_schedule_wiring(int program, p2e_gen_wiring* out, size_t cap) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    const auto& g = host_program(program).gens;
+    const auto& g = host_program(program).sb.gens;
     for (size_t i = 0; i < g.size() && i < cap && out; i++) {
         out[i].num_operands = g[i].nops;
         out[i].range_check = g[i].range_check ? 1 : 0;
@@ -2446,7 +2244,7 @@ extern "C" int p2e_wiring_const(uint32_t id, uint8_t out32[32]) {
 }
 extern "C" long p2e_schedule_num_cols(int program) {
     if (program < 0 || program > 1) return P2E_E_INVALID;
-    return host_program(program).prog.num_cols;
+    return host_program(program).sb.prog.num_cols;
 }
 extern "C" int p2e_synth_signatures(uint64_t seed, size_t first, size_t n, uint8_t* msg32, uint8_t* r32, uint8_t* s32,
                                     uint8_t* pkx32, uint8_t* pky32) {
@@ -2546,26 +2344,21 @@ static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Af
         set_error("batch too large for one launch");
         return P2E_E_INVALID;
     }
-    *chosen = plan == P2E_SIGN_PLAN_AUTO ? (n <= c->sign_quad_max_n ? SIGN_PLAN_QUAD : SIGN_PLAN_LANE) : (int)plan;
+    *chosen = plan == P2E_SIGN_PLAN_AUTO ? (n <= c->tune.sign_quad_max_n ? SIGN_PLAN_QUAD : SIGN_PLAN_LANE) : (int)plan;
     if (curve == P2E_CURVE_SECP256K1) {
-        *table = c->d_fbtab;
+        *table = c->d_fbtab.get();
         return 0;
     }
-    if (!c->d_fbtab_p256 && n) {
+    if (!c->d_fbtab_p256.get() && n) {
         DeviceGuard guard(c->device);
         static const std::vector<Aff> t = host::fixed_base_table_cv<P256>(host::generator_cv<P256>());
-        Aff* d = nullptr;
-        HIP_TRY(hipMalloc(&d, sizeof(Aff) * t.size()));
-        hipError_t e = hipMemcpy(d, t.data(), sizeof(Aff) * t.size(), hipMemcpyHostToDevice);
+        hipError_t e = c->d_fbtab_p256.upload(t);
         if (e != hipSuccess) {
-            (void)hipFree(d);
-            (void)hipGetLastError();
             set_error(std::string("upload of the P-256 generator table failed: ") + hipGetErrorString(e));
             return P2E_E_HIP;
         }
-        c->d_fbtab_p256 = d;
     }
-    *table = c->d_fbtab_p256;
+    *table = c->d_fbtab_p256.get();
     return 0;
 }
 extern "C" long p2e_ecdsa_public_key_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* sk32, uint8_t* pkx32, uint8_t* pky32,

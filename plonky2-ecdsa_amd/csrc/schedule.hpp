@@ -550,7 +550,14 @@ public:
 
     // Expansion runs of `run_iters` loop iterations: inside a run only the last (double, conditional add) pair
     // can be the next run's starting point, every other result never needs affine coordinates in memory.
-    void mark_runs(int run_iters, bool mark_fb = true) {
+    void mark_runs(int run_iters, bool mark_fb = true) { mark_runs(ops, run_iters, mark_fb); }
+    // the op list with those marks, the builder left as it is
+    std::vector<OpDesc> ops_with_runs(int run_iters, bool mark_fb = true) const {
+        std::vector<OpDesc> marked(ops);
+        mark_runs(marked, run_iters, mark_fb);
+        return marked;
+    }
+    void mark_runs(std::vector<OpDesc>& ops, int run_iters, bool mark_fb) const {
         for (auto& o : ops) o.flags &= (uint8_t)~F_NO_AFFINE;
         if (run_iters < 1) return;
         const int D = prog.loop_dbls;   // doublings per iteration; the conditional add follows them

@@ -13,6 +13,7 @@
 #include "../../plonky2-ecdsa_amd/csrc/quad.hpp"
 #include "../../plonky2-ecdsa_amd/csrc/schedule.hpp"
 #include "../../plonky2-ecdsa_amd/csrc/curve_program.hpp"
+#include "../../plonky2-ecdsa_amd/csrc/knobs.hpp"
 
 using namespace p2e;
 
@@ -377,6 +378,25 @@ long emu_safegcd_selfcheck(int field, unsigned long long seed, size_t n) {
         fails += field == 0 ? safegcd_one<ModP>(x) : field == 1 ? safegcd_one<ModN>(x) : field == 2 ? safegcd_one<ModP256>(x) : safegcd_one<ModN256>(x);
     }
     return fails;
+}
+// the knob table (csrc/knobs.hpp) read from `count` (name, value) pairs instead of the environment: out[0..21] = the
+// scalar fields in the order below, out[22..38] = small_takes
+long emu_tuning(const char* const* names, const char* const* values, size_t count, long long* out) {
+    Tuning t;
+    read_tuning(t, [&](const char* name) -> const char* {
+        for (size_t k = 0; k < count; k++)
+            if (!std::strcmp(names[k], name)) return values[k];
+        return nullptr;
+    });
+    const long long scalars[] = {t.run_iters, t.run_iters_mid, t.run_iters_small, t.fb_run, (long long)t.runs_min_n, (long long)t.quad_max_n,
+                                 (long long)t.cp_quad_max_n, (long long)t.binv_alt_max_n, (long long)t.cp_runs_min_n, t.msm_pieces,
+                                 t.msm_pieces_mid, t.msm_pieces_small, t.fixed_pieces, t.fixed_pieces_small, t.binv_mid_split_log2,
+                                 t.binv_split_log2, t.binv_split_log2_last, t.binv_split_log2_fixed, t.quad_b_first_on_fixed,
+                                 t.quad_few_waits, t.expand_lds_small, t.expand_lds};
+    long k = 0;
+    for (long long v : scalars) out[k++] = v;
+    for (int v : t.small_takes) out[k++] = v;
+    return k;
 }
 long emu_verify(const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx, const uint8_t* pky,
                 uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int chunk, int run_iters) {

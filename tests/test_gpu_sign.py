@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 N_MAIN = 4161            # 65 full waves of scalars + one lane: the quad plan ends in a workgroup with a single live quad
 PLANS = [S.PLAN_LANE, S.PLAN_QUAD]
-AUTO_QUAD_MAX_N = 65536   # p2e_ctx::sign_quad_max_n: P2E_SIGN_PLAN_AUTO takes the quad plan up to here
+AUTO_QUAD_MAX_N = 65536   # Tuning::sign_quad_max_n: P2E_SIGN_PLAN_AUTO takes the quad plan up to here
 
 
 @pytest.fixture(scope="module")
@@ -146,7 +146,7 @@ def test_s_equal_zero_is_returned_unflagged(curve_id, ctx):
 
 @pytest.mark.parametrize("curve_id", [0, 1])
 def test_auto_plan_equals_both_forced_plans_around_its_threshold(curve_id, ctx):
-    """ragged batches on either side of the AUTO threshold (p2e_ctx::sign_quad_max_n, MEASUREMENTS.md)"""
+    """ragged batches on either side of the AUTO threshold (Tuning::sign_quad_max_n, MEASUREMENTS.md)"""
     threshold = AUTO_QUAD_MAX_N
     rng = np.random.default_rng(77 + curve_id)
     for n in (threshold - 61, threshold + 67):
