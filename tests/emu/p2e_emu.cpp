@@ -242,6 +242,25 @@ extern "C" long emu_f29_selftest(unsigned long long seed, size_t n) {
     return fails;
 }
 
+// f29_canon on caller-supplied limb forms (nine limbs each below 2^31, any value): the canonical 256-bit value,
+// little-endian.  The walks above never hand it a value in [p, 2^256) -- the one range in which only its final conditional
+// subtraction makes the result canonical -- so tests/test_adversarial_cpu.py builds such forms directly.
+extern "C" long emu_f29_canon(const uint32_t* limbs, size_t n, uint8_t* out) {
+    for (size_t i = 0; i < n; i++) {
+        F29 a;
+        for (int k = 0; k < 9; k++) {
+            a.l[k] = limbs[9 * i + k];
+            if (a.l[k] >> 31) return -1;
+#if P2E_F29_TRACK
+            a.ub[k] = a.l[k];
+#endif
+        }
+        const U256 x = f29_canon_call(a);
+        memcpy(out + 32 * i, x.w, 32);
+    }
+    return (long)n;
+}
+
 // the same stress loop for fe_inv_safegcd (csrc/fe.hpp), over all four moduli of the crate (field: 0 p, 1 n of secp256k1,
 // 2 p, 3 n of P-256): x * inv(x) == 1, the result is canonical and equal to fe_inv_bingcd's; zero is reported as not invertible
 template <class MOD>
