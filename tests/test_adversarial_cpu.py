@@ -100,33 +100,9 @@ def test_lazy_limb_canonical_reduction_between_p_and_2_256(emu):
     2^32 + 976 (= 2^256 - 1 - p) and values within 2^32 of p on either side, h = 0 .. 127 (the bits above 2^256 that limb 8
     may carry), split into 29-bit limbs and again with a borrow pushed into every limb (limbs up to 2^30, as sums of two
     tight values have); also p - 1, 2 p - 1, 0 and uniform limbs below 2^31.  Expected: the value mod p, Python integers."""
+    import probe_inputs
+    forms, want = probe_inputs.canon_forms()                   # (the builder is shared with the device probe's f29_canon ops)
     p = R.P
-    c = (1 << 256) - p
-    rng = np.random.default_rng(29)
-    ds = [0, 1, 2, 976, 977, 1 << 29, (1 << 32) - 1, 1 << 32, c - 2, c - 1] + [int(v) for v in rng.integers(0, c, 40)]
-    values = [(1 + h) * p + d for d in ds for h in (0, 1, 2, 5, 64, 127) if (1 + h) * p + d < 128 << 256]
-    values += [p - 1, p - 2, p - c, 2 * p - 1, 0, 1, (1 << 256) - 1, 1 << 256, (1 << 256) + c - 1]
-    values += [p - int(v) for v in rng.integers(1, 1 << 32, 20)]
-    forms, want = [], []
-    for v in values:
-        l = [(v >> (29 * k)) & R.MASK29 for k in range(8)] + [v >> 232]
-        assert l[8] < 1 << 31
-        forms.append(l)
-        for k in range(8):                                     # the same value with 2^29 borrowed from limb k + 1
-            if l[k + 1]:
-                b = list(l)
-                b[k] += 1 << 29
-                b[k + 1] -= 1
-                forms.append(b)
-        b = list(l)
-        for k in range(8):                                     # ... and borrowed everywhere it can be
-            if b[k + 1]:
-                b[k] += 1 << 29
-                b[k + 1] -= 1
-        forms.append(b)
-    for _ in range(2000):
-        forms.append([int(v) for v in rng.integers(0, 1 << 31, 9)])
-    want = [sum(x << (29 * k) for k, x in enumerate(l)) % p for l in forms]
     arr = np.array(forms, np.uint32)
     out = np.zeros((len(forms), 32), np.uint8)
     emu.L.emu_f29_canon.restype = C.c_long
