@@ -548,6 +548,60 @@ long p2e_ecdsa_recover_batch(p2e_ctx *ctx, int curve, const uint8_t *msg32, cons
 long p2e_ecdsa_sign_recoverable_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *msg32, const uint8_t *sk32,
                                       const uint8_t *k32, uint8_t *r32, uint8_t *s32, uint8_t *v, size_t n, uint8_t *err);
 
+/* ---- message hashing, deterministic nonces and Ethereum addresses: the two ends of the signing pipeline.  Raw bytes on
+ * the device become msg32, then (r, s, v), then pk, then the sender's address, and nothing passes through the host.
+ * The nearest reference counterpart is curve/ecdsa.rs:25-40 sign_message, which takes the message as a field element and
+ * draws its nonce with rand() (:29-32): the reference neither hashes nor derives nonces, so what these calls compute is
+ * defined by FIPS 180-4 (SHA-256), the Keccak submission as Ethereum uses it, and RFC 6979 section 3.2.
+ *
+ * p2e_hash_batch      out32[32 i ..] = hash of message i = data[offsets[i], offsets[i + 1]), i < n (offsets holds n + 1
+ *     entries).  Messages are concatenated without padding; neither data nor any offset needs an alignment (out32 and
+ *     offsets are aligned to 4 and 8 bytes, as arrays of their types).  The kernel reads aligned 4-byte words and only
+ *     those that hold at least one byte of a message: nothing before data + offsets[i] rounded down to 4 and nothing from
+ *     data + offsets[i + 1] rounded up to 4 on.  Every offset lies in [offsets[0], offsets[n]].
+ *     alg: P2E_HASH_SHA256, P2E_HASH_SHA256D (SHA-256 of the SHA-256 digest), P2E_HASH_KECCAK256 (rate 136, the legacy
+ *     0x01 padding: Ethereum's hash, NOT SHA3-256).  out_form: P2E_DIGEST_BYTES = the 32 digest bytes in the order the
+ *     hash defines;  P2E_DIGEST_SCALAR = the same bytes reversed, i.e. the digest read as a big-endian integer and stored
+ *     as the 32-byte little-endian msg32 of every other entry point.
+ *     An element with offsets[i + 1] < offsets[i] is hashed as the empty message; the return value is the number of such
+ *     elements (0 otherwise).  P2E_E_INVALID on a null pointer or an unknown alg or out_form; n == 0 returns 0.
+ *     With P2E_CTX_HOST_POINTERS the library reads offsets[0] and offsets[n] on the host to size its staging copy of
+ *     data[offsets[0], offsets[n]) (offsets[n] < offsets[0] is P2E_E_INVALID there).
+ * p2e_ecdsa_nonce_rfc6979_batch   k32[32 i ..] = the RFC 6979 section 3.2 nonce (HMAC-SHA256; qlen = hlen = 256, so
+ *     bits2int is the identity on both curves) for the key sk32[i] and the message hash msg32[i], both taken modulo n
+ *     exactly as p2e_ecdsa_sign_batch takes them; 32 bytes little-endian, 1 <= k < n.  Returns 0.
+ *     The output is secret and a nonce must never sign two different messages: both are the caller's concern.
+ * p2e_ecdsa_sign_deterministic_batch   r, s, v and err are bit for bit what p2e_ecdsa_sign_recoverable_batch returns for
+ *     the same inputs and plan with k32 taken from p2e_ecdsa_nonce_rfc6979_batch; v == NULL: no recovery byte is written
+ *     (p2e_ecdsa_sign_batch's outputs).  Two launches on the caller's stream: the nonce kernel writes into the context's
+ *     scratch block (32 n bytes, allocated on first need and kept), the unchanged signing kernel reads it, and a memset
+ *     on the same stream wipes it behind the signer.  r = 0 or s = 0 are returned as computed and NOT flagged, as
+ *     sign_message and p2e_ecdsa_sign_batch return them: RFC 6979 section 3.2's further retry for them (step h.3's "if r
+ *     or s is zero, update K and V and loop") is NOT implemented.  sk = 0 (mod n) is defined and not flagged, as in the
+ *     plain signer.  Return value: number of flagged elements (none for k in [1, n)).
+ * p2e_eth_address_batch   addr20[20 i ..] = keccak256(BE32(pkx) || BE32(pky))[12..32], the inputs being this library's
+ *     little-endian coordinates (each is reversed).  err (nullable): where err[i] != 0, twenty zero bytes are written --
+ *     pass the err of p2e_ecdsa_recover_batch, whose flagged elements hold zero coordinates that must not turn into a
+ *     plausible address.  addr20 is 4-byte aligned.  Returns 0.  secp256k1 by meaning: there is no curve argument.
+ * Each call is one kernel (the deterministic signer: two and a memset) on the context's caller stream: no internal
+ * streams, no LDS.  P2E_E_INVALID on a null pointer (other than the nullable ones), an unknown curve or plan; n == 0
+ * returns 0.  Host pointers, async mode, the current device and failed calls behave as for the signing calls. */
+#define P2E_HASH_SHA256 0
+#define P2E_HASH_SHA256D 1     /* SHA-256 of the SHA-256 digest (Bitcoin) */
+#define P2E_HASH_KECCAK256 2   /* legacy 0x01 padding (Ethereum), not SHA3-256 */
+#define P2E_DIGEST_BYTES 0     /* the 32 digest bytes as the hash defines them */
+#define P2E_DIGEST_SCALAR 1    /* byte-reversed: the digest read as a big-endian integer, stored as the 32-byte
+                                  little-endian msg32 every other entry point takes */
+long p2e_hash_batch(p2e_ctx *ctx, int alg, unsigned out_form, const uint8_t *data, const uint64_t *offsets /* n + 1 */,
+                    uint8_t *out32, size_t n);
+long p2e_ecdsa_nonce_rfc6979_batch(p2e_ctx *ctx, int curve, const uint8_t *msg32, const uint8_t *sk32, uint8_t *k32,
+                                   size_t n);
+long p2e_ecdsa_sign_deterministic_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *msg32,
+                                        const uint8_t *sk32, uint8_t *r32, uint8_t *s32, uint8_t *v /* nullable */,
+                                        size_t n, uint8_t *err);
+long p2e_eth_address_batch(p2e_ctx *ctx, const uint8_t *pkx32, const uint8_t *pky32, const uint8_t *err /* nullable */,
+                           uint8_t *addr20, size_t n);
+
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */
 int p2e_synth_signatures(uint64_t seed, size_t first, size_t n, uint8_t *msg32, uint8_t *r32, uint8_t *s32,

@@ -39,6 +39,8 @@ ERR_DIVISION_BY_ZERO = 32
 ERR_POINT_AT_INFINITY = 64   # ecdsa_public_key_batch: sk = 0 (mod n)
 ERR_NOT_RECOVERABLE = 128    # ecdsa_recover_batch: (r, s, v) names no curve point
 SIGN_PLAN_AUTO, SIGN_PLAN_LANE, SIGN_PLAN_QUAD = 0, 1, 2   # include/p2e.h P2E_SIGN_PLAN_*
+HASH_SHA256, HASH_SHA256D, HASH_KECCAK256 = 0, 1, 2        # include/p2e.h P2E_HASH_*
+DIGEST_BYTES, DIGEST_SCALAR = 0, 1                         # include/p2e.h P2E_DIGEST_*
 CTX_HOST_POINTERS, CTX_ASYNC, CTX_PHASE_TIMING = 1, 2, 4
 VERIFY_COLS = 82615
 GLV_MUL_COLS = 65243
@@ -79,6 +81,7 @@ EXPORTS = (
     "p2e_curve_program_ux_witness_compact_batch", "p2e_curve_msm_ux_witness_batch",
     "p2e_ecdsa_public_key_batch", "p2e_ecdsa_sign_batch",
     "p2e_ecdsa_recover_batch", "p2e_ecdsa_sign_recoverable_batch",
+    "p2e_hash_batch", "p2e_ecdsa_nonce_rfc6979_batch", "p2e_ecdsa_sign_deterministic_batch", "p2e_eth_address_batch",
 )
 
 
@@ -1055,6 +1058,57 @@ class Context:
         bad = self._check(self._L.p2e_ecdsa_recover_batch(self._h, C.c_int(curve), _ptr(msg), _ptr(r), _ptr(s), _ptr(v), _ptr(pkx),
                                                           _ptr(pky), C.c_size_t(n), _ptr(err)))
         return pkx, pky, err, bad
+
+    # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
+    def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):
+        """Hash message i = data[offsets[i]:offsets[i + 1]] for i < n = len(offsets) - 1: data a 1-D uint8 buffer (any
+        alignment, messages concatenated without padding), offsets (n + 1,) int64 / uint64.  alg: HASH_SHA256, HASH_SHA256D,
+        HASH_KECCAK256 (Ethereum's, not SHA3-256); out_form: DIGEST_BYTES, or DIGEST_SCALAR = the msg32 of the signing calls.
+        (out (n, 32), count of elements with offsets[i + 1] < offsets[i]: those are hashed as the empty message)."""
+        n = self._shape(offsets)[0] - 1
+        out = out if out is not None else self._packed(n)
+        bad = self._check(self._L.p2e_hash_batch(self._h, C.c_int(alg), C.c_uint(out_form), _ptr(data), _ptr(offsets), _ptr(out),
+                                                 C.c_size_t(n)))
+        return out, bad
+
+    def ecdsa_nonce_rfc6979_batch(self, msg, sk, curve=CURVE_SECP256K1, k=None):
+        """The RFC 6979 nonce (HMAC-SHA256) of every (msg, sk), both (n, 32) little-endian and taken modulo the group order as
+        the signer takes them: (k (n, 32) little-endian with 1 <= k < n, 0).  The output is secret."""
+        n = self._shape(msg)[0]
+        k = k if k is not None else self._packed(n)
+        rc = self._check(self._L.p2e_ecdsa_nonce_rfc6979_batch(self._h, C.c_int(curve), _ptr(msg), _ptr(sk), _ptr(k), C.c_size_t(n)))
+        return k, rc
+
+    def ecdsa_sign_deterministic_batch(self, msg, sk, curve=CURVE_SECP256K1, plan=SIGN_PLAN_AUTO, r=None, s=None, v=None, err=None,
+                                       recoverable=True):
+        """ecdsa_sign_recoverable_batch with the nonces of ecdsa_nonce_rfc6979_batch, which never leave the library:
+        (r, s, v, err, flagged count), bit for bit.  recoverable=False: no v is written (None is returned in its place) and
+        the outputs are ecdsa_sign_batch's.  r = 0 or s = 0 are returned unflagged (RFC 6979's retry for them is not done)."""
+        n = self._shape(msg)[0]
+        r = r if r is not None else self._packed(n)
+        s = s if s is not None else self._packed(n)
+        if recoverable:
+            v = v if v is not None else self._vec(n, np.uint8)
+        else:
+            v = None
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_ecdsa_sign_deterministic_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(msg), _ptr(sk), _ptr(r),
+                                                                     _ptr(s), _ptr(v), C.c_size_t(n), _ptr(err)))
+        return r, s, v, err, bad
+
+    def eth_address_batch(self, pkx, pky, err=None, addr=None):
+        """Ethereum addresses keccak256(BE32(pkx) || BE32(pky))[12:] of (n, 32) little-endian secp256k1 coordinates:
+        (addr (n, 20), 0).  err (n,) uint8, optional: where err[i] != 0 the address is twenty zero bytes (pass
+        ecdsa_recover_batch's err, whose flagged elements hold zero coordinates)."""
+        n = self._shape(pkx)[0]
+        if addr is None:
+            if self.host_pointers:
+                addr = np.zeros((n, 20), dtype=np.uint8)
+            else:
+                import torch
+                addr = torch.empty((n, 20), dtype=torch.uint8, device=f"cuda:{self.device}")
+        rc = self._check(self._L.p2e_eth_address_batch(self._h, _ptr(pkx), _ptr(pky), _ptr(err), _ptr(addr), C.c_size_t(n)))
+        return addr, rc
 
     def _compact_out(self, program, n, narrow, wide, ld_narrow, ld_wide):
         _m, nn, nw = compact_layout(program)

@@ -23,6 +23,7 @@
 #include "curve_program.hpp"
 #include "sign.hpp"
 #include "recover.hpp"
+#include "hash.hpp"
 
 using namespace p2e;
 using host::COMPACT_WIDE;
@@ -31,7 +32,7 @@ using host::COMPACT_WIDE;
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
 // streaming passes, descriptions;  1 = the fused pipeline of the two built-in programs (run_program);  2 / 3 = the
 // curve-program pipeline instantiated for secp256k1 / P-256 (run_curve_program<CV>).  Undefined = everything in one
-// unit.  Small static helpers (error text, staging, scratch) are compiled into every part.
+// unit.  The hashing, nonce and address kernels (hash.hpp) ride in part 1, the part that builds fastest.  Small static helpers (error text, staging, scratch) are compiled into every part.
 #ifndef P2E_PART
 #define P2E_PART (-1)
 #endif
@@ -2468,6 +2469,160 @@ extern "C" long p2e_ecdsa_recover_batch(p2e_ctx* c, int curve, const uint8_t* ms
         launch_recover<P256>(c, table, msg32, r32, s32, v, pkx32, pky32, n, err);
     else
         launch_recover<Secp256k1>(c, table, msg32, r32, s32, v, pkx32, pky32, n, err);
+    return S.done(finish_call(c));
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// message hashing, RFC 6979 nonces, Ethereum addresses (hash.hpp)
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 1 (the part that builds fastest), called from part 0
+void launch_hash(p2e_ctx* c, int alg, unsigned form, const uint8_t* data, const uint64_t* offsets, uint8_t* out32, size_t n);
+void launch_nonce_rfc6979(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* sk32, uint8_t* k32, size_t n);
+void launch_eth_address(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err, uint8_t* addr20, size_t n);
+#if P2E_HAS(1)
+void launch_hash(p2e_ctx* c, int alg, unsigned form, const uint8_t* data, const uint64_t* offsets, uint8_t* out32, size_t n) {
+    if (alg == P2E_HASH_KECCAK256)
+        hipLaunchKernelGGL((k_hash<HASH_KECCAK256>), grid1(n), dim3(BS), 0, c->stream, data, offsets, out32, n, form, c->d_counter);
+    else if (alg == P2E_HASH_SHA256D)
+        hipLaunchKernelGGL((k_hash<HASH_SHA256D>), grid1(n), dim3(BS), 0, c->stream, data, offsets, out32, n, form, c->d_counter);
+    else
+        hipLaunchKernelGGL((k_hash<HASH_SHA256>), grid1(n), dim3(BS), 0, c->stream, data, offsets, out32, n, form, c->d_counter);
+}
+void launch_nonce_rfc6979(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* sk32, uint8_t* k32, size_t n) {
+    if (curve == P2E_CURVE_P256)
+        hipLaunchKernelGGL((k_nonce_rfc6979<ModN256>), grid1(n), dim3(BS), 0, c->stream, msg32, sk32, k32, n);
+    else
+        hipLaunchKernelGGL((k_nonce_rfc6979<ModN>), grid1(n), dim3(BS), 0, c->stream, msg32, sk32, k32, n);
+}
+void launch_eth_address(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err, uint8_t* addr20, size_t n) {
+    if (err)
+        hipLaunchKernelGGL((k_eth_address<true>), grid1(n), dim3(BS), 0, c->stream, pkx32, pky32, err, addr20, n);
+    else
+        hipLaunchKernelGGL((k_eth_address<false>), grid1(n), dim3(BS), 0, c->stream, pkx32, pky32, err, addr20, n);
+}
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static bool hash_batch_too_large(size_t n) {
+    if (n <= ((size_t)1 << 31)) return false;
+    set_error("batch too large for one launch");
+    return true;
+}
+extern "C" long p2e_hash_batch(p2e_ctx* c, int alg, unsigned out_form, const uint8_t* data, const uint64_t* offsets, uint8_t* out32,
+                               size_t n) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!data || !offsets || !out32) {
+        set_error("null pointer (data, offsets and out32 are all required)");
+        return P2E_E_INVALID;
+    }
+    if (alg != P2E_HASH_SHA256 && alg != P2E_HASH_SHA256D && alg != P2E_HASH_KECCAK256) {
+        set_error("unknown alg (P2E_HASH_SHA256, P2E_HASH_SHA256D or P2E_HASH_KECCAK256)");
+        return P2E_E_INVALID;
+    }
+    if (out_form != P2E_DIGEST_BYTES && out_form != P2E_DIGEST_SCALAR) {
+        set_error("unknown out_form (P2E_DIGEST_BYTES or P2E_DIGEST_SCALAR)");
+        return P2E_E_INVALID;
+    }
+    if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    Staged S(c);
+    if (S.host) {   // the staging copy holds data[offsets[0], offsets[n]): the kernel's `data` is that copy moved back by offsets[0]
+        const uint64_t first = offsets[0], last = offsets[n];
+        if (last < first) {
+            set_error("offsets[n] < offsets[0]");
+            return S.done(P2E_E_INVALID);
+        }
+        const uint8_t* d = S.in(data + first, (size_t)(last - first));
+        data = d ? d - first : nullptr;
+    }
+    offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
+    out32 = S.out(out32, n * 32);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_hash(c, alg, out_form, data, offsets, out32, n);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_ecdsa_nonce_rfc6979_batch(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* sk32, uint8_t* k32, size_t n) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !sk32 || !k32) {
+        set_error("null pointer (msg32, sk32 and k32 are all required)");
+        return P2E_E_INVALID;
+    }
+    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
+        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
+        return P2E_E_INVALID;
+    }
+    if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    Staged S(c);
+    msg32 = S.in(msg32, n * 32);
+    sk32 = S.in(sk32, n * 32);
+    k32 = S.out(k32, n * 32);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_nonce_rfc6979(c, curve, msg32, sk32, k32, n);
+    return S.done(finish_call(c));
+}
+// the nonce kernel into the context's scratch, the unchanged signer behind it, then the wipe: all on the caller's stream
+extern "C" long p2e_ecdsa_sign_deterministic_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32,
+                                                   uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !sk32 || !r32 || !s32 || !err) {
+        set_error("null pointer (msg32, sk32, r32, s32 and err are all required; v may be null)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    int chosen = 0;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    msg32 = S.in(msg32, n * 32);
+    sk32 = S.in(sk32, n * 32);
+    r32 = S.out(r32, n * 32);
+    s32 = S.out(s32, n * 32);
+    v = S.out(v, n);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    if (int rc = ensure_scratch(c, n * 32)) return S.done(rc);
+    uint8_t* const k32 = static_cast<uint8_t*>(c->scratch);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_nonce_rfc6979(c, curve, msg32, sk32, k32, n);
+    if (curve == P2E_CURVE_P256) {
+        if (v)
+            launch_sign_recoverable<P256>(c, chosen, table, msg32, sk32, k32, r32, s32, v, n, err);
+        else
+            launch_sign<P256>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
+    } else {
+        if (v)
+            launch_sign_recoverable<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, v, n, err);
+        else
+            launch_sign<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
+    }
+    HIP_TRY(hipMemsetAsync(k32, 0, n * 32, c->stream));   // the nonces are secret: gone once the signer has read them
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_eth_address_batch(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err, uint8_t* addr20,
+                                      size_t n) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!pkx32 || !pky32 || !addr20) {
+        set_error("null pointer (pkx32, pky32 and addr20 are all required; err may be null)");
+        return P2E_E_INVALID;
+    }
+    if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    Staged S(c);
+    pkx32 = S.in(pkx32, n * 32);
+    pky32 = S.in(pky32, n * 32);
+    err = S.in(err, n);
+    addr20 = S.out(addr20, n * 20);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_eth_address(c, pkx32, pky32, err, addr20, n);
     return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)

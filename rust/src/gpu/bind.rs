@@ -172,6 +172,58 @@ pub fn sign_messages_recoverable(ctx: *mut P2eCtx, curve: i32, msgs: &[BigUint],
         .collect()
 }
 
+/// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
+/// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
+/// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).
+pub fn hash_messages(ctx: *mut P2eCtx, alg: i32, messages: &[&[u8]]) -> Result<Vec<BigUint>> {
+    let n = messages.len();
+    let mut offsets = Vec::with_capacity(n + 1);
+    let mut data = Vec::new();
+    offsets.push(0u64);
+    for m in messages {
+        data.extend_from_slice(m);
+        offsets.push(data.len() as u64);
+    }
+    data.push(0); // never read: keeps the pointer of an all-empty batch valid
+    let mut out = vec![0u8; 32 * n];
+    let rc = unsafe { p2e_hash_batch(ctx, alg, P2E_DIGEST_SCALAR, data.as_ptr(), offsets.as_ptr(), out.as_mut_ptr(), n) };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| BigUint::from_bytes_le(&out[32 * i..32 * i + 32])).collect())
+}
+
+/// `sign_messages_recoverable` with the nonces of RFC 6979 (`p2e_ecdsa_sign_deterministic_batch`) instead of the
+/// `rand()` of curve/ecdsa.rs:29-32: the same `(msg, sk)` always gives the same `(r, s, v)`.
+pub fn sign_messages_deterministic(ctx: *mut P2eCtx, curve: i32, msgs: &[BigUint], sks: &[BigUint]) -> Result<Vec<(BigUint, BigUint, u8)>> {
+    let n = msgs.len();
+    ensure!(sks.len() == n);
+    let (msg, sk) = (pack32(msgs.iter().cloned(), n), pack32(sks.iter().cloned(), n));
+    let (mut r, mut s, mut v, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_ecdsa_sign_deterministic_batch(ctx, curve, P2E_SIGN_PLAN_AUTO, msg.as_ptr(), sk.as_ptr(), r.as_mut_ptr(), s.as_mut_ptr(),
+                                           v.as_mut_ptr(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    (0..n)
+        .map(|i| {
+            ensure!(err[i] == 0, "signature {i}: error bits {:#x}", err[i]);
+            Ok((BigUint::from_bytes_le(&r[32 * i..32 * i + 32]), BigUint::from_bytes_le(&s[32 * i..32 * i + 32]), v[i]))
+        })
+        .collect()
+}
+
+/// Ethereum addresses of recovered keys (`p2e_eth_address_batch`): `None` stays `None`, never the address of a zero key.
+pub fn eth_addresses(ctx: *mut P2eCtx, keys: &[Option<(BigUint, BigUint)>]) -> Result<Vec<Option<[u8; 20]>>> {
+    let n = keys.len();
+    let zero = (BigUint::default(), BigUint::default());
+    let pkx = pack32(keys.iter().map(|k| k.as_ref().unwrap_or(&zero).0.clone()), n);
+    let pky = pack32(keys.iter().map(|k| k.as_ref().unwrap_or(&zero).1.clone()), n);
+    let err: Vec<u8> = keys.iter().map(|k| k.is_none() as u8).collect();
+    let mut addr = vec![0u8; 20 * n];
+    let rc = unsafe { p2e_eth_address_batch(ctx, pkx.as_ptr(), pky.as_ptr(), err.as_ptr(), addr.as_mut_ptr(), n) };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| keys[i].as_ref().map(|_| addr[20 * i..20 * i + 20].try_into().unwrap())).collect())
+}
+
 /// One built circuit of `verify_p256_message_circuit` (gadgets/ecdsa.rs:55-78): its hot-path output targets in
 /// registration order (len == 115 557 = `p2e_curve_program_num_cols`) and the library's program object, which carries
 /// the point `precompute_window` drew with `rand()` while THIS circuit was built (gadgets/curve_windowed_mul.rs:57).

@@ -81,6 +81,11 @@ pub const P2E_CURVE_P256: i32 = 1;
 pub const P2E_SIGN_PLAN_AUTO: u32 = 0;
 pub const P2E_SIGN_PLAN_LANE: u32 = 1;
 pub const P2E_SIGN_PLAN_QUAD: u32 = 2;
+pub const P2E_HASH_SHA256: i32 = 0;
+pub const P2E_HASH_SHA256D: i32 = 1;
+pub const P2E_HASH_KECCAK256: i32 = 2;
+pub const P2E_DIGEST_BYTES: u32 = 0;
+pub const P2E_DIGEST_SCALAR: u32 = 1;
 pub const P2E_ERR_POINT_AT_INFINITY: u8 = 64;
 pub const P2E_CP_WINDOWED_MUL: i32 = 1;
 pub const P2E_CP_SCALAR_MUL: i32 = 2;
@@ -198,6 +203,17 @@ extern "C" {
         pkx32: *mut u8, pky32: *mut u8, n: usize, err: *mut u8) -> i64;
     pub fn p2e_ecdsa_sign_recoverable_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, msg32: *const u8, sk32: *const u8,
         k32: *const u8, r32: *mut u8, s32: *mut u8, v: *mut u8, n: usize, err: *mut u8) -> i64;
+
+    // ---- message hashing, RFC 6979 nonces, the deterministic signer and Ethereum addresses (nearest reference counterpart:
+    // curve/ecdsa.rs:25-40 sign_message, which draws its nonce with rand(), :29-32)
+    pub fn p2e_hash_batch(ctx: *mut P2eCtx, alg: i32, out_form: u32, data: *const u8, offsets: *const u64, out32: *mut u8,
+        n: usize) -> i64;
+    pub fn p2e_ecdsa_nonce_rfc6979_batch(ctx: *mut P2eCtx, curve: i32, msg32: *const u8, sk32: *const u8, k32: *mut u8,
+        n: usize) -> i64;
+    pub fn p2e_ecdsa_sign_deterministic_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, msg32: *const u8, sk32: *const u8,
+        r32: *mut u8, s32: *mut u8, v: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_eth_address_batch(ctx: *mut P2eCtx, pkx32: *const u8, pky32: *const u8, err: *const u8, addr20: *mut u8,
+        n: usize) -> i64;
 
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
