@@ -602,6 +602,49 @@ long p2e_ecdsa_sign_deterministic_batch(p2e_ctx *ctx, int curve, unsigned plan, 
 long p2e_eth_address_batch(p2e_ctx *ctx, const uint8_t *pkx32, const uint8_t *pky32, const uint8_t *err /* nullable */,
                            uint8_t *addr20, size_t n);
 
+/* ---- multi-scalar multiplication: out = sum_i k_i P_i over n points of one curve (P2E_CURVE_*), by the bucket
+ * (Pippenger) method; the native many-point sum of curve/curve_msm.rs (msm_parallel / msm_execute) without its
+ * precomputation.  All 32-byte values little-endian, element i at +32 i.
+ *     k32      taken modulo the group order with one conditional subtraction, exactly as p2e_ecdsa_sign_batch takes its
+ *              scalars (reduced, not flagged).
+ *     points   (0, 0) is the neutral element -- the encoding p2e_ecdsa_public_key_batch and p2e_ecdsa_recover_batch write
+ *              for flagged elements: it contributes nothing and is no error.  Any other point with a coordinate >= p, or
+ *              not on the curve, is REJECTED: point_err[i] = 1 (0 for every other i; point_err is nullable), *status =
+ *              P2E_MSM_BAD_POINT, both outputs zero, return value = the number of rejected points.  Nothing is summed
+ *              "without" the rejected points.
+ *     outputs  otherwise the canonical affine coordinates of the sum and P2E_MSM_OK, or, where the sum is the neutral
+ *              element (n == 0 included), zeros and P2E_MSM_NEUTRAL; return value 0.  outx32 / outy32: 32 bytes each,
+ *              4-byte aligned; status: one byte.  The outputs are written by every call that does not fail.
+ *     window_bits   P2E_MSM_WINDOW_AUTO (the library chooses by n) or a width in [P2E_MSM_WINDOW_MIN, P2E_MSM_WINDOW_MAX];
+ *              every width yields the same bytes.  n <= 2^24.
+ * P2E_E_INVALID on a null pointer (other than point_err), an unknown curve, a window_bits outside the above, n > 2^24.
+ * Seven launches on the context's caller stream (csrc/pmsm.hpp: digits and counts, scan, scatter, segment sums, bucket
+ * sums, chunked bucket reduction, window combination with ONE inversion); scratch comes from the context, allocated on
+ * first need, kept, and regrown when a later call needs more.  Host pointers, async mode (the return value then comes
+ * from p2e_sync), the current device and failed calls behave as for the signing calls.
+ * p2e_point_msm_plan (host only, no context): what a call with these arguments will use, as P2E_MSM_PLAN_WORDS 64-bit
+ * words indexed by P2E_MSM_PLAN_*: the window width and the number of windows, buckets per window, the segment length
+ * (a bucket is cut into segments of at most so many entries, one lane each), scratch bytes, and MAX_LANE_ADDITIONS: an
+ * upper bound on the point operations (additions and doublings) any single lane performs in any launch of the call.
+ * It depends on n and the plan only, never on the scalars.  Returns 0, or P2E_E_INVALID as above. */
+#define P2E_MSM_WINDOW_AUTO 0
+#define P2E_MSM_WINDOW_MIN 4
+#define P2E_MSM_WINDOW_MAX 12
+#define P2E_MSM_OK 0
+#define P2E_MSM_NEUTRAL 1     /* the sum is the neutral element: zeros written */
+#define P2E_MSM_BAD_POINT 2   /* at least one input point rejected: zeros written */
+#define P2E_MSM_PLAN_WINDOW_BITS 0
+#define P2E_MSM_PLAN_WINDOWS 1
+#define P2E_MSM_PLAN_BUCKETS 2
+#define P2E_MSM_PLAN_SEG 3
+#define P2E_MSM_PLAN_SCRATCH_BYTES 4
+#define P2E_MSM_PLAN_MAX_LANE_ADDITIONS 5
+#define P2E_MSM_PLAN_WORDS 6
+long p2e_point_msm(p2e_ctx *ctx, int curve, unsigned window_bits, const uint8_t *k32, const uint8_t *px32,
+                   const uint8_t *py32, size_t n, uint8_t *outx32, uint8_t *outy32, uint8_t *status /* 1 byte */,
+                   uint8_t *point_err /* nullable, n bytes */);
+int p2e_point_msm_plan(int curve, size_t n, unsigned window_bits, uint64_t *plan /* P2E_MSM_PLAN_WORDS words */);
+
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */
 int p2e_synth_signatures(uint64_t seed, size_t first, size_t n, uint8_t *msg32, uint8_t *r32, uint8_t *s32,

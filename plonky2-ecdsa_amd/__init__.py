@@ -41,6 +41,8 @@ ERR_NOT_RECOVERABLE = 128    # ecdsa_recover_batch: (r, s, v) names no curve poi
 SIGN_PLAN_AUTO, SIGN_PLAN_LANE, SIGN_PLAN_QUAD = 0, 1, 2   # include/p2e.h P2E_SIGN_PLAN_*
 HASH_SHA256, HASH_SHA256D, HASH_KECCAK256 = 0, 1, 2        # include/p2e.h P2E_HASH_*
 DIGEST_BYTES, DIGEST_SCALAR = 0, 1                         # include/p2e.h P2E_DIGEST_*
+MSM_WINDOW_AUTO, MSM_WINDOW_MIN, MSM_WINDOW_MAX = 0, 4, 12  # include/p2e.h P2E_MSM_WINDOW_*
+MSM_OK, MSM_NEUTRAL, MSM_BAD_POINT = 0, 1, 2               # include/p2e.h P2E_MSM_* (the status byte of point_msm)
 CTX_HOST_POINTERS, CTX_ASYNC, CTX_PHASE_TIMING = 1, 2, 4
 VERIFY_COLS = 82615
 GLV_MUL_COLS = 65243
@@ -82,6 +84,7 @@ EXPORTS = (
     "p2e_ecdsa_public_key_batch", "p2e_ecdsa_sign_batch",
     "p2e_ecdsa_recover_batch", "p2e_ecdsa_sign_recoverable_batch",
     "p2e_hash_batch", "p2e_ecdsa_nonce_rfc6979_batch", "p2e_ecdsa_sign_deterministic_batch", "p2e_eth_address_batch",
+    "p2e_point_msm", "p2e_point_msm_plan",
 )
 
 
@@ -155,7 +158,7 @@ def lib():
         for name in EXPORTS:
             if experimental and not hasattr(_lib, name):
                 continue
-            if name.endswith("_batch") or name in ("p2e_limb_split", "p2e_limb_pack", "p2e_columns_to_rows", "p2e_schedule_describe",
+            if name.endswith("_batch") or name in ("p2e_point_msm", "p2e_limb_split", "p2e_limb_pack", "p2e_columns_to_rows", "p2e_schedule_describe",
                                                    "p2e_schedule_num_cols", "p2e_aux_describe", "p2e_aux_num_cols", "p2e_compact_layout",
                                                    "p2e_columns_compact", "p2e_compact_to_rows", "p2e_curve_program_num_cols",
                                                    "p2e_curve_program_num_aux_cols", "p2e_curve_program_describe",
@@ -303,6 +306,17 @@ def compact_expand(program, narrow, wide):
 
 def aux_num_cols(program: int = PROGRAM_VERIFY) -> int:
     return int(lib().p2e_aux_num_cols(C.c_int(program)))
+
+
+def point_msm_plan(n: int, curve: int = CURVE_SECP256K1, window_bits: int = MSM_WINDOW_AUTO) -> dict:
+    """What Context.point_msm will use for n points (include/p2e.h p2e_point_msm_plan; host only): window_bits, windows,
+    buckets (per window), seg, scratch_bytes, max_lane_additions (a bound on the point operations of one lane in one
+    launch that depends on n and the plan alone)."""
+    buf = (C.c_uint64 * 6)()
+    rc = lib().p2e_point_msm_plan(C.c_int(curve), C.c_size_t(n), C.c_uint(window_bits), buf)
+    if rc:
+        raise P2EError(f"p2e_point_msm_plan failed ({rc}): {lib().p2e_last_error().decode()}")
+    return dict(zip(("window_bits", "windows", "buckets", "seg", "scratch_bytes", "max_lane_additions"), [int(v) for v in buf]))
 
 
 def synth_signatures(seed: int, n: int, first: int = 0):
@@ -1058,6 +1072,24 @@ class Context:
         bad = self._check(self._L.p2e_ecdsa_recover_batch(self._h, C.c_int(curve), _ptr(msg), _ptr(r), _ptr(s), _ptr(v), _ptr(pkx),
                                                           _ptr(pky), C.c_size_t(n), _ptr(err)))
         return pkx, pky, err, bad
+
+    # ---- the many-point sum (include/p2e.h p2e_point_msm) ---------------------------------------------------------------
+    def point_msm(self, k, px, py, curve=CURVE_SECP256K1, window_bits=MSM_WINDOW_AUTO, outx=None, outy=None, status=None,
+                  point_err=None, want_point_err=True, n=None):
+        """sum_i k[i] * (px[i], py[i]) by the bucket method; k, px, py are (n, 32) little-endian, k taken modulo the group
+        order, (0, 0) the neutral element.  (outx (32,), outy (32,), status (1,), point_err (n,) or None, rejected count):
+        status MSM_OK and the canonical affine sum; MSM_NEUTRAL and zeros; MSM_BAD_POINT, zeros and point_err[i] = 1 where
+        a point is not on the curve (nothing is summed without them).  want_point_err=False passes no point_err; n: the
+        number of points where it is not k's first dimension (n = 0 still needs buffers that are not empty)."""
+        n = self._shape(k)[0] if n is None else n
+        outx = outx if outx is not None else self._packed(1)[0]
+        outy = outy if outy is not None else self._packed(1)[0]
+        status = status if status is not None else self._vec(1, np.uint8)
+        if point_err is None and want_point_err:
+            point_err = self._vec(max(n, 1), np.uint8)[:n]
+        bad = self._check(self._L.p2e_point_msm(self._h, C.c_int(curve), C.c_uint(window_bits), _ptr(k), _ptr(px), _ptr(py),
+                                                C.c_size_t(n), _ptr(outx), _ptr(outy), _ptr(status), _ptr(point_err)))
+        return outx, outy, status, point_err, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

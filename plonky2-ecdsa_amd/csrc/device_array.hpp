@@ -45,6 +45,17 @@ public:
         *this = std::move(fresh);
         return hipSuccess;
     }
+    // Replaces the contents by `count` uninitialised elements (scratch); on failure the array is empty, as for upload().
+    hipError_t alloc(size_t count) {
+        *this = DeviceArray();
+        if (!count) return hipSuccess;
+        hipError_t e = hipMalloc(&p_, sizeof(T) * count);
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            (void)hipGetLastError();
+        }
+        return e;
+    }
     hipError_t upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
 };
 

@@ -23,6 +23,7 @@
 #include "curve_program.hpp"
 #include "sign.hpp"
 #include "recover.hpp"
+#include "pmsm.hpp"
 #include "hash.hpp"
 
 using namespace p2e;
@@ -597,6 +598,8 @@ struct p2e_ctx {
     DeviceProgram progs[2];
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
+    DeviceArray<unsigned char> d_msm;   // scratch of p2e_point_msm (pmsm.hpp MsmPlan): allocated on first need, kept, regrown
+    size_t msm_bytes = 0;
     unsigned long long* d_counter = nullptr;
     unsigned long long* h_counter = nullptr;  // pinned
     hipEvent_t ev[6] = {};   // [0],[1] around k_scalar, [5] end of the call (2..4 unused)
@@ -2623,6 +2626,106 @@ extern "C" long p2e_eth_address_batch(p2e_ctx* c, const uint8_t* pkx32, const ui
     c->have_phases = false;
     ZERO_COUNTER(c);
     launch_eth_address(c, pkx32, pky32, err, addr20, n);
+    return S.done(finish_call(c));
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// bucket-method multi-scalar multiplication (pmsm.hpp)
+// ====================================================================================================
+// the seven launches of one call on the caller's stream; defined in part 1 beside the hashing kernels, called from part 0
+template <class CV>
+void launch_msm(p2e_ctx* c, const MsmArgs& a);
+#if P2E_HAS(1)
+template <class CV>
+void launch_msm(p2e_ctx* c, const MsmArgs& a) {
+    const dim3 bs(BS);
+    if (a.n) hipLaunchKernelGGL((k_msm_digits<CV>), grid1(a.n), bs, 0, c->stream, a);
+    hipLaunchKernelGGL((k_msm_scan<0>), dim3(1), dim3(MSM_SCAN_LANES), 0, c->stream, a);
+    if (a.n) {
+        hipLaunchKernelGGL((k_msm_scatter<CV>), grid1(a.n), bs, 0, c->stream, a);
+        hipLaunchKernelGGL((k_msm_segment<CV>), grid1(a.max_segments), bs, 0, c->stream, a);
+    }
+    hipLaunchKernelGGL((k_msm_bucket<CV>), grid1(a.entries), bs, 0, c->stream, a);
+    hipLaunchKernelGGL((k_msm_chunk<CV>), grid1((size_t)a.windows * a.chunks), bs, 0, c->stream, a);
+    hipLaunchKernelGGL((k_msm_final<CV>), dim3(1), dim3(MSM_FINAL_LANES), 0, c->stream, a);
+}
+template void launch_msm<Secp256k1>(p2e_ctx*, const MsmArgs&);
+template void launch_msm<P256>(p2e_ctx*, const MsmArgs&);
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static bool msm_bad_args(int curve, size_t n, unsigned window_bits) {
+    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
+        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
+        return true;
+    }
+    if (window_bits != P2E_MSM_WINDOW_AUTO && (window_bits < P2E_MSM_WINDOW_MIN || window_bits > P2E_MSM_WINDOW_MAX)) {
+        set_error("window_bits outside P2E_MSM_WINDOW_AUTO, [P2E_MSM_WINDOW_MIN, P2E_MSM_WINDOW_MAX]");
+        return true;
+    }
+    if (n > MSM_MAX_N) {
+        set_error("batch too large for one sum (2^24 points)");
+        return true;
+    }
+    return false;
+}
+static_assert(P2E_MSM_WINDOW_MIN == MSM_WINDOW_MIN && P2E_MSM_WINDOW_MAX == MSM_WINDOW_MAX, "include/p2e.h and pmsm.hpp");
+static_assert(P2E_MSM_OK == MSM_OK && P2E_MSM_NEUTRAL == MSM_NEUTRAL && P2E_MSM_BAD_POINT == MSM_BAD_POINT, "include/p2e.h and pmsm.hpp");
+extern "C" int p2e_point_msm_plan(int curve, size_t n, unsigned window_bits, uint64_t* plan) {
+    if (!plan) {
+        set_error("null pointer (plan is required)");
+        return P2E_E_INVALID;
+    }
+    if (msm_bad_args(curve, n, window_bits)) return P2E_E_INVALID;
+    const MsmPlan p = msm_plan(n, window_bits == P2E_MSM_WINDOW_AUTO ? msm_auto_window(n) : window_bits);
+    plan[P2E_MSM_PLAN_WINDOW_BITS] = p.c;
+    plan[P2E_MSM_PLAN_WINDOWS] = p.windows;
+    plan[P2E_MSM_PLAN_BUCKETS] = p.buckets;
+    plan[P2E_MSM_PLAN_SEG] = p.seg;
+    plan[P2E_MSM_PLAN_SCRATCH_BYTES] = p.total;
+    plan[P2E_MSM_PLAN_MAX_LANE_ADDITIONS] = p.max_lane_additions;
+    return 0;
+}
+extern "C" long p2e_point_msm(p2e_ctx* c, int curve, unsigned window_bits, const uint8_t* k32, const uint8_t* px32, const uint8_t* py32,
+                              size_t n, uint8_t* outx32, uint8_t* outy32, uint8_t* status, uint8_t* point_err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!k32 || !px32 || !py32 || !outx32 || !outy32 || !status) {
+        set_error("null pointer (k32, px32, py32, outx32, outy32 and status are all required; point_err may be null)");
+        return P2E_E_INVALID;
+    }
+    if (msm_bad_args(curve, n, window_bits)) return P2E_E_INVALID;
+    const MsmPlan P = msm_plan(n, window_bits == P2E_MSM_WINDOW_AUTO ? msm_auto_window(n) : window_bits);
+    Staged S(c);
+    k32 = S.in(k32, n * 32);
+    px32 = S.in(px32, n * 32);
+    py32 = S.in(py32, n * 32);
+    outx32 = S.out(outx32, 32);
+    outy32 = S.out(outy32, 32);
+    status = S.out(status, 1);
+    point_err = S.out(point_err, n);
+    if (S.rc) return S.done(S.rc);
+    if (P.total > c->msm_bytes) {
+        HIP_TRY(hipStreamSynchronize(c->stream));   // an earlier asynchronous call may still use the block that goes
+        c->msm_bytes = 0;
+        hipError_t e = c->d_msm.alloc(P.total);
+        if (e != hipSuccess) {
+            set_error("scratch allocation of " + std::to_string(P.total) + " bytes failed: " + hipGetErrorString(e));
+            return S.done(P2E_E_NOMEM);
+        }
+        c->msm_bytes = P.total;
+    }
+    MsmArgs a = msm_args(P, c->d_msm.get());
+    a.k32 = k32, a.px32 = px32, a.py32 = py32;
+    a.outx32 = outx32, a.outy32 = outy32, a.status = status, a.point_err = point_err;
+    a.counter = c->d_counter;
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    HIP_TRY(hipMemsetAsync(c->d_msm.get(), 0, P.o_off, c->stream));   // meta, count, cursor
+    if (curve == P2E_CURVE_P256)
+        launch_msm<P256>(c, a);
+    else
+        launch_msm<Secp256k1>(c, a);
     return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)

@@ -172,6 +172,27 @@ pub fn sign_messages_recoverable(ctx: *mut P2eCtx, curve: i32, msgs: &[BigUint],
         .collect()
 }
 
+/// The sum `Σ k_i · P_i` of a batch of points (`p2e_point_msm`, host-pointer context), the many-point sum of
+/// curve/curve_msm.rs `msm_parallel`.  A point `None` (or `(0, 0)`) is the neutral element and contributes nothing.
+/// `Ok(None)`: the sum is the neutral element.  `Err`: the call failed, or some point is not on the curve (the message
+/// names the first one); nothing is summed without the rejected points.
+pub fn point_msm(ctx: *mut P2eCtx, curve: i32, scalars: &[BigUint], points: &[Option<(BigUint, BigUint)>]) -> Result<Option<(BigUint, BigUint)>> {
+    let n = scalars.len();
+    ensure!(points.len() == n);
+    let zero = (BigUint::default(), BigUint::default());
+    let k = pack32(scalars.iter().cloned(), n);
+    let px = pack32(points.iter().map(|p| p.as_ref().unwrap_or(&zero).0.clone()), n);
+    let py = pack32(points.iter().map(|p| p.as_ref().unwrap_or(&zero).1.clone()), n);
+    let (mut outx, mut outy, mut status, mut point_err) = ([0u8; 32], [0u8; 32], 0u8, vec![0u8; n]);
+    let rc = unsafe {
+        p2e_point_msm(ctx, curve, P2E_MSM_WINDOW_AUTO, k.as_ptr(), px.as_ptr(), py.as_ptr(), n, outx.as_mut_ptr(), outy.as_mut_ptr(),
+                      &mut status, point_err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    ensure!(status != P2E_MSM_BAD_POINT, "{rc} points are not on the curve, the first at index {:?}", point_err.iter().position(|&e| e != 0));
+    Ok((status == P2E_MSM_OK).then(|| (BigUint::from_bytes_le(&outx), BigUint::from_bytes_le(&outy))))
+}
+
 /// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
 /// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
 /// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).

@@ -86,6 +86,19 @@ pub const P2E_HASH_SHA256D: i32 = 1;
 pub const P2E_HASH_KECCAK256: i32 = 2;
 pub const P2E_DIGEST_BYTES: u32 = 0;
 pub const P2E_DIGEST_SCALAR: u32 = 1;
+pub const P2E_MSM_WINDOW_AUTO: u32 = 0;
+pub const P2E_MSM_WINDOW_MIN: u32 = 4;
+pub const P2E_MSM_WINDOW_MAX: u32 = 12;
+pub const P2E_MSM_OK: u8 = 0;
+pub const P2E_MSM_NEUTRAL: u8 = 1;
+pub const P2E_MSM_BAD_POINT: u8 = 2;
+pub const P2E_MSM_PLAN_WINDOW_BITS: usize = 0;
+pub const P2E_MSM_PLAN_WINDOWS: usize = 1;
+pub const P2E_MSM_PLAN_BUCKETS: usize = 2;
+pub const P2E_MSM_PLAN_SEG: usize = 3;
+pub const P2E_MSM_PLAN_SCRATCH_BYTES: usize = 4;
+pub const P2E_MSM_PLAN_MAX_LANE_ADDITIONS: usize = 5;
+pub const P2E_MSM_PLAN_WORDS: usize = 6;
 pub const P2E_ERR_POINT_AT_INFINITY: u8 = 64;
 pub const P2E_CP_WINDOWED_MUL: i32 = 1;
 pub const P2E_CP_SCALAR_MUL: i32 = 2;
@@ -214,6 +227,12 @@ extern "C" {
         r32: *mut u8, s32: *mut u8, v: *mut u8, n: usize, err: *mut u8) -> i64;
     pub fn p2e_eth_address_batch(ctx: *mut P2eCtx, pkx32: *const u8, pky32: *const u8, err: *const u8, addr20: *mut u8,
         n: usize) -> i64;
+
+    // ---- bucket-method multi-scalar multiplication sum k_i P_i (curve/curve_msm.rs msm_parallel / msm_execute); `plan`:
+    // P2E_MSM_PLAN_WORDS words indexed by P2E_MSM_PLAN_*
+    pub fn p2e_point_msm(ctx: *mut P2eCtx, curve: i32, window_bits: u32, k32: *const u8, px32: *const u8, py32: *const u8,
+        n: usize, outx32: *mut u8, outy32: *mut u8, status: *mut u8, point_err: *mut u8) -> i64;
+    pub fn p2e_point_msm_plan(curve: i32, n: usize, window_bits: u32, plan: *mut u64) -> i32;
 
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
