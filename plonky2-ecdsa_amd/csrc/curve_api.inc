@@ -1,14 +1,14 @@
-// Curve programs (curves.hpp, curve_program.hpp): kernels, launch plan and C ABI.  Included at the end of p2e_hip.hip
+// Curve programs (curves.hpp, curve_program.hpp): kernels, launcher and C ABI.  Included at the end of p2e_hip.hip
 // (same translation unit: it shares the context, the staging helper and the finalisation kernel).
 //
-// Launch plan: the op list is cut into pieces; piece k runs  chain (phase A, chain stream)  ->  batch inversion
+// Launch plan (launch_plan.hpp choose_curve / build_curve): the op list is cut into pieces; piece k runs  chain (phase A, chain stream)  ->  batch inversion
 // (phase B, second stream)  ->  expansion (phase C, caller's stream), so that the HBM-bound expansion of finished pieces
 // runs underneath the chains and inversions of later ones, exactly as in the built-in programs.  The per-signature
 // window table is its own piece, inverted on the chain stream itself; every later piece reads it in affine form (mixed
-// additions).  Batches of >= cp_runs_min_n (49 152): the windowed loop in pieces of CP_RUN_OPS ops expanded as runs
+// additions).  Batches of >= cp_runs_min_n (49 152): the windowed loop in pieces of plan::CP_RUN_OPS ops expanded as runs
 // (body_expand_run<.., 4>, the MSM program's 2-doubling loop body_expand_run<.., 2>), the fixed-base windows of the
 // verifier (on a second chain stream) and of the fixed-base program as one run per signature (body_expand_fb_run);
-// smaller batches: pieces of <= CP_PIECE_OPS ops expanded op by op.
+// smaller batches: pieces of <= plan::CP_PIECE_OPS ops expanded op by op.
 
 #if P2E_HAS(2) || P2E_HAS(3)
 template <class CV, int MODE>
@@ -108,12 +108,7 @@ struct p2e_curve_program {
     PassTables tab;
     DeviceArray<U256> d_constv;   // constants by source id: points at 2c / 2c + 1, scalar constants from AUX_GCONST_BASE
 };
-constexpr int CP_PIECE_OPS = 32;
-constexpr int CP_PIECE_OPS_QUAD = 45;   // four-lane plan: 9 windows of the windowed loop per piece
-constexpr int CP_TAIL_OPS_QUAD = 17;    // ... and a last piece of 3 windows + the trailing adds
-constexpr int CP_RUN_OPS = 30;   // ops per expansion run of a loop: 6 windows of the windowed loop, 10 digits of the MSM
-// loop iterations per expansion run (the op stride of an iteration is its doublings + the conditional add)
-inline int cp_run_iters(const Program& G) { return CP_RUN_OPS / (G.loop_dbls + 1); }
+using plan::cp_run_iters;   // loop iterations per expansion run: the run marks of d_ops_runs (launch_plan.hpp)
 
 // the pipeline of one curve: defined (and explicitly instantiated) in parts 2 and 3
 template <class CV>
@@ -276,54 +271,67 @@ extern "C" int p2e_curve_program_const(const p2e_curve_program* P, uint32_t id, 
 
 #if P2E_HAS(2) || P2E_HAS(3)
 template <class CV>
+struct CurveKernels {
+    static constexpr bool has_rows = false;   // no curve plan walks a table as rows
+    static int loop_stride(const Program& G) { return G.loop_dbls + 1; }   // the loop's doublings + the conditional add
+    template <int MODE>
+    static void scalar(dim3 g, hipStream_t st, const Program& G, const Buffers& B, size_t first) {
+        hipLaunchKernelGGL((kc_scalar<CV, MODE>), g, dim3(BS), 0, st, G, B, first);
+    }
+    // (the curve programs' chains never continue a prefix and their inversion batches always have phase A's)
+    static void chain_lane(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int table_affine, int) {
+        hipLaunchKernelGGL((kc_chains<CV>), g, dim3(BS), 0, st, G, B, lo, hi, table_affine);
+    }
+    static void chain_quad(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int table_affine, int) {
+        hipLaunchKernelGGL((kc_chains_quad<CV>), g, dim3(BS), 0, st, G, B, lo, hi, table_affine);
+    }
+    static void binv(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int) {
+        hipLaunchKernelGGL((kc_batch_inv<CV>), g, dim3(BS), 0, st, G, B, lo, hi);
+    }
+    static void binv_split(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int, int split_log2) {
+        hipLaunchKernelGGL((kc_batch_inv_split<CV>), g, dim3(BS), 0, st, G, B, lo, hi, split_log2);
+    }
+    template <int MODE>
+    static void expand(dim3 g, unsigned lds, hipStream_t st, const Program& G, const Buffers& B, int lo, size_t first) {
+        hipLaunchKernelGGL((kc_expand<CV, MODE>), g, dim3(BS), lds, st, G, B, lo, first);
+    }
+    template <int MODE>
+    static void expand_runs(dim3 g, unsigned lds, hipStream_t st, const Program& G, const Buffers& B, int it0, int run_iters, int it1,
+                            size_t first) {
+        if (G.loop_dbls == 2)
+            hipLaunchKernelGGL((kc_expand_runs2<CV, MODE>), g, dim3(BS), lds, st, G, B, it0, run_iters, it1, first);
+        else
+            hipLaunchKernelGGL((kc_expand_runs<CV, MODE>), g, dim3(BS), lds, st, G, B, it0, run_iters, it1, first);
+    }
+    template <int MODE>
+    static void expand_fb_run(dim3 g, unsigned lds, hipStream_t st, const Program& G, const Buffers& B, int t_after, size_t first) {
+        hipLaunchKernelGGL((kc_expand_fb_run<CV, MODE>), g, dim3(BS), lds, st, G, B, t_after, first);
+    }
+};
+
+// Stage, bind, build the plan, issue (as run_program).
+template <class CV>
 long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg, const uint8_t* r, const uint8_t* s,
                        const uint8_t* pkx, const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err,
                        uint8_t* valid, bool verify_only, uint32_t* narrow, size_t ldn, uint64_t* wide, size_t ldw,
                        const uint8_t* qx, const uint8_t* qy) {
+    const CallSwitches sw = read_call_switches(getenv);
     const bool compact = cols == nullptr && !verify_only;
     const Program& G = P->H.sb.prog;
-    const std::vector<OpDesc>& h_ops = P->H.sb.ops;
     Staged S(c);
-    msg = S.in(msg, n * 32);
-    r = S.in(r, n * 32);
-    s = S.in(s, n * 32);
-    pkx = S.in(pkx, n * 32);
-    pky = S.in(pky, n * 32);
-    qx = S.in(qx, n * 32);
-    qy = S.in(qy, n * 32);
-    if (compact) {
-        narrow = S.out(narrow, (size_t)P->compact.num_narrow * ldn * 4);
-        wide = S.out(wide, (size_t)P->compact.num_wide * ldw * 8);
-    } else if (!verify_only) {
-        cols = S.out(cols, (size_t)G.num_cols * ld * 8);
-    }
-    err = S.out(err, n);
-    valid = S.out(valid, n);
-    if (S.rc) return S.done(S.rc);
-    ScratchLayout L = scratch_layout(G, n);
-    int rc = ensure_scratch(c, L.total);
-    if (rc) return S.done(rc);
-    Buffers B{};
-    B.msg = msg;
-    B.r = r;
-    B.s = s;
-    B.pkx = pkx;
-    B.pky = pky;
-    B.qx = qx;
-    B.qy = qy;
-    B.sink = Sink{cols, ld, narrow, ldn, wide, ldw, P->tab.wide_before.get()};
-    B.n = n;
-    L.bind(B, (char*)c->scratch);
+    FusedIO io{{msg, r, s, pkx, pky, qx, qy}, cols, ld, narrow, ldn, wide, ldw, err, valid};
+    Buffers B;
+    if (long rc = stage_fused(c, S, G, P->compact, P->tab.wide_before.get(), compact, verify_only, n, io, B)) return S.done(rc);
     B.cpts = P->d_cpts.get();
     B.fbtab = P->d_fbtab.get();
     B.ops = P->d_ops.get();
     ZERO_COUNTER(c);
     c->seg_blocks.clear();
-    const unsigned gx = (unsigned)((n + BS - 1) / BS);
     if (verify_only) {
         // the circuit's verdict alone (the P-256 counterpart of p2e_ecdsa_verify_batch): scalar phase without emission,
         // the fixed-base chain beside the windowed chain in Jacobian coordinates (no batch inversion, no expansion: the
         // window table stays Jacobian), the final add, r == x on its Jacobian result
+        const unsigned gx = (unsigned)((n + BS - 1) / BS);
         const int fb_end = G.fb_begin + G.fb_windows + 1;
         hipLaunchKernelGGL((kc_scalar<CV, 4>), dim3(gx), dim3(BS), 0, c->stream, G, B, (size_t)0);
         HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
@@ -334,281 +342,22 @@ long run_curve_program(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* ms
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fixed, 0));
         hipLaunchKernelGGL((kc_chains<CV>), dim3(gx), dim3(BS), 0, c->stream, G, B, G.num_ops - 1, G.num_ops, 0);
         hipLaunchKernelGGL((kc_verify_check<CV>), dim3(gx), dim3(BS), 0, c->stream, G, B);
-        hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, B.err, B.valid, err, valid, n, c->d_counter);
+        hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, B.err, B.valid, io.err, io.valid, n, c->d_counter);
         c->have_phases = false;
         return S.done(finish_call(c));
     }
-    // paired stores need full workgroups, even column strides and matrices aligned to two elements
-    const bool wide_ok = !narrow_stores_forced() &&
-                         (compact ? (ldn % 2 == 0 && ldw % 2 == 0 && (reinterpret_cast<uintptr_t>(narrow) & 7) == 0 &&
-                                     (reinterpret_cast<uintptr_t>(wide) & 15) == 0)
-                                  : (ld % 2 == 0 && (reinterpret_cast<uintptr_t>(cols) & 15) == 0));
-    // kernel variant per launch: EmitOf<MODE>, bit 0 = paired stores, bit 1 = compact container
-#define CP_LAUNCH(KERNEL, PAIRED, GRID, STREAM, ...)                                                             \
-    do {                                                                                                          \
-        if (compact) {                                                                                            \
-            if (PAIRED) hipLaunchKernelGGL((KERNEL<CV, 3>), GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);      \
-            else hipLaunchKernelGGL((KERNEL<CV, 2>), GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);             \
-        } else {                                                                                                  \
-            if (PAIRED) hipLaunchKernelGGL((KERNEL<CV, 1>), GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);      \
-            else hipLaunchKernelGGL((KERNEL<CV, 0>), GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);             \
-        }                                                                                                         \
-    } while (0)
-    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
-    const unsigned gx_wide = (unsigned)(n_wide / BS);
-    const unsigned gx_tail = (unsigned)((n - n_wide + BS - 1) / BS);
-    // pieces of the op list: one chain kernel + one inversion batch + the expansion launches each
-    struct Piece {
-        int lo, hi;          // ops of phases A and B
-        hipStream_t chain;   // chain stream
-        bool table, wait_fb; // the per-signature window table; needs the fixed-base chain (the final add)
-        bool fb_run;         // phase C: the fixed-base windows as one run ...
-        int it0, it1;        // ... loop iterations as runs ...
-        int s_lo, s_hi;      // ... ops one by one
-    };
-    Piece pieces[p2e_ctx::MAX_SEG];
-    int np = 0;
-    int tb = -1, te = -1;
-    if (G.cp_table_ops > 0) {   // the table = the ops the msm_tab slots refer to
-        te = 0;
-        for (int k = 1; k < 16; k++) te = std::max(te, (int)ref_id(G.msm_tab[k]) + 1);
-        tb = te - G.cp_table_ops;
+    const plan::CurveParams cp = plan::choose_curve(G, c->tune, n, P->d_ops_runs.get() != nullptr, stream_layout(c),
+                                                    (c->flags & P2E_CTX_PHASE_TIMING) != 0, sw);
+    plan::Plan pl;
+    if (!plan::build_curve(G, cp, pl)) {
+        set_plan_error(pl.error, "curve program", cp.quad);
+        return S.done(P2E_E_INVALID);
     }
-    bool overflow = false;   // more pieces than the plan holds: the call fails (never a silently shorter op list)
-    auto add = [&](Piece pc) {
-        if (pc.hi <= pc.lo) return;
-        if (np < p2e_ctx::MAX_SEG)
-            pieces[np++] = pc;
-        else
-            overflow = true;
-    };
-    // small batches: the chains are pure latency (429 dependent ops in the P-256 verifier): four lanes per signature walk
-    // them, every inversion batch is cut into 2^binv_split_log2 sub-ranges, and the expansion kernels ask for dynamic LDS
-    // they do not use so that one workgroup per CU leaves the register file to the chain waves (as the built-in programs'
-    // four-lane plan, DESIGN.md section 5a)
-    const bool runs = P->d_ops_runs.get() && n >= c->tune.cp_runs_min_n && !getenv("P2E_CP_NO_RUNS");
-    const bool quad = !runs && n <= c->tune.cp_quad_max_n && !getenv("P2E_CP_NO_QUAD");
-    // ops per piece: the expansions are nowhere near the critical path of a small batch (the chain is), so its pieces are
-    // longer: fewer launches and inversion batches on the chain's way
-    int piece_ops = quad ? CP_PIECE_OPS_QUAD : CP_PIECE_OPS, tail_ops_quad = CP_TAIL_OPS_QUAD;
-    if (const char* env = getenv("P2E_CP_PIECE_OPS_QUAD")) {   // tuning knobs (tools/bench_curve_programs.py sweeps)
-        const int v = atoi(env);
-        if (quad && v >= 8 && v <= 200) piece_ops = v;
-    }
-    if (const char* env = getenv("P2E_CP_TAIL_OPS_QUAD")) {
-        const int v = atoi(env);
-        if (v >= 0 && v <= 100) tail_ops_quad = v;
-    }
-    auto cut = [&](int lo, int hi) {   // chunks of <= piece_ops ops, expanded op by op
-        if (hi <= lo) return;
-        const int chunks = (hi - lo + piece_ops - 1) / piece_ops;
-        for (int k = 0; k < chunks; k++) {
-            const int a = lo + (int)((long long)(hi - lo) * k / chunks), b = lo + (int)((long long)(hi - lo) * (k + 1) / chunks);
-            add(Piece{a, b, c->st_msm, false, false, false, 0, 0, a, b});
-        }
-    };
-    // large batches: the windowed loop as runs and the fixed-base windows as one run (a run is walked by ONE lane, so
-    // below cp_runs_min_n the SIMDs are better filled op by op, as in the built-in programs); the verifier's fixed-base
-    // chain then runs beside the windowed chain on its own stream
-    bool fb_beside = false;
-    unsigned emit_lds = 0;   // dynamic LDS of the expansion kernels (the scalar phase launches with none)
-    const unsigned gx4 = (unsigned)((4 * n + BS - 1) / BS);
-    const int stride = G.loop_dbls + 1, run_iters = cp_run_iters(G);   // ops per loop iteration, iterations per run
-    if (runs && G.msm_loop_iters == 0) {
-        // the fixed-base program: its windows as one run per signature, then the unblinding add (one piece)
-        B.ops = P->d_ops_runs.get();
-        add(Piece{G.fb_begin, G.num_ops, c->st_msm, false, false, true, 0, 0, G.fb_begin + G.fb_windows, G.num_ops});
-        if (overflow || G.fb_begin != 0 || np != 1) {
-            set_error("curve program does not have the shape the run plan expects");
-            return S.done(P2E_E_INVALID);
-        }
-    } else if (runs) {
-        B.ops = P->d_ops_runs.get();
-        const int lb = G.msm_loop_begin, iters = G.msm_loop_iters, le = lb + stride * iters;
-        int fb_end = 0;
-        if (G.fb_begin >= 0) {   // verifier: fixed-base windows + unblinding add, one piece on the second chain stream
-            fb_end = G.fb_begin + G.fb_windows + 1;
-            add(Piece{G.fb_begin, fb_end, c->st_fixed, false, false, true, 0, 0, G.fb_begin + G.fb_windows, fb_end});
-        }
-        add(Piece{tb, te, c->st_msm, true, false, false, 0, 0, tb, te});
-        for (int it = 0; it < iters; it += run_iters) {
-            const int it1 = std::min(it + run_iters, iters);
-            Piece pc{lb + stride * it, lb + stride * it1, c->st_msm, false, false, false, it, it1, 0, 0};
-            if (it1 == iters) {   // the last run takes the trailing ops (unblinding add, the verifier's final add)
-                pc.hi = G.num_ops;
-                pc.s_lo = le;
-                pc.s_hi = G.num_ops;
-                pc.wait_fb = G.fb_begin >= 0;
-            }
-            add(pc);
-        }
-        if (overflow || tb != fb_end || np == 0 || pieces[np - 1].hi != G.num_ops) {
-            set_error("curve program does not have the shape the run plan expects");
-            return S.done(P2E_E_INVALID);
-        }
-    } else {
-        if (tb >= 0) {
-            // the verifier's fixed-base chain (67 ops) does not depend on the windowed chain: its pieces go to the second
-            // chain stream and run beside the table / loop pieces; only the final add needs both (P2E_CP_FB_SERIAL=1: one
-            // chain stream, as in round 2)
-            fb_beside = G.fb_begin == 0 && tb == G.fb_begin + G.fb_windows + 1 && !getenv("P2E_CP_FB_SERIAL");
-            const int first_fb = np;
-            cut(0, tb);
-            if (fb_beside)
-                for (int k = first_fb; k < np; k++) pieces[k].chain = c->st_fixed;
-            add(Piece{tb, te, c->st_msm, true, false, false, 0, 0, tb, te});
-            // four-lane plan: a SHORT last piece -- its inversion batch and expansion are the exposed tail of the call
-            const int tail_ops = quad && G.num_ops - te > 2 * tail_ops_quad ? tail_ops_quad : 0;
-            cut(te, G.num_ops - tail_ops);
-            cut(G.num_ops - tail_ops, G.num_ops);
-            if (fb_beside && np > 0) pieces[np - 1].wait_fb = true;
-        } else {
-            cut(0, G.num_ops);
-        }
-        if (overflow || np == 0 || pieces[np - 1].hi != G.num_ops) {
-            set_error("curve program has too many pieces for the launch plan (at most " + std::to_string(p2e_ctx::MAX_SEG) + ")" +
-                      std::string(quad ? ": raise P2E_CP_PIECE_OPS_QUAD" : ""));
-            return S.done(P2E_E_INVALID);
-        }
-    }
-    c->n_seg = np;
-    c->n_expand = 0;
-    seg_begin_call(c, h_ops, (u32)G.num_cols);
-    if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    if (gx_wide) CP_LAUNCH(kc_scalar, true, dim3(gx_wide), c->stream, G, B, (size_t)0);
-    if (gx_tail) CP_LAUNCH(kc_scalar, false, dim3(gx_tail), c->stream, G, B, n_wide);
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->st_msm, c->ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(c->st_fixed, c->ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(c->st_binv, c->ev_fork, 0));
-    if (fb_beside || quad) HIP_TRY(hipStreamWaitEvent(c->st_c2, c->ev_fork, 0));
-    auto cols_of = [&](int lo, int hi) {
-        double cw = 0;
-        for (int t = lo; t < hi; t++) cw += h_ops[t].kind == OP_DBL ? COLS_DBL : h_ops[t].kind == OP_CADD ? COLS_CADD : COLS_ADD;
-        return cw;
-    };
-    // phases A and B of every piece
-    bool table_done = false;
-    int table_piece = -1, pieces_after_table = 0;
-    for (int k = 0; k < np; k++) {
-        const Piece& pc = pieces[k];
-        // four-lane plan: the table's inversion batch runs OFF the chain stream and the first piece after the table reads
-        // the table in Jacobian form (one level more per window addition) instead of waiting 0.3 ms for it; from the
-        // second piece on the chain waits for the inversion (long done) and reads the table in affine form
-        if (quad && table_piece >= 0 && pc.chain == c->st_msm && !pc.table) {
-            if (pieces_after_table == 1) {
-                HIP_TRY(hipStreamWaitEvent(c->st_msm, c->ev_binv[table_piece], 0));
-                table_done = true;
-            }
-            pieces_after_table++;
-        }
-        if (pc.wait_fb) HIP_TRY(hipStreamWaitEvent(pc.chain, c->ev_fixed, 0));
-        if (quad)
-            hipLaunchKernelGGL((kc_chains_quad<CV>), dim3(gx4), dim3(BS), 0, pc.chain, G, B, pc.lo, pc.hi, (table_done && pc.chain == c->st_msm) ? 1 : 0);
-        else
-            hipLaunchKernelGGL((kc_chains<CV>), dim3(gx), dim3(BS), 0, pc.chain, G, B, pc.lo, pc.hi, (table_done && pc.chain == c->st_msm) ? 1 : 0);
-        HIP_TRY(hipEventRecord(c->ev_piece[k], pc.chain));
-        if (pc.chain == c->st_fixed) HIP_TRY(hipEventRecord(c->ev_fixed, c->st_fixed));
-        // the table's inversion runs on the chain stream itself (everything after it reads the table affine), the
-        // fixed-base piece's behind its own chain, the others on the inversion stream (on the fixed-base stream a
-        // verifier's first windowed pieces would queue behind that 67-op chain)
-        // (op-by-op plan: the inversion batches of consecutive pieces alternate between two streams, as in the mid-size plan
-        // of the built-in programs -- they are latency-bound and would otherwise queue behind each other)
-        const bool alt = !runs && n < c->tune.binv_alt_max_n && !getenv("P2E_CP_NO_ALT_B");
-        // (fixed-base chain beside the windowed one: st_fixed carries chain pieces, so the inversion batches alternate
-        // between the inversion stream and the otherwise idle second expansion stream)
-        // (four-lane plan: the table's batch goes to the second expansion stream, which has nothing queued yet -- the first
-        // piece after the table's successor waits for it --, the fixed-base pieces' batches to the inversion stream)
-        hipStream_t st_b = pc.table ? (quad ? c->st_c2 : c->st_msm)
-                           : (fb_beside && quad && pc.chain == c->st_fixed) ? c->st_binv
-                           : fb_beside ? ((k & 1) ? c->st_binv : c->st_c2)
-                           : !runs ? ((alt && (k & 1)) ? c->st_binv : c->st_fixed)
-                           : pc.chain == c->st_fixed ? c->st_fixed : c->st_binv;
-        if (st_b != pc.chain) HIP_TRY(hipStreamWaitEvent(st_b, c->ev_piece[k], 0));
-        if (quad && c->tune.binv_split_log2 > 0)
-            hipLaunchKernelGGL((kc_batch_inv_split<CV>), dim3((unsigned)(((n << c->tune.binv_split_log2) + BS - 1) / BS)), dim3(BS), 0, st_b, G, B,
-                               pc.lo, pc.hi, c->tune.binv_split_log2);
-        else
-            hipLaunchKernelGGL((kc_batch_inv<CV>), dim3(gx), dim3(BS), 0, st_b, G, B, pc.lo, pc.hi);
-        HIP_TRY(hipEventRecord(c->ev_binv[k], st_b));
-        if (pc.table) {
-            table_piece = k;
-            if (!quad) table_done = true;
-        }
-    }
-    // the expansions run on the library's own first expansion stream when the stream layout has one (p2e_ctx_create)
-    hipStream_t st_x = c->st_c1 ? c->st_c1 : c->stream;
-    if (c->st_c1) HIP_TRY(hipStreamWaitEvent(c->st_c1, c->ev_fork, 0));
-    emit_lds = quad ? c->tune.expand_lds_small : 0;
-    // phase C by readiness: the table first, the fixed-base run after the first loop piece (its chain is 67 ops long)
-    int order[p2e_ctx::MAX_SEG];
-    int no = 0;
-    if (runs && G.fb_begin >= 0 && G.msm_loop_iters > 0) {   // (the verifier; the fixed-base program is one piece)
-        order[no++] = 1;
-        if (np > 2) order[no++] = 2;
-        order[no++] = 0;
-        for (int k = 3; k < np; k++) order[no++] = k;
-    } else {
-        for (int k = 0; k < np; k++) order[no++] = k;
-    }
-    for (int q = 0; q < no; q++) {
-        const int k = order[q];
-        if (k >= np) {
-            set_error("curve program: phase C order names a piece the plan does not have");
-            return S.done(P2E_E_INVALID);
-        }
-        const Piece& pc = pieces[k];
-        HIP_TRY(hipStreamWaitEvent(st_x, c->ev_binv[k], 0));
-        // an expansion also reads affine results of earlier pieces: with the inversions on two streams say so
-        if (runs && q > 0) HIP_TRY(hipStreamWaitEvent(st_x, c->ev_binv[k > 0 ? k - 1 : 0], 0));
-        if (pc.wait_fb) HIP_TRY(hipStreamWaitEvent(st_x, c->ev_binv[0], 0));
-        if (pc.fb_run) {
-            const int e = c->n_expand++;
-            if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev_c0[e], st_x));
-            if (gx_wide) CP_LAUNCH(kc_expand_fb_run, true, dim3(gx_wide), st_x, G, B, G.fb_begin + G.fb_windows, (size_t)0);
-            if (gx_tail) CP_LAUNCH(kc_expand_fb_run, false, dim3(gx_tail), st_x, G, B, G.fb_begin + G.fb_windows, n_wide);
-            HIP_TRY(hipEventRecord(c->ev_c1[e], st_x));
-            c->expand_kind[e] = 2;
-            c->expand_cols[e] = cols_of(G.fb_begin, G.fb_begin + G.fb_windows);
-            seg_note_expand(c, e, h_ops, G.fb_begin, G.fb_begin + G.fb_windows);
-        }
-        if (pc.it1 > pc.it0) {
-            const int e = c->n_expand++;
-            const unsigned nr = (unsigned)((pc.it1 - pc.it0 + run_iters - 1) / run_iters);
-            if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev_c0[e], st_x));
-            if (G.loop_dbls == 2) {
-                if (gx_wide) CP_LAUNCH(kc_expand_runs2, true, dim3(gx_wide, nr), st_x, G, B, pc.it0, run_iters, pc.it1, (size_t)0);
-                if (gx_tail) CP_LAUNCH(kc_expand_runs2, false, dim3(gx_tail, nr), st_x, G, B, pc.it0, run_iters, pc.it1, n_wide);
-            } else {
-                if (gx_wide) CP_LAUNCH(kc_expand_runs, true, dim3(gx_wide, nr), st_x, G, B, pc.it0, run_iters, pc.it1, (size_t)0);
-                if (gx_tail) CP_LAUNCH(kc_expand_runs, false, dim3(gx_tail, nr), st_x, G, B, pc.it0, run_iters, pc.it1, n_wide);
-            }
-            HIP_TRY(hipEventRecord(c->ev_c1[e], st_x));
-            c->expand_kind[e] = 1;
-            c->expand_cols[e] = cols_of(G.msm_loop_begin + stride * pc.it0, G.msm_loop_begin + stride * pc.it1);
-            seg_note_expand(c, e, h_ops, G.msm_loop_begin + stride * pc.it0, G.msm_loop_begin + stride * pc.it1);
-        }
-        if (pc.s_hi > pc.s_lo) {
-            const int e = c->n_expand++;
-            if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev_c0[e], st_x));
-            if (gx_wide) CP_LAUNCH(kc_expand, true, dim3(gx_wide, (unsigned)(pc.s_hi - pc.s_lo)), st_x, G, B, pc.s_lo, (size_t)0);
-            if (gx_tail) CP_LAUNCH(kc_expand, false, dim3(gx_tail, (unsigned)(pc.s_hi - pc.s_lo)), st_x, G, B, pc.s_lo, n_wide);
-            HIP_TRY(hipEventRecord(c->ev_c1[e], st_x));
-            c->expand_kind[e] = 0;
-            c->expand_cols[e] = cols_of(pc.s_lo, pc.s_hi);
-            seg_note_expand(c, e, h_ops, pc.s_lo, pc.s_hi);
-        }
-    }
-    if (c->st_c1) {
-        HIP_TRY(hipEventRecord(c->ev_c1join, c->st_c1));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_c1join, 0));
-    }
-    if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev[5], c->stream));
-    hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, B.err, B.valid, err, valid, n, c->d_counter);
-    c->have_phases = true;
+    if (pl.ops == plan::OPS_RUNS) B.ops = P->d_ops_runs.get();
+    if (long rc = issue_plan<CurveKernels<CV>>(c, pl, G, B, P->H.sb.ops, compact, !sw.narrow_stores && io.paired_stores_ok(compact), io.err,
+                                                io.valid))
+        return rc;
     return S.done(finish_call(c));
-#undef CP_LAUNCH
 }
 
 #if P2E_PART < 0 || P2E_PART == 2

@@ -1,10 +1,11 @@
-// Tuning knobs of a context: the values the launch plans of run_program / run_curve_program read, their defaults with
-// the measurements behind them, and the ONE table that fills them from the environment when a context is created
-// (p2e_ctx_create).  Host only, no HIP: tests/emu drives read_tuning with a getenv of its own.
+// Tuning knobs of a context: the values the launch plans (launch_plan.hpp choose_builtin / choose_curve) read, their
+// defaults with the measurements behind them, and the ONE table that fills them from the environment when a context is
+// created (p2e_ctx_create).  Host only, no HIP: tests/emu drives read_tuning with a getenv of its own.
 //
-// Read on every call instead, by getenv at the place of use: P2E_NARROW_STORES (narrow_stores_forced below) and the
-// curve-program switches P2E_CP_NO_RUNS, P2E_CP_NO_QUAD, P2E_CP_NO_ALT_B, P2E_CP_FB_SERIAL, P2E_CP_PIECE_OPS_QUAD and
-// P2E_CP_TAIL_OPS_QUAD (run_curve_program): a test may toggle them between two calls on one context.
+// Read on every call instead (CallSwitches, read_call_switches below): P2E_NARROW_STORES and the curve-program switches
+// P2E_CP_NO_RUNS, P2E_CP_NO_QUAD, P2E_CP_NO_ALT_B, P2E_CP_FB_SERIAL, P2E_CP_PIECE_OPS_QUAD and P2E_CP_TAIL_OPS_QUAD: a test
+// may toggle them between two calls on one context.  The two launchers (run_program, run_curve_program) read them once, in
+// their first lines, and hand them to the plan; nothing below the launchers looks at the environment.
 // P2E_STREAM_LAYOUT, P2E_TOUCH_STREAMS, P2E_QUAD_EXPAND_CUS and P2E_QUAD_EXPAND_CU_PATTERN belong to the stream setup
 // of p2e_ctx_create.
 #pragma once
@@ -150,7 +151,33 @@ inline void read_tuning(Tuning& t, Env env) {
     }
 }
 
-// 16-byte (paired) column stores switched off for this call: every emitting launch takes its one-signature-per-lane form
+// P2E_NARROW_STORES alone, for the streaming passes (aux, gate, constraint-block), which have no launch plan
 inline bool narrow_stores_forced() { return getenv("P2E_NARROW_STORES") != nullptr; }
+
+// The per-call switches.  The five flags are set by the variable's PRESENCE, whatever its value.
+struct CallSwitches {
+    bool narrow_stores = false;   // 16-byte (paired) column stores switched off: every emitting launch takes its one-signature-per-lane form
+    bool cp_no_runs = false, cp_no_quad = false, cp_no_alt_b = false, cp_fb_serial = false;
+    bool cp_piece_ops_quad_set = false, cp_tail_ops_quad_set = false;   // atoi of the value; choose_curve ignores one out of range
+    int cp_piece_ops_quad = 0, cp_tail_ops_quad = 0;
+};
+template <class Env>
+inline CallSwitches read_call_switches(Env env) {
+    CallSwitches s;
+    s.narrow_stores = env("P2E_NARROW_STORES") != nullptr;
+    s.cp_no_runs = env("P2E_CP_NO_RUNS") != nullptr;
+    s.cp_no_quad = env("P2E_CP_NO_QUAD") != nullptr;
+    s.cp_no_alt_b = env("P2E_CP_NO_ALT_B") != nullptr;
+    s.cp_fb_serial = env("P2E_CP_FB_SERIAL") != nullptr;
+    if (const char* v = env("P2E_CP_PIECE_OPS_QUAD")) {
+        s.cp_piece_ops_quad_set = true;
+        s.cp_piece_ops_quad = atoi(v);
+    }
+    if (const char* v = env("P2E_CP_TAIL_OPS_QUAD")) {
+        s.cp_tail_ops_quad_set = true;
+        s.cp_tail_ops_quad = atoi(v);
+    }
+    return s;
+}
 
 }  // namespace p2e

@@ -9,6 +9,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/p2e.h"
@@ -16,6 +17,7 @@
 #include "consts.hpp"
 #include "device_array.hpp"
 #include "knobs.hpp"
+#include "launch_plan.hpp"
 #include "pipeline.hpp"
 #include "prims.hpp"
 #include "quad.hpp"
@@ -565,8 +567,7 @@ struct p2e_ctx {
     // ALU and all of the HBM bandwidth idle; the witness expansion is HBM-bound.  So the chains run on
     // their own high-priority streams, cut into pieces, and phases B/C of every finished piece run on the
     // caller's stream underneath the following pieces.
-    static constexpr int MAX_PIECES = Tuning::MAX_PIECES;
-    static constexpr int MAX_SEG = 2 * MAX_PIECES + 2;
+    static constexpr int MAX_SEG = plan::MAX_SEG;
     // st_binv, st_c2: second phase-B and second phase-C stream of the small-batch plan
     hipStream_t st_msm = nullptr, st_fixed = nullptr, st_binv = nullptr, st_c2 = nullptr;
     // st_c1: the library's OWN first expansion stream (stream_layout with a '1'): the caller's stream then only starts the
@@ -579,7 +580,7 @@ struct p2e_ctx {
     hipEvent_t ev_c2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_fixed = nullptr, ev_piece[MAX_SEG] = {}, ev_binv[MAX_SEG] = {};
     // one event pair around every expansion launch; kind 0 = k_expand (op by op), 1 = k_expand_runs, 2 = k_expand_fb_run
-    static constexpr int MAX_EXPAND = 2 * MAX_SEG;
+    static constexpr int MAX_EXPAND = plan::MAX_EXPAND;
     hipEvent_t ev_c0[MAX_EXPAND] = {}, ev_c1[MAX_EXPAND] = {};
     int n_expand = 0, n_seg = 0;
     double expand_cols[MAX_EXPAND] = {};
@@ -1295,64 +1296,244 @@ extern "C" long p2e_limb_pack(p2e_ctx* c, const uint64_t* limbs, uint8_t* packed
 // ====================================================================================================
 // fused schedules
 // ====================================================================================================
+// The caller's pointers of a fused call; stage_fused replaces them by device pointers where the context stages.
+struct FusedIO {
+    const uint8_t* in[7];   // msg, r, s, pkx, pky, qx, qy (null: not an input of the program)
+    uint64_t* cols;         // the u64 column matrix, or null: the compact container (narrow, wide) / no witness at all
+    size_t ld;
+    uint32_t* narrow;
+    size_t ldn;
+    uint64_t* wide;
+    size_t ldw;
+    uint8_t *err, *valid;
+    // 16-byte column stores need full workgroups, an even column stride and a 16-byte aligned matrix
+    // paired stores need full workgroups, even column strides and matrices aligned to two elements
+    bool paired_stores_ok(bool compact) const {
+        return compact ? (ldn % 2 == 0 && ldw % 2 == 0 && (reinterpret_cast<uintptr_t>(narrow) & 7) == 0 &&
+                          (reinterpret_cast<uintptr_t>(wide) & 15) == 0)
+                       : (ld % 2 == 0 && (reinterpret_cast<uintptr_t>(cols) & 15) == 0);
+    }
+};
+// the common preface of the two launchers: inputs and outputs staged, the scratch sized and bound, B filled except for
+// the tables (cpts, fbtab, ops)
+static long stage_fused(p2e_ctx* c, Staged& S, const Program& G, const host::CompactLayout& CL, const u32* wide_before, bool compact,
+                        bool verify_only, size_t n, FusedIO& io, Buffers& B) {
+    for (const uint8_t*& p : io.in) p = S.in(p, n * 32);
+    if (compact) {
+        io.narrow = S.out(io.narrow, (size_t)CL.num_narrow * io.ldn * 4);
+        io.wide = S.out(io.wide, (size_t)CL.num_wide * io.ldw * 8);
+    } else if (!verify_only) {
+        io.cols = S.out(io.cols, (size_t)G.num_cols * io.ld * 8);
+    }
+    io.err = S.out(io.err, n);
+    io.valid = S.out(io.valid, n);
+    if (S.rc) return S.rc;
+    ScratchLayout L = scratch_layout(G, n);
+    int rc = ensure_scratch(c, L.total);
+    if (rc) return rc;
+    B = Buffers{};
+    B.msg = io.in[0];
+    B.r = io.in[1];
+    B.s = io.in[2];
+    B.pkx = io.in[3];
+    B.pky = io.in[4];
+    B.qx = io.in[5];
+    B.qy = io.in[6];
+    B.sink = Sink{io.cols, io.ld, io.narrow, io.ldn, io.wide, io.ldw, wide_before};
+    B.n = n;
+    L.bind(B, (char*)c->scratch);
+    return 0;
+}
+static plan::Layout stream_layout(const p2e_ctx* c) { return plan::Layout{c->st_c1 != nullptr, c->st_c1q != nullptr}; }
+// what: "curve program" / "built-in program"; quad: the four-lane plan of a curve program (its piece length is a switch)
+static void set_plan_error(plan::Error e, const std::string& what, bool quad) {
+    set_error(e == plan::TOO_MANY_PIECES
+                  ? what + " has too many pieces for the launch plan (at most " + std::to_string(plan::MAX_SEG) + ")" +
+                        std::string(quad ? ": raise P2E_CP_PIECE_OPS_QUAD" : "")
+              : e == plan::BAD_SHAPE ? what + " does not have the shape the run plan expects"
+              : e == plan::BAD_ORDER ? what + ": phase C order names a piece the plan does not have"
+                                     : what + ": the launch plan has more steps than a plan holds");
+}
+
+// The ONE place a plan becomes HIP calls: walks the steps in list order and does what each says.  K names the kernels of
+// a family (BuiltinKernels, CurveKernels<CV>); no decision is taken here except the kernel variant of an emitting launch
+// (EmitOf<MODE>: bit 0 = paired stores, bit 1 = compact container), which depends on pointer alignment (wide_ok): the
+// paired launch over the full workgroups, the narrow one over the ragged tail.
+// Keeps the books of p2e_segments_describe / p2e_last_phase_ms from the EXPAND_* steps.
+template <class K>
+static long issue_plan(p2e_ctx* c, const plan::Plan& pl, const Program& G, const Buffers& B, const std::vector<OpDesc>& h_ops,
+                       bool compact, bool wide_ok, uint8_t* err, uint8_t* valid) {
+    using namespace plan;
+    const size_t n = B.n;
+    const unsigned gx = (unsigned)((n + BS - 1) / BS), gx4 = (unsigned)((4 * n + BS - 1) / BS);
+    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
+    const unsigned gx_wide = (unsigned)(n_wide / BS);
+    const unsigned gx_tail = (unsigned)((n - n_wide + BS - 1) / BS);
+    auto stream_of = [&](Stream s) -> hipStream_t {
+        switch (s) {
+        case ST_M: return c->st_msm;
+        case ST_F: return c->st_fixed;
+        case ST_B: return c->st_binv;
+        case ST_C1: return pl.masked_expand ? c->st_c1q : c->st_c1 ? c->st_c1 : c->stream;
+        case ST_C2: return pl.masked_expand ? c->st_c2q : c->st_c2;
+        default: return c->stream;
+        }
+    };
+    auto event_of = [&](Event e) -> hipEvent_t {
+        switch (e.kind) {
+        case EV_FORK: return c->ev_fork;
+        case EV_FIXED: return c->ev_fixed;
+        case EV_PIECE: return c->ev_piece[e.idx];
+        case EV_BINV: return c->ev_binv[e.idx];
+        case EV_C0: return c->ev_c0[e.idx];
+        case EV_C1: return c->ev_c1[e.idx];
+        case EV_C2: return c->ev_c2;
+        case EV_C1JOIN: return c->ev_c1join;
+        case EV_T0: return c->ev[0];
+        case EV_T1: return c->ev[1];
+        default: return c->ev[5];
+        }
+    };
+    // launch(mode, workgroups, first signature) once per store form
+    auto emit = [&](auto&& launch) {
+        if (gx_wide) {
+            if (compact) launch(std::integral_constant<int, 3>{}, gx_wide, (size_t)0);
+            else launch(std::integral_constant<int, 1>{}, gx_wide, (size_t)0);
+        }
+        if (gx_tail) {
+            if (compact) launch(std::integral_constant<int, 2>{}, gx_tail, n_wide);
+            else launch(std::integral_constant<int, 0>{}, gx_tail, n_wide);
+        }
+    };
+    // expansion launch e completes the columns of ops [lo, hi); kind 0 = op by op, 1 = loop runs, 2 = the fixed-base run
+    auto note_expand = [&](int e, int kind, int lo, int hi) {
+        double cw = 0;
+        for (int t = lo; t < hi; t++) cw += op_cols(h_ops[t]);
+        c->n_expand = e + 1;
+        c->expand_kind[e] = kind;
+        c->expand_cols[e] = cw;
+        seg_note_expand(c, e, h_ops, lo, hi);
+    };
+    c->n_seg = pl.n_seg;
+    c->n_expand = 0;
+    seg_begin_call(c, h_ops, (u32)G.num_cols);
+    const unsigned lds = pl.expand_lds;
+    for (int k = 0; k < pl.n_steps; k++) {
+        const Step& s = pl.steps[k];
+        hipStream_t st = stream_of(s.stream);
+        switch (s.kind) {
+        case RECORD: HIP_TRY(hipEventRecord(event_of(s.ev), st)); break;
+        case WAIT: HIP_TRY(hipStreamWaitEvent(st, event_of(s.ev), 0)); break;
+        case SCALAR:
+            emit([&](auto m, unsigned g, size_t first) { K::template scalar<decltype(m)::value>(dim3(g), st, G, B, first); });
+            break;
+        case CHAIN:
+            if (s.form == ROWS) {
+                if constexpr (K::has_rows) {
+                    K::chain_rows(dim3(gx, (unsigned)s.b), st, G, B, s.a, s.c);
+                } else {   // a missing kernel is an error, never a skipped step
+                    set_error("launch plan: this kernel family has no row chains");
+                    return P2E_E_INVALID;
+                }
+            } else if (s.form == QUAD)
+                K::chain_quad(dim3(gx4), st, G, B, s.a, s.b, s.c, s.d);
+            else
+                K::chain_lane(dim3(gx), st, G, B, s.a, s.b, s.c, s.d);
+            break;
+        case BINV:
+            if (s.d > 0)
+                K::binv_split(dim3((unsigned)(((n << s.d) + BS - 1) / BS)), st, G, B, s.a, s.b, s.c, s.d);
+            else
+                K::binv(dim3(gx), st, G, B, s.a, s.b, s.c);
+            break;
+        case EXPAND_OPS:
+            emit([&](auto m, unsigned g, size_t first) {
+                K::template expand<decltype(m)::value>(dim3(g, (unsigned)(s.b - s.a)), lds, st, G, B, s.a, first);
+            });
+            note_expand(s.d, 0, s.a, s.b);
+            break;
+        case EXPAND_RUNS: {
+            const unsigned nr = (unsigned)((s.b - s.a + s.c - 1) / s.c);
+            emit([&](auto m, unsigned g, size_t first) {
+                K::template expand_runs<decltype(m)::value>(dim3(g, nr), lds, st, G, B, s.a, s.c, s.b, first);
+            });
+            const int stride = K::loop_stride(G);
+            note_expand(s.d, 1, G.msm_loop_begin + stride * s.a, G.msm_loop_begin + stride * s.b);
+            break;
+        }
+        case EXPAND_FB_RUN:
+            emit([&](auto m, unsigned g, size_t first) { K::template expand_fb_run<decltype(m)::value>(dim3(g), lds, st, G, B, s.a, first); });
+            note_expand(s.d, 2, G.fb_begin, G.fb_begin + G.fb_windows);
+            break;
+        case FINALIZE:
+            hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, st, B.err, B.valid, err, valid, n, c->d_counter);
+            break;
+        }
+    }
+    c->have_phases = true;
+    return 0;
+}
+
 #if P2E_HAS(1)
-// cols != nullptr: the u64 column matrix; otherwise the compact container (narrow, wide)
+struct BuiltinKernels {
+    static constexpr bool has_rows = true;
+    static int loop_stride(const Program&) { return 3; }   // double, double, conditional add
+    template <int MODE>
+    static void scalar(dim3 g, hipStream_t st, const Program& G, const Buffers& B, size_t first) {
+        hipLaunchKernelGGL(k_scalar<MODE>, g, dim3(BS), 0, st, G, B, first);
+    }
+    static void chain_lane(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int table_affine, int cont) {
+        hipLaunchKernelGGL(k_chains, g, dim3(BS), 0, st, G, B, lo, hi, table_affine, cont);
+    }
+    static void chain_quad(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int table_affine, int cont) {
+        hipLaunchKernelGGL(k_chains_quad, g, dim3(BS), 0, st, G, B, lo, hi, table_affine, cont);
+    }
+    static void chain_rows(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int count) {
+        hipLaunchKernelGGL(k_chain_rows, g, dim3(BS), 0, st, G, B, lo, count);
+    }
+    static void binv(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int have_prefix) {
+        hipLaunchKernelGGL(k_batch_inv, g, dim3(BS), 0, st, G, B, lo, hi, have_prefix);
+    }
+    static void binv_split(dim3 g, hipStream_t st, const Program& G, const Buffers& B, int lo, int hi, int have_prefix, int split_log2) {
+        hipLaunchKernelGGL(k_batch_inv_split, g, dim3(BS), 0, st, G, B, lo, hi, have_prefix, split_log2);
+    }
+    template <int MODE>
+    static void expand(dim3 g, unsigned lds, hipStream_t st, const Program& G, const Buffers& B, int lo, size_t first) {
+        hipLaunchKernelGGL(k_expand<MODE>, g, dim3(BS), lds, st, G, B, lo, first);
+    }
+    template <int MODE>
+    static void expand_runs(dim3 g, unsigned lds, hipStream_t st, const Program& G, const Buffers& B, int it0, int run_iters, int it1,
+                            size_t first) {
+        hipLaunchKernelGGL(k_expand_runs<MODE>, g, dim3(BS), lds, st, G, B, it0, run_iters, it1, first);
+    }
+    template <int MODE>
+    static void expand_fb_run(dim3 g, unsigned lds, hipStream_t st, const Program& G, const Buffers& B, int t_after, size_t first) {
+        hipLaunchKernelGGL(k_expand_fb_run<MODE>, g, dim3(BS), lds, st, G, B, t_after, first);
+    }
+};
+
+// cols != nullptr: the u64 column matrix; otherwise the compact container (narrow, wide).  Stage, bind, build the plan, issue.
 static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8_t* r, const uint8_t* s,
                         const uint8_t* pkx, const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err,
                         uint8_t* valid, uint32_t* narrow = nullptr, size_t ldn = 0, uint64_t* wide = nullptr, size_t ldw = 0,
                         bool verify_only = false) {
+    const CallSwitches sw = read_call_switches(getenv);
     const bool compact = cols == nullptr && !verify_only;
     const DeviceProgram& DP = c->progs[program];
     const Program& G = DP.host->sb.prog;
     Staged S(c);
-    msg = S.in(msg, n * 32);
-    r = S.in(r, n * 32);
-    s = S.in(s, n * 32);
-    pkx = S.in(pkx, n * 32);
-    pky = S.in(pky, n * 32);
-    if (compact) {
-        narrow = S.out(narrow, (size_t)DP.host->compact.num_narrow * ldn * 4);
-        wide = S.out(wide, (size_t)DP.host->compact.num_wide * ldw * 8);
-    } else if (!verify_only) {
-        cols = S.out(cols, (size_t)G.num_cols * ld * 8);
-    }
-    err = S.out(err, n);
-    valid = S.out(valid, n);
-    if (S.rc) return S.done(S.rc);
-    ScratchLayout L = scratch_layout(G, n);
-    int rc = ensure_scratch(c, L.total);
-    if (rc) return S.done(rc);
-    Buffers B{};
-    B.msg = msg;
-    B.r = r;
-    B.s = s;
-    B.pkx = pkx;
-    B.pky = pky;
-    B.sink = Sink{cols, ld, narrow, ldn, wide, ldw, DP.tab.wide_before.get()};
-    B.n = n;
-    L.bind(B, (char*)c->scratch);
+    FusedIO io{{msg, r, s, pkx, pky, nullptr, nullptr}, cols, ld, narrow, ldn, wide, ldw, err, valid};
+    Buffers B;
+    if (long rc = stage_fused(c, S, G, DP.host->compact, DP.tab.wide_before.get(), compact, verify_only, n, io, B)) return S.done(rc);
     B.cpts = c->d_cpts.get();
     B.fbtab = c->d_fbtab.get();
-    // three regimes: four lanes per signature (n <= quad_max_n), lane per signature with phase B on two streams and longer
-    // runs in fewer pieces (below binv_alt_max_n), and the large-batch plan
-    const bool mid_plan = n > c->tune.quad_max_n && n < c->tune.binv_alt_max_n;
-    const bool quad_plan = n <= c->tune.quad_max_n;
-    int run_iters = 0;
-    B.ops = DP.d_ops_plain.get();
-    if (n >= c->tune.runs_min_n) {
-        run_iters = mid_plan ? c->tune.run_iters_mid : c->tune.run_iters;
-        if (run_iters > 0) B.ops = mid_plan ? DP.d_ops_mid.get() : DP.d_ops.get();
-    } else if (quad_plan && c->tune.run_iters_small > 0) {
-        run_iters = c->tune.run_iters_small;
-        B.ops = DP.d_ops_small.get();
-    }
     ZERO_COUNTER(c);
-    unsigned gx = (unsigned)((n + BS - 1) / BS);
     c->n_expand = 0;
     c->seg_blocks.clear();
     if (verify_only) {
         // the native verification alone: scalar phase without emission, the two chains side by side in Jacobian
         // coordinates (no batch inversion, no expansion), the final add, r == x on its Jacobian result
+        const unsigned gx = (unsigned)((n + BS - 1) / BS);
         B.ops = DP.d_ops_plain.get();
         hipLaunchKernelGGL(k_scalar<4>, dim3(gx), dim3(BS), 0, c->stream, G, B, (size_t)0);
         HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
@@ -1363,288 +1544,20 @@ static long run_program(p2e_ctx* c, int program, const uint8_t* msg, const uint8
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fixed, 0));
         hipLaunchKernelGGL(k_chains, dim3(gx), dim3(BS), 0, c->stream, G, B, G.chain_begin[2], G.chain_end[2], 0, 0);
         hipLaunchKernelGGL(k_verify_check, dim3(gx), dim3(BS), 0, c->stream, G, B);
-        hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, B.err, B.valid, err, valid, n, c->d_counter);
+        hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, B.err, B.valid, io.err, io.valid, n, c->d_counter);
         c->have_phases = false;
         return S.done(finish_call(c));
     }
-    // 16-byte column stores need full workgroups, an even column stride and a 16-byte aligned matrix
-    // paired stores need full workgroups, even column strides and matrices aligned to two elements
-    const bool wide_ok = !narrow_stores_forced() &&
-                         (compact ? (ldn % 2 == 0 && ldw % 2 == 0 && (reinterpret_cast<uintptr_t>(narrow) & 7) == 0 &&
-                                     (reinterpret_cast<uintptr_t>(wide) & 15) == 0)
-                                  : (ld % 2 == 0 && (reinterpret_cast<uintptr_t>(cols) & 15) == 0));
-    // kernel variant per launch: EmitOf<MODE>
-#define LAUNCH_EMIT(KERNEL, PAIRED, GRID, STREAM, ...)                                                    \
-    do {                                                                                                  \
-        if (compact) {                                                                                    \
-            if (PAIRED) hipLaunchKernelGGL(KERNEL<3>, GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);     \
-            else hipLaunchKernelGGL(KERNEL<2>, GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);            \
-        } else {                                                                                          \
-            if (PAIRED) hipLaunchKernelGGL(KERNEL<1>, GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);     \
-            else hipLaunchKernelGGL(KERNEL<0>, GRID, dim3(BS), emit_lds, STREAM, __VA_ARGS__);            \
-        }                                                                                                 \
-    } while (0)
-    unsigned emit_lds = 0;   // dynamic LDS of the emitting kernels (only ever non-zero for the expansions of the small-batch plan)
-    const size_t n_wide = wide_ok ? (n / BS) * BS : 0;
-    const unsigned gx_wide = (unsigned)(n_wide / BS);
-    const unsigned gx_tail = (unsigned)((n - n_wide + BS - 1) / BS);
-    // ---- launch plan ------------------------------------------------------------------------------------
-    // chains (latency-bound, sequential) : their own high-priority streams, cut into pieces
-    // phase B of a piece                 : the fixed-base chain's stream, once the piece's chain kernel is done
-    // phase C of a piece                 : the caller's stream, after its phase B (HBM-bound)
-    // so that the HBM-bound expansion of finished pieces hides the chains and inversions of later ones.
-    struct Seg {
-        int lo, hi, order;   // ops for phases A and B; readiness estimate (ops walked on its chain before it completes)
-        hipStream_t chain_stream;
-        bool final_after;    // append the final add (needs the fixed-base chain) to this piece
-        int s_lo, s_hi;      // ops expanded one by one (k_expand)
-        int it0, it1;        // MSM-loop iterations expanded as runs (k_expand_runs)
-        bool fb_run;         // the fixed-base windows of this piece expanded as one run per signature (k_expand_fb_run)
-    };
-    Seg segs[p2e_ctx::MAX_SEG];
-    int ns = 0;
-    const bool verify = G.num_chains == 3;
-    // small batches: four lanes per signature in phase A, split inversion batches in phase B (quad.hpp)
-    const bool quad = n <= c->tune.quad_max_n;
-    const int msm_pieces = quad ? c->tune.msm_pieces_small : mid_plan ? c->tune.msm_pieces_mid : c->tune.msm_pieces;
-    // with run expansion the fixed-base chain is ONE piece: its windows keep no X, Y / affine form in memory
-    // (F_NO_AFFINE), so nothing could resume the chain from scratch in the middle
-    const bool fb_run = run_iters > 0 && verify && c->tune.fb_run && G.fb_begin == G.chain_begin[1];
-    const int fixed_pieces = fb_run ? 1 : quad ? c->tune.fixed_pieces_small : c->tune.fixed_pieces;
-    auto cut = [&](int lo, int hi, int pieces, hipStream_t st) {
-        if (pieces > hi - lo) pieces = hi - lo;
-        int a = lo;
-        for (int k = 0; k < pieces; k++) {
-            int rem = pieces - k;
-            int len = (hi - a + rem - 1) / rem;
-            segs[ns++] = Seg{a, a + len, a + len - lo, st, false, a, a + len, 0, 0, false};
-            a += len;
-        }
-    };
-    if (verify) cut(G.chain_begin[1], G.chain_end[1], fixed_pieces, c->st_fixed);
-    if (fb_run) {   // windows as one run, then the unblinding add op by op
-        segs[0].fb_run = true;
-        segs[0].s_lo = G.fb_begin + G.fb_windows;
+    plan::Plan pl;
+    if (!plan::build_builtin(G, plan::choose_builtin(G, c->tune, n, stream_layout(c), (c->flags & P2E_CTX_PHASE_TIMING) != 0), pl)) {
+        set_plan_error(pl.error, "built-in program", false);
+        return S.done(P2E_E_INVALID);
     }
-    const int first_msm = ns;
-    {
-        // MSM chain = window table (its own piece: inverted first, read in affine form by everything after) +
-        // the loop, cut at run boundaries into msm_pieces - 1 groups + the trailing unblinding add
-        const int lo0 = G.chain_begin[0], hi0 = G.chain_end[0];
-        const int lb = G.msm_loop_begin, iters = G.msm_loop_iters, le = lb + 3 * iters;
-        const int R = run_iters > 0 ? run_iters : 1;
-        const int nruns = (iters + R - 1) / R;
-        int groups = msm_pieces > 1 ? msm_pieces - 1 : 1;
-        if (groups > nruns) groups = nruns;
-        // small-batch plan: an explicit list of runs per piece (the list is used while it fits; the last piece takes the rest)
-        int listed = 0;
-        // default list for the runs of 4 iterations (19 runs): 6, 5, 5, 2 and the last run alone -- the last piece's inversion
-        // batch and expansion are the exposed tail of the call (2.27 / 2.92 against 2.32 / 2.98 ms at 2^13 / 12 288 with
-        // equal pieces, profiles/r03_quad_plan_piece_sizes_sweep.txt)
-        static const int takes_r4[p2e_ctx::MAX_PIECES + 1] = {6, 5, 5, 2, 0};
-        const int* takes = c->tune.small_takes[0] > 0 ? c->tune.small_takes : (quad && run_iters == 4 && iters == MSM_DIGITS) ? takes_r4 : c->tune.small_takes;
-        if (quad && takes[0] > 0) {
-            int sum = 0;
-            while (listed < p2e_ctx::MAX_PIECES - 1 && takes[listed] > 0 && sum + takes[listed] < nruns) sum += takes[listed++];
-            groups = listed + 1;
-        }
-        segs[ns++] = Seg{lo0, lb, lb - lo0, c->st_msm, false, lo0, lb, 0, 0, false};
-        int run = 0;
-        for (int g = 0; g < groups; g++) {
-            int rem = groups - g;
-            int take = (nruns - run + rem - 1) / rem;
-            if (listed) take = g < listed ? takes[g] : nruns - run;
-            int it0 = run * R, it1 = (run + take) * R < iters ? (run + take) * R : iters;
-            Seg sg{lb + 3 * it0, lb + 3 * it1, lb + 3 * it1 - lo0, c->st_msm, false, 0, 0, it0, it1, false};
-            if (run_iters == 0) {   // no run expansion: op by op
-                sg.s_lo = sg.lo;
-                sg.s_hi = sg.hi;
-                sg.it0 = sg.it1 = 0;
-            }
-            if (g == groups - 1) {     // trailing ops of the chain (the unblinding add)
-                sg.hi = hi0;
-                if (run_iters == 0) sg.s_hi = hi0; else { sg.s_lo = le; sg.s_hi = hi0; }
-                sg.order = hi0 - lo0;
-            }
-            segs[ns++] = sg;
-            run += take;
-        }
-    }
-    if (verify) segs[ns - 1].final_after = true;
-    c->n_seg = ns;
-
-    const unsigned gx4 = (unsigned)((4 * n + BS - 1) / BS);
-    const bool alt_b = quad || n < c->tune.binv_alt_max_n;   // phase B of consecutive pieces on two streams
-    auto launch_binv = [&](hipStream_t st, int lo, int hi, int have_prefix, bool last_piece = false, bool fixed_piece = false) {
-        const int sl = !quad ? (alt_b ? c->tune.binv_mid_split_log2 : 0)
-                             : last_piece ? c->tune.binv_split_log2_last : fixed_piece ? c->tune.binv_split_log2_fixed : c->tune.binv_split_log2;
-        if ((quad || alt_b) && sl > 0)
-            hipLaunchKernelGGL(k_batch_inv_split, dim3((unsigned)(((n << sl) + BS - 1) / BS)), dim3(BS), 0, st, G, B, lo, hi,
-                               have_prefix, sl);
-        else
-            hipLaunchKernelGGL(k_batch_inv, dim3(gx), dim3(BS), 0, st, G, B, lo, hi, have_prefix);
-    };
-    seg_begin_call(c, DP.h_ops, (u32)G.num_cols);
-    if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    if (gx_wide) LAUNCH_EMIT(k_scalar, true, dim3(gx_wide), c->stream, G, B, (size_t)0);
-    if (gx_tail) LAUNCH_EMIT(k_scalar, false, dim3(gx_tail), c->stream, G, B, n_wide);
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->st_msm, c->ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(c->st_fixed, c->ev_fork, 0));
-    if (alt_b) HIP_TRY(hipStreamWaitEvent(c->st_binv, c->ev_fork, 0));
-    // first expansion stream: the library's own if the layout has one (the caller's stream then waits for it at the end)
-    hipStream_t st_c1 = c->st_c1 ? c->st_c1 : c->stream;
-    hipStream_t st_c2 = c->st_c2;
-    const bool own_c1 = c->st_c1 != nullptr || (quad && c->st_c1q);
-    if (quad && c->st_c1q) {
-        st_c1 = c->st_c1q;
-        st_c2 = c->st_c2q;
-    }
-    if (own_c1) HIP_TRY(hipStreamWaitEvent(st_c1, c->ev_fork, 0));
-    // chains
-    for (int k = 0; k < ns; k++) {
-        Seg& sg = segs[k];
-        // once the table piece has been inverted on this stream (below), later pieces read the table affine
-        // (small-batch plan: the FIRST loop piece does not wait for the table's inversion -- it reads the table in
-        // Jacobian form, one level more per addition, and starts ~0.15 ms earlier; the table's phase B runs beside it)
-        const int table_affine = (sg.chain_stream == c->st_msm && k > first_msm + (quad ? 1 : 0)) ? 1 : 0;
-        if (quad && k == first_msm + 2) HIP_TRY(hipStreamWaitEvent(c->st_msm, c->ev_binv[first_msm], 0));
-        // glv_mul alone: the window table as 2 chains of 4 adds, then 6 and 9 independent adds (body_chain_rows):
-        // -6 % at 2^10, -4 % at 2^16.  Not in the verify program: there the fixed-base chain runs beside it, three
-        // 186-VGPR waves do not fit a SIMD and the rows only queue (+0.6...1 % measured).
-        const bool table_rows = (!verify || quad) && k == first_msm && sg.hi - sg.lo == MSM_TABLE_OPS;
-        if (table_rows) {
-            hipLaunchKernelGGL(k_chain_rows, dim3(gx, 2), dim3(BS), 0, sg.chain_stream, G, B, sg.lo, 4);
-            hipLaunchKernelGGL(k_chain_rows, dim3(gx, 6), dim3(BS), 0, sg.chain_stream, G, B, sg.lo + 8, 1);
-            hipLaunchKernelGGL(k_chain_rows, dim3(gx, 9), dim3(BS), 0, sg.chain_stream, G, B, sg.lo + 14, 1);
-        } else if (quad) {
-            hipLaunchKernelGGL(k_chains_quad, dim3(gx4), dim3(BS), 0, sg.chain_stream, G, B, sg.lo, sg.hi, table_affine, 0);
-        } else {
-            hipLaunchKernelGGL(k_chains, dim3(gx), dim3(BS), 0, sg.chain_stream, G, B, sg.lo, sg.hi, table_affine, 0);
-        }
-        if (verify && k == first_msm - 1) HIP_TRY(hipEventRecord(c->ev_fixed, c->st_fixed));
-        if (sg.final_after) {
-            HIP_TRY(hipStreamWaitEvent(c->st_msm, c->ev_fixed, 0));
-            // the final add joins the inversion batch of the last MSM piece
-            if (quad)
-                hipLaunchKernelGGL(k_chains_quad, dim3(gx4), dim3(BS), 0, c->st_msm, G, B, G.chain_begin[2], G.chain_end[2], 0, 1);
-            else
-                hipLaunchKernelGGL(k_chains, dim3(gx), dim3(BS), 0, c->st_msm, G, B, G.chain_begin[2], G.chain_end[2], 0, 1);
-            sg.hi = G.chain_end[2];
-            sg.s_hi = G.chain_end[2];
-        }
-        HIP_TRY(hipEventRecord(c->ev_piece[k], sg.chain_stream));
-        if (k == first_msm) {
-            // The first MSM piece is the 23-op table build.  Its phase B runs right here on the chain's own
-            // stream (the rest of the chain is not on the critical path: it ends long before the expansion
-            // does), so that the first k_expand can start ~0.8 ms earlier than if it queued behind the
-            // fixed-base chain on the other stream.
-            hipStream_t st_tab = quad ? c->st_binv : c->st_msm;
-            if (quad) HIP_TRY(hipStreamWaitEvent(st_tab, c->ev_piece[k], 0));
-            launch_binv(st_tab, sg.lo, sg.hi, table_rows ? 0 : 1);
-            HIP_TRY(hipEventRecord(c->ev_binv[k], st_tab));
-        }
-    }
-    // order of phases B / C: by readiness
-    int order[p2e_ctx::MAX_SEG];
-    for (int k = 0; k < ns; k++) order[k] = k;
-    for (int a = 1; a < ns; a++)
-        for (int b = a; b > 0 && segs[order[b]].order < segs[order[b - 1]].order; b--) {
-            int t = order[b];
-            order[b] = order[b - 1];
-            order[b - 1] = t;
-        }
-    c->n_expand = 0;
-    bool used_c2 = false;
-    int last_b[2] = {-1, quad ? first_msm : -1};   // most recent inversion batch on st_fixed / st_binv (the table's: above)
-    emit_lds = quad ? c->tune.expand_lds_small : c->tune.expand_lds;
-    for (int q = 0; q < ns; q++) {
-        const int k = order[q];
-        const Seg& sg = segs[k];
-        // HIP multiplexes streams onto a few hardware queues (4 by default) and kernels of one queue run
-        // in order: a dedicated inversion stream ended up sharing the caller's queue and serialised B
-        // with C.  The fixed-base chain's stream is idle after its first ~1 ms, so phase B lives there.
-        // (small-batch plan: phase B of consecutive pieces alternates between two streams, so that an inversion batch
-        // does not queue behind the previous one -- there the chains are no slower than phase B)
-        const bool b_odd = (q & 1) != (quad && c->tune.quad_b_first_on_fixed ? 1 : 0);
-        hipStream_t st_b = (alt_b && b_odd) ? c->st_binv : c->st_fixed;
-        if (k != first_msm) {
-            HIP_TRY(hipStreamWaitEvent(st_b, c->ev_piece[k], 0));
-            launch_binv(st_b, sg.lo, sg.hi, 1, k == ns - 1, k < first_msm);
-            HIP_TRY(hipEventRecord(c->ev_binv[k], st_b));
-            last_b[st_b == c->st_binv ? 1 : 0] = k;
-        }
-        // (small-batch plan: phase C alternates between the caller's stream and a second one, so that an expansion
-        // waiting for its inversion batch does not hold up the expansions queued behind it)
-        hipStream_t st_c = (quad && (q & 1)) ? st_c2 : st_c1;
-        used_c2 = used_c2 || st_c == st_c2;
-        HIP_TRY(hipStreamWaitEvent(st_c, c->ev_binv[k], 0));
-        // an expansion also reads affine results of EARLIER pieces (the first operand of its first op, the window
-        // table, the fixed-base result under the final add): with one expansion stream the queue order implied
-        // their inversion batches, with two it has to be said
-        // (the inversion batches sit on two in-order streams: the most recent one of each implies every earlier one, so
-        // two waits say what q of them used to -- 28 barrier packets less on the expansion streams of a verify call)
-        if (quad) {
-            if (c->tune.quad_few_waits) {
-                for (int sb = 0; sb < 2; sb++)
-                    if (last_b[sb] >= 0 && last_b[sb] != k) HIP_TRY(hipStreamWaitEvent(st_c, c->ev_binv[last_b[sb]], 0));
-            } else {
-                for (int q2 = 0; q2 < q; q2++) HIP_TRY(hipStreamWaitEvent(st_c, c->ev_binv[order[q2]], 0));
-            }
-        }
-        auto cols_of = [&](int lo, int hi) {
-            double cw = 0;
-            for (int t = lo; t < hi; t++)
-                cw += DP.h_ops[t].kind == OP_DBL ? COLS_DBL : DP.h_ops[t].kind == OP_CADD ? COLS_CADD : COLS_ADD;
-            return cw;
-        };
-        if (sg.it1 > sg.it0) {
-            const int R = run_iters;
-            const unsigned nr = (unsigned)((sg.it1 - sg.it0 + R - 1) / R);
-            const int e = c->n_expand++;
-            if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev_c0[e], st_c));
-            if (gx_wide) LAUNCH_EMIT(k_expand_runs, true, dim3(gx_wide, nr), st_c, G, B, sg.it0, R, sg.it1, (size_t)0);
-            if (gx_tail) LAUNCH_EMIT(k_expand_runs, false, dim3(gx_tail, nr), st_c, G, B, sg.it0, R, sg.it1, n_wide);
-            HIP_TRY(hipEventRecord(c->ev_c1[e], st_c));
-            c->expand_kind[e] = 1;
-            c->expand_cols[e] = cols_of(G.msm_loop_begin + 3 * sg.it0, G.msm_loop_begin + 3 * sg.it1);
-            seg_note_expand(c, e, DP.h_ops, G.msm_loop_begin + 3 * sg.it0, G.msm_loop_begin + 3 * sg.it1);
-        }
-        if (sg.fb_run) {
-            const int e = c->n_expand++;
-            if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev_c0[e], st_c));
-            if (gx_wide) LAUNCH_EMIT(k_expand_fb_run, true, dim3(gx_wide), st_c, G, B, G.fb_begin + G.fb_windows, (size_t)0);
-            if (gx_tail) LAUNCH_EMIT(k_expand_fb_run, false, dim3(gx_tail), st_c, G, B, G.fb_begin + G.fb_windows, n_wide);
-            HIP_TRY(hipEventRecord(c->ev_c1[e], st_c));
-            c->expand_kind[e] = 2;
-            c->expand_cols[e] = cols_of(G.fb_begin, G.fb_begin + G.fb_windows);
-            seg_note_expand(c, e, DP.h_ops, G.fb_begin, G.fb_begin + G.fb_windows);
-        }
-        if (sg.s_hi > sg.s_lo) {
-            const int e = c->n_expand++;
-            if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev_c0[e], st_c));
-            if (gx_wide) LAUNCH_EMIT(k_expand, true, dim3(gx_wide, (unsigned)(sg.s_hi - sg.s_lo)), st_c, G, B, sg.s_lo, (size_t)0);
-            if (gx_tail) LAUNCH_EMIT(k_expand, false, dim3(gx_tail, (unsigned)(sg.s_hi - sg.s_lo)), st_c, G, B, sg.s_lo, n_wide);
-            HIP_TRY(hipEventRecord(c->ev_c1[e], st_c));
-            c->expand_kind[e] = 0;
-            c->expand_cols[e] = cols_of(sg.s_lo, sg.s_hi);
-            seg_note_expand(c, e, DP.h_ops, sg.s_lo, sg.s_hi);
-        }
-    }
-    if (used_c2) {   // join the second expansion stream
-        HIP_TRY(hipEventRecord(c->ev_c2, st_c2));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_c2, 0));
-    }
-    if (own_c1) {
-        HIP_TRY(hipEventRecord(c->ev_c1join, st_c1));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_c1join, 0));
-    }
-    if (c->flags & P2E_CTX_PHASE_TIMING) HIP_TRY(hipEventRecord(c->ev[5], c->stream));
-    hipLaunchKernelGGL(k_finalize, dim3(gx), dim3(BS), 0, c->stream, B.err, B.valid, err, valid, n, c->d_counter);
-    c->have_phases = true;
+    const DeviceArray<OpDesc>* tables[] = {&DP.d_ops_plain, &DP.d_ops, &DP.d_ops_mid, &DP.d_ops_small};   // by plan::OpTable
+    B.ops = tables[pl.ops]->get();
+    if (long rc = issue_plan<BuiltinKernels>(c, pl, G, B, DP.h_ops, compact, !sw.narrow_stores && io.paired_stores_ok(compact), io.err, io.valid))
+        return rc;
     return S.done(finish_call(c));
-#undef LAUNCH_EMIT
 }
 
 extern "C" long p2e_ecdsa_verify_witness_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* r32,

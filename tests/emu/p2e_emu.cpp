@@ -14,29 +14,186 @@
 #include "../../plonky2-ecdsa_amd/csrc/schedule.hpp"
 #include "../../plonky2-ecdsa_amd/csrc/curve_program.hpp"
 #include "../../plonky2-ecdsa_amd/csrc/knobs.hpp"
+#include "../../plonky2-ecdsa_amd/csrc/launch_plan.hpp"
 
 using namespace p2e;
 
-// E = Emit (u64 column matrix `cols`) or CompactEmit (narrow / wide matrices of the compact container)
+// The per-lane bodies behind the steps of a launch plan (csrc/launch_plan.hpp), for the built-in programs and for the
+// curve programs.  E = Emit (u64 column matrix) or CompactEmit (narrow / wide matrices of the compact container).
 template <class E>
-static long run(int program, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx,
-                const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int chunk,
-                int run_iters, uint32_t* narrow = nullptr, size_t ldn = 0, uint64_t* wide = nullptr, size_t ldw = 0) {
+struct BuiltinBodies {
+    static void scalar(const Program& G, const Buffers& B, size_t i) { body_scalar<E>(G, B, i); }
+    static void chain_lane(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool affine, bool cont) {
+        body_chain_range(G, B, i, lo, hi, affine, cont);
+    }
+    // every role walks the whole range (the host form of a level computes all four products) and writes only its own
+    // share of the scratch outputs
+    static void chain_quad(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool affine, bool cont) {
+        for (int role = 0; role < 4; role++) body_chain_range_quad(G, B, i, role, lo, hi, affine, cont);
+    }
+    static void chain_rows(const Program& G, const Buffers& B, size_t i, int lo, int nrows, int count) {
+        for (int r = 0; r < nrows; r++) body_chain_rows(G, B, i, lo, nrows, r, count);
+    }
+    static void binv(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool have_prefix) { body_batch_inv(G, B, i, lo, hi, have_prefix); }
+    static void binv_split(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool have_prefix, int q, int split) {
+        body_batch_inv_split(G, B, i, lo, hi, have_prefix, q, split);
+    }
+    static void expand(const Program& G, const Buffers& B, size_t i, int t) { body_expand<E>(G, B, i, t); }
+    static void expand_run(const Program& G, const Buffers& B, size_t i, int it0, int it1) { body_expand_run<E>(G, B, i, it0, it1); }
+    static void expand_fb_run(const Program& G, const Buffers& B, size_t i, int t_after) { body_expand_fb_run<E>(G, B, i, t_after); }
+};
+template <class CV, class E>
+struct CurveBodies {
+    static void scalar(const Program& G, const Buffers& B, size_t i) { body_cscalar<CV, E>(G, B, i); }
+    static void chain_lane(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool affine, bool) {
+        body_chain_range<CV, true>(G, B, i, lo, hi, affine, false);
+    }
+    // body_chain_range_quad_cv with the four roles in lock step, op by op, as the four lanes of a quad run: the generic walker
+    // reads most first operands back from scratch (X, Y, Z, W each stored by ONE role), so one role cannot walk the whole
+    // range before the others have started
+    static void chain_quad(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool affine, bool) {
+        ChainStateQ st[4];
+        for (ChainStateQ& q : st) {
+            q.out_id = q.p1_id = q.dyn_idx = q.dyn_val = 0xFFFF;
+            q.out.X = q.out.Y = q.out.Z = q.p1.X = q.p1.Y = q.p1.Z = q.out_zz = q.p1_zz = u256_zero();
+            q.acc = u256_small(1);
+        }
+        for (int t = lo; t < hi; t++) {
+            const OpDesc op = load_op(B.ops, t);
+            P1Sel s1[4];
+            for (int role = 0; role < 4; role++) s1[role] = quad_first_operand(G, B, i, op, st[role]);
+            for (int role = 0; role < 4; role++) body_chain_op_quad_cv<CV>(G, B, i, role, t, op, affine, s1[role], st[role]);
+        }
+    }
+    static void chain_rows(const Program&, const Buffers&, size_t, int, int, int) { abort(); }   // no curve plan has rows
+    static void binv(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool have_prefix) { body_batch_inv<CV>(G, B, i, lo, hi, have_prefix); }
+    static void binv_split(const Program& G, const Buffers& B, size_t i, int lo, int hi, bool have_prefix, int q, int split) {
+        body_batch_inv_split<CV>(G, B, i, lo, hi, have_prefix, q, split);
+    }
+    static void expand(const Program& G, const Buffers& B, size_t i, int t) { body_expand<E, CV>(G, B, i, t); }
+    static void expand_run(const Program& G, const Buffers& B, size_t i, int it0, int it1) {
+        if (G.loop_dbls == 2)   // kc_expand_runs2
+            body_expand_run<E, CV, 2>(G, B, i, it0, it1);
+        else                    // kc_expand_runs
+            body_expand_run<E, CV, 4>(G, B, i, it0, it1);
+    }
+    static void expand_fb_run(const Program& G, const Buffers& B, size_t i, int t_after) { body_expand_fb_run<E, CV>(G, B, i, t_after); }
+};
+
+// Executes the compute steps of a plan one after the other, in list order.  RECORD and WAIT are ignored: list order is
+// a valid execution order because every wait names an event recorded earlier in the list (tests/test_knobs_cpu.py).
+// How a BINV step is executed is a local matter (arbitrary batching must not change any output):
+//   split > 0          : the batch cut into `split` sub-ranges, whatever the step says (any count, not only 2^k)
+//   0 < chunk < hi - lo: the forward pass re-run inside phase B, `chunk` ops at a time
+//   otherwise          : what the step says (2^split_log2 sub-ranges, or one batch on phase A's prefix products)
+template <class K>
+static void exec_plan(const plan::Plan& pl, const Program& G, const Buffers& B, int chunk, int split) {
+    const long long n = (long long)B.n;
+    for (int k = 0; k < pl.n_steps; k++) {
+        const plan::Step& s = pl.steps[k];
+        switch (s.kind) {
+        case plan::RECORD:
+        case plan::WAIT:
+        case plan::FINALIZE: break;
+        case plan::SCALAR:
+#pragma omp parallel for
+            for (long long i = 0; i < n; i++) K::scalar(G, B, (size_t)i);
+            break;
+        case plan::CHAIN:
+#pragma omp parallel for
+            for (long long i = 0; i < n; i++) {
+                if (s.form == plan::ROWS)
+                    K::chain_rows(G, B, (size_t)i, s.a, s.b, s.c);
+                else if (s.form == plan::QUAD)
+                    K::chain_quad(G, B, (size_t)i, s.a, s.b, s.c != 0, s.d != 0);
+                else
+                    K::chain_lane(G, B, (size_t)i, s.a, s.b, s.c != 0, s.d != 0);
+            }
+            break;
+        case plan::BINV: {
+            const int parts = split > 0 ? split : s.d > 0 ? 1 << s.d : 0;
+            if (parts > 0) {
+#pragma omp parallel for
+                for (long long i = 0; i < n; i++)
+                    for (int q = 0; q < parts; q++) K::binv_split(G, B, (size_t)i, s.a, s.b, s.c != 0, q, parts);
+            } else if (chunk <= 0 || chunk >= s.b - s.a) {
+#pragma omp parallel for
+                for (long long i = 0; i < n; i++) K::binv(G, B, (size_t)i, s.a, s.b, s.c != 0);
+            } else {
+                for (int t0 = s.a; t0 < s.b; t0 += chunk) {
+                    const int t1 = t0 + chunk < s.b ? t0 + chunk : s.b;
+#pragma omp parallel for
+                    for (long long i = 0; i < n; i++) K::binv(G, B, (size_t)i, t0, t1, false);
+                }
+            }
+            break;
+        }
+        case plan::EXPAND_OPS:
+#pragma omp parallel for
+            for (long long i = 0; i < n; i++)
+                for (int t = s.a; t < s.b; t++) K::expand(G, B, (size_t)i, t);
+            break;
+        case plan::EXPAND_RUNS:
+            for (int a = s.a; a < s.b; a += s.c) {   // one run per workgroup row of the launch
+                const int b = a + s.c < s.b ? a + s.c : s.b;
+#pragma omp parallel for
+                for (long long i = 0; i < n; i++) K::expand_run(G, B, (size_t)i, a, b);
+            }
+            break;
+        case plan::EXPAND_FB_RUN:
+#pragma omp parallel for
+            for (long long i = 0; i < n; i++) K::expand_fb_run(G, B, (size_t)i, s.a);
+            break;
+        }
+    }
+}
+
+// the scratch of one emulated call, bound to B (everything but the inputs, the sink and the tables)
+struct Scratch {
+    std::vector<U256> PX, PY, PZ, PW, PREF, AX, AY;
+    std::vector<uint8_t> dig4, dig2, valid8;
+    std::vector<uint16_t> dyn, src, msrc;
+    std::vector<u32> err32;
+    Scratch(const Program& G, size_t n, Buffers& B)
+        : PX((size_t)G.num_slots * n), PY(PX.size()), PZ(PX.size()), PW((size_t)G.num_ops * n), PREF(PW.size()), AX(PX.size()), AY(PX.size()),
+          dig4((size_t)FB_WINDOWS * n), dig2((size_t)(G.cp_rows > MSM_DIGITS ? G.cp_rows : MSM_DIGITS) * n), valid8(n),
+          dyn((size_t)G.num_cadd * n + 1), src((size_t)G.num_ops * 2 * n), msrc(dig2.size()), err32(n) {
+        B.n = n;
+        B.err = err32.data(); B.valid = valid8.data();
+        B.PX = PX.data(); B.PY = PY.data(); B.PZ = PZ.data(); B.PW = PW.data(); B.PREF = PREF.data();
+        B.AX = AX.data(); B.AY = AY.data();
+        B.dig4 = dig4.data(); B.dig2 = dig2.data(); B.dyn = dyn.data(); B.src = src.data(); B.msrc = msrc.data();
+    }
+    // what k_finalize leaves: the flagged count
+    long finalize(uint8_t* err, uint8_t* valid) const {
+        long bad = 0;
+        for (size_t i = 0; i < err32.size(); i++) {
+            err[i] = (uint8_t)err32[i];
+            if (valid) valid[i] = err32[i] ? 0 : valid8[i];
+            bad += err32[i] != 0;
+        }
+        return bad;
+    }
+};
+
+// A built-in program under the plan build_builtin makes of `P` (chunk, split: exec_plan); cols != nullptr: the u64 column
+// matrix, otherwise the compact container.  -2: the record asks for a plan that build refuses.
+static long run(int program, const plan::BuiltinParams& P, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx,
+                const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int chunk, int split,
+                uint32_t* narrow = nullptr, size_t ldn = 0, uint64_t* wide = nullptr, size_t ldw = 0) {
     host::ScheduleBuilder sb;
     if (program == 0)
         sb.verify_secp256k1_message_circuit();
     else
         sb.glv_mul_circuit();
-    if (chunk < 0) run_iters = 0;   // the small-batch plan expands op by op (plain op table), as run_program() does
-    sb.mark_runs(run_iters);
+    sb.mark_runs(P.run_iters, P.fb_run);   // (as p2e_ctx_create marks the op tables: the fixed-base windows only with the fixed-base run)
     const Program& G = sb.prog;
     const host::Consts& C = host::consts();
-    std::vector<U256> PX((size_t)G.num_slots * n), PY((size_t)G.num_slots * n), PZ((size_t)G.num_slots * n),
-        PW((size_t)G.num_ops * n), PREF((size_t)G.num_ops * n), AX((size_t)G.num_slots * n), AY((size_t)G.num_slots * n);
-    std::vector<uint8_t> dig4((size_t)FB_WINDOWS * n), dig2((size_t)MSM_DIGITS * n), valid8(n);
-    std::vector<uint16_t> dyn((size_t)G.num_cadd * n), src((size_t)G.num_ops * 2 * n), msrc((size_t)MSM_DIGITS * n);
-    std::vector<u32> err32(n);
+    plan::Plan pl;
+    pl.max_seg = plan::PIECES_CAP;   // no events here: any piece count the record asks for
+    if (!plan::build_builtin(G, P, pl)) return -2;
     Buffers B{};
+    Scratch scratch(G, n, B);
     B.msg = msg; B.r = r; B.s = s; B.pkx = pkx; B.pky = pky;
     // wide_before[c] = check_sum / carry columns (33 per mul generator, after its r and q limbs) before column c
     std::vector<u32> wide_before((size_t)G.num_cols + 1, 0);
@@ -44,132 +201,26 @@ static long run(int program, const uint8_t* msg, const uint8_t* r, const uint8_t
         for (u32 k = 0; k < g.ncols; k++) wide_before[g.col + k + 1] = (g.kind == host::GEN_MUL && k >= 2 * NL) ? 1u : 0u;
     for (size_t c2 = 1; c2 < wide_before.size(); c2++) wide_before[c2] += wide_before[c2 - 1];
     B.sink = Sink{cols, ld, narrow, ldn, wide, ldw, wide_before.data()};
-    B.n = n;
-    B.err = err32.data(); B.valid = valid8.data();
-    B.PX = PX.data(); B.PY = PY.data(); B.PZ = PZ.data(); B.PW = PW.data(); B.PREF = PREF.data();
-    B.AX = AX.data(); B.AY = AY.data();
-    B.dig4 = dig4.data(); B.dig2 = dig2.data(); B.dyn = dyn.data(); B.src = src.data(); B.msrc = msrc.data();
     B.cpts = C.cpts; B.fbtab = C.fbtab.data(); B.ops = sb.ops.data();
-#pragma omp parallel for
-    for (long long i = 0; i < (long long)n; i++) body_scalar<E>(G, B, (size_t)i);
-    // same dependency order as the stream plan of p2e_hip.hip, with the MSM chain cut into `pieces` pieces whose
-    // phases B and C are interleaved with the following pieces of the chain
-    // chunk >= piece length: one batch per piece using phase A's prefix products (what the GPU launches);
-    // smaller chunks re-run the forward pass inside phase B (arbitrary batching must not change any output)
-    // chunk < 0: the small-batch plan of run_program() (quad.hpp): four lanes per signature walk the chains, the
-    // window table is walked as rows, every inversion batch is cut into -chunk sub-ranges
-    const bool quad = chunk < 0;
-    const int split = quad ? -chunk : 1;
-    auto binv = [&](int lo, int hi, bool have_prefix = true) {
-        if (quad) {
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++)
-                for (int q = 0; q < split; q++) body_batch_inv_split(G, B, (size_t)i, lo, hi, have_prefix, q, split);
-            return;
-        }
-        if (chunk >= hi - lo) {
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) body_batch_inv(G, B, (size_t)i, lo, hi, true);
-            return;
-        }
-        for (int t0 = lo; t0 < hi; t0 += chunk) {
-            int t1 = t0 + chunk < hi ? t0 + chunk : hi;
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) body_batch_inv(G, B, (size_t)i, t0, t1, false);
-        }
-    };
-    auto chain = [&](int lo, int hi, bool table_affine, bool cont = false) {
-#pragma omp parallel for
-        for (long long i = 0; i < (long long)n; i++) {
-            if (quad)   // every role walks the whole range (the host form of a level computes all four products) and
-                        // writes only its own share of the scratch outputs
-                for (int role = 0; role < 4; role++) body_chain_range_quad(G, B, (size_t)i, role, lo, hi, table_affine, cont);
-            else
-                body_chain_range(G, B, (size_t)i, lo, hi, table_affine, cont);
-        }
-    };
-    auto expand = [&](int lo, int hi) {
-#pragma omp parallel for
-        for (long long i = 0; i < (long long)n; i++)
-            for (int t = lo; t < hi; t++) body_expand<E>(G, B, (size_t)i, t);
-    };
-    auto expand_runs = [&](int it0, int it1) {
-        for (int a = it0; a < it1; a += run_iters) {
-            int b = a + run_iters < it1 ? a + run_iters : it1;
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) body_expand_run<E>(G, B, (size_t)i, a, b);
-        }
-    };
-    // the same plan as run_program() in csrc/p2e_hip.hip: fixed-base chain; window table piece (inverted
-    // before the loop, which then reads it affine); the loop cut at run boundaries into `groups` pieces whose
-    // phase C walks runs; the trailing unblinding add and the final add op by op
-    if (G.num_chains == 3) {
-        chain(G.chain_begin[1], G.chain_end[1], false);
-        binv(G.chain_begin[1], G.chain_end[1]);
-        if (run_iters > 0 && !quad) {   // the windows as one run per signature, then the unblinding add (k_expand_fb_run)
-            const int t_after = G.fb_begin + G.fb_windows;
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) body_expand_fb_run<E>(G, B, (size_t)i, t_after);
-            expand(t_after, G.chain_end[1]);
-        } else {
-            expand(G.chain_begin[1], G.chain_end[1]);
-        }
-    }
-    {
-        const int lo0 = G.chain_begin[0], hi0 = G.chain_end[0], lb = G.msm_loop_begin, iters = G.msm_loop_iters;
-        const int le = lb + 3 * iters, R = run_iters > 0 ? run_iters : 1, groups = 3;
-        if (G.num_chains == 1 || quad) {
-            // glv_mul alone (and small batches): the window table as rows of independent sub-chains, as the GPU walks it there
-            // (body_chain_rows), prefix products left to phase B
-            auto rows = [&](int lo, int nrows, int count) {
-#pragma omp parallel for
-                for (long long i = 0; i < (long long)n; i++)
-                    for (int r = 0; r < nrows; r++) body_chain_rows(G, B, (size_t)i, lo, nrows, r, count);
-            };
-            rows(lo0, 2, 4);
-            rows(lo0 + 8, 6, 1);
-            rows(lo0 + 14, 9, 1);
-            if (quad) {
-                binv(lo0, lb, false);
-            } else {
-#pragma omp parallel for
-                for (long long i = 0; i < (long long)n; i++) body_batch_inv(G, B, (size_t)i, lo0, lb, false);
-            }
-        } else {
-            chain(lo0, lb, false);
-            binv(lo0, lb);
-        }
-        expand(lo0, lb);
-        const int nruns = (iters + R - 1) / R;
-        int rn = 0;
-        for (int g = 0; g < groups; g++) {
-            int take = (nruns - rn + (groups - g) - 1) / (groups - g);
-            int it0 = rn * R, it1 = (rn + take) * R < iters ? (rn + take) * R : iters;
-            int a = lb + 3 * it0, b = lb + 3 * it1;
-            const bool last = g == groups - 1;
-            if (last) b = hi0;
-            chain(a, b, true);
-            if (last && G.num_chains == 3) {
-                chain(G.chain_begin[2], G.chain_end[2], false, true);
-                b = G.chain_end[2];
-            }
-            binv(a, b);
-            if (run_iters > 0) {
-                expand_runs(it0, it1);
-                if (last) expand(le, b);
-            } else {
-                expand(a, b);
-            }
-            rn += take;
-        }
-    }
-    long bad = 0;
-    for (size_t i = 0; i < n; i++) {
-        err[i] = (uint8_t)err32[i];
-        if (valid) valid[i] = err32[i] ? 0 : valid8[i];
-        bad += err32[i] != 0;
-    }
-    return bad;
+    if (cols)
+        exec_plan<BuiltinBodies<Emit>>(pl, G, B, chunk, split);
+    else
+        exec_plan<BuiltinBodies<CompactEmit>>(pl, G, B, chunk, split);
+    return scratch.finalize(err, valid);
+}
+// the record of the emu_verify / emu_glv_mul family: the loop in 3 pieces of runs of `run_iters` iterations (0: op by
+// op), the fixed-base chain as one piece (with runs: its windows as one run per signature); chunk < 0: the four-lane
+// plan with every inversion batch cut into -chunk sub-ranges
+static long run_legacy(int program, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx, const uint8_t* pky,
+                       uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int chunk, int run_iters, uint32_t* narrow = nullptr,
+                       size_t ldn = 0, uint64_t* wide = nullptr, size_t ldw = 0) {
+    plan::BuiltinParams P;
+    P.quad = P.alt_b = chunk < 0;
+    P.run_iters = run_iters;
+    P.ops = run_iters > 0 ? plan::OPS_RUNS : plan::OPS_PLAIN;
+    P.msm_pieces = 4;
+    P.fb_run = run_iters > 0 && !P.quad && program == 0;
+    return run(program, P, msg, r, s, pkx, pky, cols, n, ld, err, valid, chunk, chunk < 0 ? -chunk : 0, narrow, ldn, wide, ldw);
 }
 
 // ---- fe29.hpp (lazy 29-bit limbs) against fe.hpp (canonical words): every operation on patterned and random values,
@@ -419,7 +470,7 @@ long emu_tuning(const char* const* names, const char* const* values, size_t coun
 }
 long emu_verify(const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx, const uint8_t* pky,
                 uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int chunk, int run_iters) {
-    return run<Emit>(0, msg, r, s, pkx, pky, cols, n, ld, err, valid, chunk, run_iters);
+    return run_legacy(0, msg, r, s, pkx, pky, cols, n, ld, err, valid, chunk, run_iters);
 }
 // verdict only (p2e_ecdsa_verify_batch): scalar phase without emission, Jacobian chains, r == x on the Jacobian result
 long emu_verify_only(const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx, const uint8_t* pky, size_t n,
@@ -428,18 +479,9 @@ long emu_verify_only(const uint8_t* msg, const uint8_t* r, const uint8_t* s, con
     sb.verify_secp256k1_message_circuit();
     const Program& G = sb.prog;
     const host::Consts& C = host::consts();
-    std::vector<U256> PX((size_t)G.num_slots * n), PY((size_t)G.num_slots * n), PZ((size_t)G.num_slots * n),
-        PW((size_t)G.num_ops * n), PREF((size_t)G.num_ops * n), AX((size_t)G.num_slots * n), AY((size_t)G.num_slots * n);
-    std::vector<uint8_t> dig4((size_t)FB_WINDOWS * n), dig2((size_t)MSM_DIGITS * n), valid8(n);
-    std::vector<uint16_t> dyn((size_t)G.num_cadd * n), src((size_t)G.num_ops * 2 * n), msrc((size_t)MSM_DIGITS * n);
-    std::vector<u32> err32(n);
     Buffers B{};
+    Scratch scratch(G, n, B);
     B.msg = msg; B.r = r; B.s = s; B.pkx = pkx; B.pky = pky;
-    B.n = n;
-    B.err = err32.data(); B.valid = valid8.data();
-    B.PX = PX.data(); B.PY = PY.data(); B.PZ = PZ.data(); B.PW = PW.data(); B.PREF = PREF.data();
-    B.AX = AX.data(); B.AY = AY.data();
-    B.dig4 = dig4.data(); B.dig2 = dig2.data(); B.dyn = dyn.data(); B.src = src.data(); B.msrc = msrc.data();
     B.cpts = C.cpts; B.fbtab = C.fbtab.data(); B.ops = sb.ops.data();
 #pragma omp parallel for
     for (long long i = 0; i < (long long)n; i++) {
@@ -449,27 +491,21 @@ long emu_verify_only(const uint8_t* msg, const uint8_t* r, const uint8_t* s, con
         body_chain_range(G, B, (size_t)i, G.chain_begin[2], G.chain_end[2], false, false);
         body_verify_check(G, B, (size_t)i);
     }
-    long bad = 0;
-    for (size_t i = 0; i < n; i++) {
-        err[i] = (uint8_t)err32[i];
-        valid[i] = err32[i] ? 0 : valid8[i];
-        bad += err32[i] != 0;
-    }
-    return bad;
+    return scratch.finalize(err, valid);
 }
 // the same walk writing the compact container directly (CompactEmit: what the compact kernels' ragged tail runs)
 long emu_verify_compact(const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx, const uint8_t* pky,
                         uint32_t* narrow, size_t ldn, uint64_t* wide, size_t ldw, size_t n, uint8_t* err, uint8_t* valid,
                         int run_iters) {
-    return run<CompactEmit>(0, msg, r, s, pkx, pky, nullptr, n, 0, err, valid, 512, run_iters, narrow, ldn, wide, ldw);
+    return run_legacy(0, msg, r, s, pkx, pky, nullptr, n, 0, err, valid, 512, run_iters, narrow, ldn, wide, ldw);
 }
 long emu_glv_mul_compact(const uint8_t* px, const uint8_t* py, const uint8_t* k, uint32_t* narrow, size_t ldn, uint64_t* wide,
                          size_t ldw, size_t n, uint8_t* err, uint8_t* valid, int run_iters) {
-    return run<CompactEmit>(1, k, k, k, px, py, nullptr, n, 0, err, valid, 512, run_iters, narrow, ldn, wide, ldw);
+    return run_legacy(1, k, k, k, px, py, nullptr, n, 0, err, valid, 512, run_iters, narrow, ldn, wide, ldw);
 }
 long emu_glv_mul(const uint8_t* px, const uint8_t* py, const uint8_t* k, uint64_t* cols, size_t n, size_t ld,
                  uint8_t* err, uint8_t* valid, int chunk, int run_iters) {
-    return run<Emit>(1, k, k, k, px, py, cols, n, ld, err, valid, chunk, run_iters);
+    return run_legacy(1, k, k, k, px, py, cols, n, ld, err, valid, chunk, run_iters);
 }
 // built-in-generator columns from a finished witness matrix (aux.hpp: the body k_aux runs)
 long emu_aux(int program, const uint8_t* pky, const uint64_t* cols, size_t ld, uint64_t* aux, size_t ald, size_t n,
@@ -630,122 +666,42 @@ long emu_split(const uint8_t* packed, u64* limbs, size_t n, size_t ld) {
 long emu_pack(const u64* limbs, uint8_t* packed, size_t n, size_t ld, uint8_t* err) { LOOP(prim_pack(limbs, packed, ld, i)) }
 }
 
-// ---- curve programs (curves.hpp): the bodies kc_scalar / kc_chains / kc_batch_inv / kc_expand run, in the piece order
-// of run_curve_program (pieces of `piece` ops, the per-signature table as its own piece and affine afterwards) --------
+// ---- curve programs (curves.hpp): the bodies kc_scalar / kc_chains / kc_batch_inv / kc_expand run, under the plan
+// build_curve makes of `P` (csrc/launch_plan.hpp).  -2: the record asks for a plan that build refuses. ----------------
 template <class CV>
-static long run_curve(const host::CurveProgramHost& H, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx,
-                      const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, int piece,
+static long run_curve(const host::CurveProgramHost& H, const plan::CurveParams& P, const uint8_t* msg, const uint8_t* r, const uint8_t* s,
+                      const uint8_t* pkx, const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid,
                       const uint8_t* qx = nullptr, const uint8_t* qy = nullptr) {
     const host::ScheduleBuilder& sb = H.sb;
     const Program& G = sb.prog;
-    const size_t rows = (size_t)(G.cp_rows > MSM_DIGITS ? G.cp_rows : MSM_DIGITS);
-    std::vector<U256> PX((size_t)G.num_slots * n), PY((size_t)G.num_slots * n), PZ((size_t)G.num_slots * n),
-        PW((size_t)G.num_ops * n), PREF((size_t)G.num_ops * n), AX((size_t)G.num_slots * n), AY((size_t)G.num_slots * n);
-    std::vector<uint8_t> dig4((size_t)FB_WINDOWS * n), dig2(rows * n), valid8(n);
-    std::vector<uint16_t> dyn((size_t)G.num_cadd * n + 1), src((size_t)G.num_ops * 2 * n), msrc(rows * n);
-    std::vector<u32> err32(n);
+    plan::Plan pl;
+    pl.max_seg = plan::PIECES_CAP;   // no events here: any piece count the record asks for
+    if (!plan::build_curve(G, P, pl)) return -2;
+    if (P.runs && G.msm_loop_iters > 0 && G.loop_dbls != 2 && G.loop_dbls != 4) return -2;
     Buffers B{};
+    Scratch scratch(G, n, B);
     B.msg = msg; B.r = r; B.s = s; B.pkx = pkx; B.pky = pky;
     B.qx = qx; B.qy = qy;   // the MSM program's second point (null for every other program)
     B.sink = Sink{cols, ld, nullptr, 0, nullptr, 0, nullptr};
-    B.n = n;
-    B.err = err32.data(); B.valid = valid8.data();
-    B.PX = PX.data(); B.PY = PY.data(); B.PZ = PZ.data(); B.PW = PW.data(); B.PREF = PREF.data();
-    B.AX = AX.data(); B.AY = AY.data();
-    B.dig4 = dig4.data(); B.dig2 = dig2.data(); B.dyn = dyn.data(); B.src = src.data(); B.msrc = msrc.data();
     B.cpts = sb.gpts.data(); B.fbtab = sb.gfbtab.data(); B.ops = sb.ops.data();
-#pragma omp parallel for
-    for (long long i = 0; i < (long long)n; i++) body_cscalar<CV, Emit>(G, B, (size_t)i);
-    int tb = -1, te = -1;
-    if (G.cp_table_ops > 0) {
-        te = 0;
-        for (int k = 1; k < 16; k++) te = std::max(te, (int)ref_id(G.msm_tab[k]) + 1);
-        tb = te - G.cp_table_ops;
-    }
-    bool table_done = false;
-    auto chain_binv = [&](int lo, int hi, bool table_affine) {
-#pragma omp parallel for
-        for (long long i = 0; i < (long long)n; i++) {
-            body_chain_range<CV, true>(G, B, (size_t)i, lo, hi, table_affine, false);
-            body_batch_inv<CV>(G, B, (size_t)i, lo, hi, true);
-        }
-    };
-    auto expand = [&](int lo, int hi) {
-#pragma omp parallel for
-        for (long long i = 0; i < (long long)n; i++)
-            for (int t = lo; t < hi; t++) body_expand<Emit, CV>(G, B, (size_t)i, t);
-    };
     host::ScheduleBuilder marked;
-    if (piece < 0) {
-        // the large-batch plan of run_curve_program: runs of -piece windows (op table with the run marks), the verifier's
-        // fixed-base windows as one run per signature; the op stride of a loop iteration is its doublings + the
-        // conditional add (4 + 1 in the windowed loop, 2 + 1 in the MSM program's digit loop)
-        const int R = -piece, lb = G.msm_loop_begin, iters = G.msm_loop_iters, stride = G.loop_dbls + 1, le = lb + stride * iters;
+    if (pl.ops == plan::OPS_RUNS) {   // the op table with the run marks
         marked = sb;
-        marked.mark_runs(R);
+        marked.mark_runs(P.run_iters);
         B.ops = marked.ops.data();
-        if (iters == 0) {
-            // the fixed-base program: one piece, its windows as one run per element, then the unblinding add
-            if (G.fb_begin != 0) return -2;
-            const int t_after = G.fb_begin + G.fb_windows;
-            chain_binv(G.fb_begin, G.num_ops, false);
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) body_expand_fb_run<Emit, CV>(G, B, (size_t)i, t_after);
-            expand(t_after, G.num_ops);
-        }
-        if (iters > 0 && G.loop_dbls != 2 && G.loop_dbls != 4) return -2;
-        if (iters > 0 && G.fb_begin >= 0) {
-            const int fe = G.fb_begin + G.fb_windows + 1;
-            chain_binv(G.fb_begin, fe, false);
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) body_expand_fb_run<Emit, CV>(G, B, (size_t)i, fe - 1);
-            expand(fe - 1, fe);
-        }
-        if (iters > 0) {
-            chain_binv(tb, te, false);
-            expand(tb, te);
-        }
-        for (int it = 0; it < iters; it += R) {
-            const int it1 = std::min(it + R, iters);
-            const int hi = it1 == iters ? G.num_ops : lb + stride * it1;
-            chain_binv(lb + stride * it, hi, true);
-#pragma omp parallel for
-            for (long long i = 0; i < (long long)n; i++) {
-                if (G.loop_dbls == 2)   // kc_expand_runs2
-                    body_expand_run<Emit, CV, 2>(G, B, (size_t)i, it, it1);
-                else                    // kc_expand_runs
-                    body_expand_run<Emit, CV, 4>(G, B, (size_t)i, it, it1);
-            }
-            if (it1 == iters) expand(le, G.num_ops);
-        }
-    } else {
-        auto run_piece = [&](int lo, int hi, bool table) {
-            chain_binv(lo, hi, table_done);
-            expand(lo, hi);
-            if (table) table_done = true;
-        };
-        auto cut = [&](int lo, int hi, bool table) {
-            if (table) {
-                run_piece(lo, hi, true);
-                return;
-            }
-            for (int a2 = lo; a2 < hi; a2 += piece) run_piece(a2, a2 + piece < hi ? a2 + piece : hi, false);
-        };
-        if (tb >= 0) {
-            cut(0, tb, false);
-            cut(tb, te, true);
-            cut(te, G.num_ops, false);
-        } else {
-            cut(0, G.num_ops, false);
-        }
     }
-    long bad = 0;
-    for (size_t i = 0; i < n; i++) {
-        err[i] = (uint8_t)err32[i];
-        valid[i] = err32[i] ? 0 : valid8[i];
-        bad += err32[i] != 0;
-    }
-    return bad;
+    exec_plan<CurveBodies<CV, Emit>>(pl, G, B, 0, 0);
+    return scratch.finalize(err, valid);
+}
+// the record of emu_curve_program / emu_curve_msm: pieces of `piece` ops expanded op by op on one chain stream, or
+// (piece < 0) the run plan with -piece loop iterations per run
+static plan::CurveParams curve_legacy_params(int piece) {
+    plan::CurveParams P;
+    if (piece == 0) piece = 32;
+    P.runs = piece < 0;
+    P.run_iters = piece < 0 ? -piece : 0;
+    P.piece_ops = piece > 0 ? piece : plan::CP_PIECE_OPS;
+    return P;
 }
 extern "C" {
 // kind / curve: include/p2e.h P2E_CP_* / P2E_CURVE_*; blind: the gadget's rand() point.  Returns the flagged count, or
@@ -762,9 +718,82 @@ long emu_curve_program(int kind, int curve, const uint8_t* blind_x, const uint8_
     if (num_gens) *num_gens = (long)H.sb.gens.size();
     if (num_aux) *num_aux = (long)H.sb.aux_tab.num_aux_cols;
     if (n == 0) return 0;
-    if (piece == 0) piece = 32;   // piece < 0: the run plan with -piece windows per run
-    if (curve == 1) return run_curve<P256>(H, msg, r, s, pkx, pky, cols, n, ld, err, valid, piece);
-    return run_curve<Secp256k1>(H, msg, r, s, pkx, pky, cols, n, ld, err, valid, piece);
+    const plan::CurveParams P = curve_legacy_params(piece);   // piece < 0: the run plan with -piece windows per run
+    if (curve == 1) return run_curve<P256>(H, P, msg, r, s, pkx, pky, cols, n, ld, err, valid);
+    return run_curve<Secp256k1>(H, P, msg, r, s, pkx, pky, cols, n, ld, err, valid);
+}
+// ---- launch plans (csrc/launch_plan.hpp) ------------------------------------------------------------------------------
+// choose + build with the knobs and per-call switches read from `count` (name, value) pairs instead of the environment
+// (P2E_STREAM_LAYOUT and P2E_QUAD_EXPAND_CUS as p2e_ctx_create reads them), for a call of n elements: the plan's text
+// form in out[0..cap), its length returned; -(plan::Error) where build refuses.  family 0: built-in program `prog`;
+// family 1: curve program of kind `prog` on `curve` (blind: the gadget's rand() point).  shape (optional) receives
+// num_ops, fb_begin, fb_windows, msm_loop_begin, msm_loop_iters, ops per loop iteration, plan::MAX_SEG, plan::MAX_EXPAND.
+long emu_plan_dump(int family, int prog, int curve, const uint8_t* blind_x, const uint8_t* blind_y, size_t n, const char* const* names,
+                   const char* const* values, size_t count, int timing, char* out, size_t cap, int32_t* shape) {
+    auto env = [&](const char* name) -> const char* {
+        for (size_t k = 0; k < count; k++)
+            if (!std::strcmp(names[k], name)) return values[k];
+        return nullptr;
+    };
+    Tuning t;
+    read_tuning(t, env);
+    const char* layout = env("P2E_STREAM_LAYOUT");
+    if (!layout || !*layout) layout = "M1FB2";
+    const char* cus = env("P2E_QUAD_EXPAND_CUS");
+    const plan::Layout L{std::strchr(layout, '1') != nullptr, cus && atoi(cus) > 0};
+    host::CurveProgramHost H;
+    host::ScheduleBuilder& sb = H.sb;
+    if (family == 0) {
+        if (prog == 0)
+            sb.verify_secp256k1_message_circuit();
+        else
+            sb.glv_mul_circuit();
+    } else {
+        Aff blind;
+        memcpy(blind.x.w, blind_x, 32);
+        memcpy(blind.y.w, blind_y, 32);
+        if (!host::make_curve_program(H, prog, curve, blind)) return -100;
+    }
+    const Program& G = sb.prog;
+    if (shape) {
+        const int32_t v[8] = {G.num_ops, G.fb_begin, G.fb_windows, G.msm_loop_begin, G.msm_loop_iters, family == 0 ? 3 : G.loop_dbls + 1,
+                              plan::MAX_SEG, plan::MAX_EXPAND};
+        memcpy(shape, v, sizeof v);
+    }
+    static plan::Plan pl;   // (test infrastructure: called from one thread)
+    const bool ok = family == 0 ? plan::build_builtin(G, plan::choose_builtin(G, t, n, L, timing != 0), pl)
+                                : plan::build_curve(G, plan::choose_curve(G, t, n, G.msm_loop_iters > 0 || prog == CP_FIXED_BASE_MUL, L,
+                                                                          timing != 0, read_call_switches(env)), pl);
+    if (!ok) return -(long)pl.error;
+    return (long)plan::dump(pl, out, cap);
+}
+// The plan a call of `nominal` elements launches under the default knobs (default stream layout), executed on the n
+// elements given: what lets a CPU test run the plan of a 2^16 call on a few signatures.
+// cols != nullptr: the u64 column matrix, otherwise the compact container.
+long emu_builtin_nominal(int program, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx, const uint8_t* pky,
+                         uint64_t* cols, size_t ld, uint32_t* narrow, size_t ldn, uint64_t* wide, size_t ldw, size_t n, uint8_t* err,
+                         uint8_t* valid, size_t nominal) {
+    host::ScheduleBuilder sb;
+    if (program == 0)
+        sb.verify_secp256k1_message_circuit();
+    else
+        sb.glv_mul_circuit();
+    const plan::BuiltinParams P = plan::choose_builtin(sb.prog, Tuning{}, nominal, plan::Layout{true, false}, false);
+    return run(program, P, msg, r, s, pkx, pky, cols, n, ld, err, valid, 0, 0, narrow, ldn, wide, ldw);
+}
+long emu_curve_program_nominal(int kind, int curve, const uint8_t* blind_x, const uint8_t* blind_y, const uint8_t* msg, const uint8_t* r,
+                               const uint8_t* s, const uint8_t* pkx, const uint8_t* pky, uint64_t* cols, size_t n, size_t ld, uint8_t* err,
+                               uint8_t* valid, size_t nominal) {
+    Aff blind;
+    memcpy(blind.x.w, blind_x, 32);
+    memcpy(blind.y.w, blind_y, 32);
+    host::CurveProgramHost H;
+    if (!host::make_curve_program(H, kind, curve, blind)) return -1;
+    const Program& G = H.sb.prog;
+    const plan::CurveParams P = plan::choose_curve(G, Tuning{}, nominal, G.msm_loop_iters > 0 || kind == CP_FIXED_BASE_MUL,
+                                                   plan::Layout{true, false}, false, CallSwitches{});
+    if (curve == 1) return run_curve<P256>(H, P, msg, r, s, pkx, pky, cols, n, ld, err, valid);
+    return run_curve<Secp256k1>(H, P, msg, r, s, pkx, pky, cols, n, ld, err, valid);
 }
 // P2E_CP_MSM: curve_msm_circuit(p, q, n, m); as emu_curve_program with the second point (the program takes no blinding point)
 long emu_curve_msm(int curve, const uint8_t* px, const uint8_t* py, const uint8_t* qx, const uint8_t* qy, const uint8_t* n_scalar,
@@ -772,9 +801,9 @@ long emu_curve_msm(int curve, const uint8_t* px, const uint8_t* py, const uint8_
     host::CurveProgramHost H;
     if (!host::make_curve_program(H, CP_MSM, curve, Aff{})) return -1;
     if (n == 0) return 0;
-    if (piece == 0) piece = 32;
-    if (curve == 1) return run_curve<P256>(H, n_scalar, m_scalar, n_scalar, px, py, cols, n, ld, err, valid, piece, qx, qy);
-    return run_curve<Secp256k1>(H, n_scalar, m_scalar, n_scalar, px, py, cols, n, ld, err, valid, piece, qx, qy);
+    const plan::CurveParams P = curve_legacy_params(piece);
+    if (curve == 1) return run_curve<P256>(H, P, n_scalar, m_scalar, n_scalar, px, py, cols, n, ld, err, valid, qx, qy);
+    return run_curve<Secp256k1>(H, P, n_scalar, m_scalar, n_scalar, px, py, cols, n, ld, err, valid, qx, qy);
 }
 // generator table (kind, field, first column, column count) and operand wiring of a curve program, for the host tests
 long emu_curve_program_gens(int kind, int curve, const uint8_t* blind_x, const uint8_t* blind_y, int32_t* kinds, int32_t* fields,
@@ -950,19 +979,9 @@ long emu_p256_verify_only(const uint8_t* blind_x, const uint8_t* blind_y, const 
     if (!host::make_curve_program(H, CP_VERIFY, 1, blind)) return -1;
     const host::ScheduleBuilder& sb = H.sb;
     const Program& G = sb.prog;
-    const size_t rows = (size_t)(G.cp_rows > MSM_DIGITS ? G.cp_rows : MSM_DIGITS);
-    std::vector<U256> PX((size_t)G.num_slots * n), PY((size_t)G.num_slots * n), PZ((size_t)G.num_slots * n),
-        PW((size_t)G.num_ops * n), PREF((size_t)G.num_ops * n), AX((size_t)G.num_slots * n), AY((size_t)G.num_slots * n);
-    std::vector<uint8_t> dig4((size_t)FB_WINDOWS * n), dig2(rows * n), valid8(n);
-    std::vector<uint16_t> dyn((size_t)G.num_cadd * n + 1), src((size_t)G.num_ops * 2 * n), msrc(rows * n);
-    std::vector<u32> err32(n);
     Buffers B{};
+    Scratch scratch(G, n, B);
     B.msg = msg; B.r = r; B.s = s; B.pkx = pkx; B.pky = pky;
-    B.n = n;
-    B.err = err32.data(); B.valid = valid8.data();
-    B.PX = PX.data(); B.PY = PY.data(); B.PZ = PZ.data(); B.PW = PW.data(); B.PREF = PREF.data();
-    B.AX = AX.data(); B.AY = AY.data();
-    B.dig4 = dig4.data(); B.dig2 = dig2.data(); B.dyn = dyn.data(); B.src = src.data(); B.msrc = msrc.data();
     B.cpts = sb.gpts.data(); B.fbtab = sb.gfbtab.data(); B.ops = sb.ops.data();
     const int fb_end = G.fb_begin + G.fb_windows + 1;
 #pragma omp parallel for
@@ -973,13 +992,7 @@ long emu_p256_verify_only(const uint8_t* blind_x, const uint8_t* blind_y, const 
         body_chain_range<P256, true>(G, B, (size_t)i, G.num_ops - 1, G.num_ops, false, false);
         body_verify_check<P256>(G, B, (size_t)i, G.num_ops - 1);
     }
-    long bad = 0;
-    for (size_t i = 0; i < n; i++) {
-        err[i] = (uint8_t)err32[i];
-        valid[i] = err32[i] ? 0 : valid8[i];
-        bad += err32[i] != 0;
-    }
-    return bad;
+    return scratch.finalize(err, valid);
 }
 int emu_synth_signatures_curve(int curve, uint64_t seed, size_t first, size_t n, uint8_t* msg32, uint8_t* r32, uint8_t* s32,
                                uint8_t* pkx32, uint8_t* pky32) {

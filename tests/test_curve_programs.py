@@ -503,6 +503,31 @@ def _gpu_run(gpu, name_or_kind, curve, blind_i, args):
     return prog, out
 
 
+@pytest.mark.parametrize("nominal", [1 << 13, 1 << 16], ids=["four_lane_8192", "runs_65536"])
+def test_p256_verifier_bodies_under_the_plan_of_a_nominal_batch(emu, nominal):
+    """choose_curve with the default knobs for `nominal` elements, build_curve, and the compute steps of that plan executed in
+    list order on 96 rows (emu_curve_program_nominal): 64 synthetic P-256 signatures with 32 adversarial rows in their middle.
+    8 192: the four-lane plan (45-op pieces, a 17-op tail, the first piece after the table reading it in Jacobian form, split
+    inversion batches); 65 536: the run plan.  Columns of every row the reference does not panic on, err bytes, verdicts."""
+    import adversarial_inputs as A
+    import oracle_c
+    import plan_cases
+    import plonky2_ecdsa_amd as p2e
+    arrs = plan_cases.mixed_batch("verify", 1, p2e.synth_signatures_curve(1, 23, 64))
+    want, _aux, werr, wverdict = oracle_c.curve_program(oracle_c.CP_VERIFY, 1, A.blind(1), arrs)
+    assert 0 < int((werr != 0).sum()) <= 8
+    b = A.arrays([A.Case("blind", A.blind(1), False, None)])
+    n = arrs[0].shape[0]
+    cols, err, valid = np.zeros((want.shape[0], n), np.uint64), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    emu.L.emu_curve_program_nominal.restype = C.c_long
+    bad = emu.L.emu_curve_program_nominal(3, 1, emu._p(b[0][0]), emu._p(b[1][0]), *[emu._p(a) for a in arrs], emu._p(cols), C.c_size_t(n),
+                                          C.c_size_t(n), emu._p(err), emu._p(valid), C.c_size_t(nominal))
+    clean = werr == 0
+    assert bad == int((werr != 0).sum()) and np.array_equal(err, werr)
+    assert np.array_equal(valid[clean], wverdict[clean]) and not valid[~clean].any()
+    assert np.array_equal(cols[:, clean], want[:, clean])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", PROGRAMS)
 def test_gpu_matches_the_goldens(name, gpu):

@@ -464,3 +464,45 @@ def test_gate_internal_values_match_the_replay_model(program):
         assert ne in (0, 1) and chk == ne and dn == diff and diff < 16 and (diff * inv - ne) % R.P_GL == 0
         bits = blk[5:] if w < n_fb else blk[:72]
         assert all(sum(int(b) << k for k, b in enumerate(bits[4 * j:4 * j + 4])) == diff for j in range(18))
+
+
+# ---- the kernel bodies under the plans the library really launches (csrc/launch_plan.hpp) ------------------------------
+@pytest.fixture(scope="module", params=["verify", "glv_mul"])
+def mixed(request):
+    """(program id, 96 mixed rows, the C oracle's columns, err bytes and verdicts), one walk per program"""
+    import plan_cases
+    from test_adversarial_cpu import oracle
+    program = request.param
+    sig = p2e.synth_signatures(seed=23, n=64)
+    arrs = plan_cases.mixed_batch(program, 0, sig if program == "verify" else (sig[3], sig[4], sig[0]))
+    cols, _aux, err, verdict = oracle(program, 0, arrs)
+    assert 0 < int((err != 0).sum()) <= 8
+    return (0 if program == "verify" else 1), arrs, cols, err, verdict
+
+
+@pytest.mark.parametrize("container", ["u64", "compact"])
+@pytest.mark.parametrize("nominal", [1 << 13, 1 << 15, 1 << 16], ids=["four_lane_8192", "mid_32768", "large_65536"])
+def test_kernel_bodies_under_the_plan_of_a_nominal_batch(mixed, nominal, container):
+    """choose with the default knobs for `nominal` elements, build, and the compute steps of that plan executed in list order on
+    96 rows (emu_builtin_nominal): the very cut, op table, run lengths, inversion splits and table form (the four-lane plan's
+    first loop piece reads the window table in Jacobian form) of a 2^13 / 2^15 / 2^16 call.  Every column of every row the
+    reference does not panic on, every err byte and every verdict equal the C oracle's."""
+    import ctypes as C
+    pid, arrs, want, werr, wverdict = mixed
+    L = EmuBackend().L
+    L.emu_builtin_nominal.restype = C.c_long
+    n = arrs[0].shape[0]
+    ins = [a.ctypes.data_as(C.c_void_p) for a in (arrs if pid == 0 else (arrs[2], arrs[2], arrs[2], arrs[0], arrs[1]))]
+    err, valid = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    _map, nn, nw = p2e.compact_layout(pid)
+    cols, narrow, wide = np.zeros((want.shape[0], n), np.uint64), np.zeros((nn, n), np.uint32), np.zeros((nw, n), np.uint64)
+    u64 = container == "u64"
+    bad = L.emu_builtin_nominal(C.c_int(pid), *ins, cols.ctypes.data_as(C.c_void_p) if u64 else None, C.c_size_t(n),
+                                None if u64 else narrow.ctypes.data_as(C.c_void_p), C.c_size_t(n),
+                                None if u64 else wide.ctypes.data_as(C.c_void_p), C.c_size_t(n), C.c_size_t(n),
+                                err.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p), C.c_size_t(nominal))
+    got = cols if u64 else p2e.compact_expand(pid, narrow, wide)
+    clean = werr == 0
+    assert bad == int((werr != 0).sum()) and np.array_equal(err, werr)
+    assert np.array_equal(valid[clean], wverdict[clean]) and (pid != 0 or not valid[~clean].any())
+    assert np.array_equal(np.asarray(got)[:, clean], want[:, clean])

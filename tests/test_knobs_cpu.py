@@ -98,3 +98,108 @@ def test_every_knob_at_once(tuning):
     want = {field: hi for _n, field, _lo, hi in RANGED}
     want.update(fb_run=1, quad_max_n=0, cp_quad_max_n=0, expand_lds=1000, small_takes=[3, 2] + [0] * 15)
     assert tuning(**env) == _expect(**want)
+
+
+# ---- the launch plans choose + build make of the knobs (csrc/launch_plan.hpp) ---------------------------------------------
+import plan_cases
+
+CASES = plan_cases.cases()
+PIECE_OPS = [dict(id=f"curve:{program}:piece_ops_{v}", family=1, prog=kind, curve=curve, env={"P2E_CP_PIECE_OPS_QUAD": str(v)}, n=plan_cases.N,
+                  timing=False) for program, (kind, curve) in plan_cases.CURVE_PROGRAMS.items() for v in (8, 20, 45)]
+TOO_MANY_PIECES = -1   # -(plan::TOO_MANY_PIECES)
+
+
+@pytest.fixture(scope="module")
+def plans():
+    subprocess.check_call(["make", "-s", "-C", HERE])
+    return plan_cases.Plans()
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return plan_cases.golden()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
+def test_plan_is_the_sequence_the_library_issued_before_plans_were_data(plans, golden, case):
+    """tests/golden/launch_plans.txt.gz: every kernel launch, event record and stream wait of one call per case, recorded on a GPU
+    from the library as it was when run_program / run_curve_program issued them from control flow.  choose + build, dumped in
+    the same text form, is that sequence line for line."""
+    lines, _shape = plans.of(case)
+    assert lines == golden[case["id"]]
+
+
+def test_the_fixture_holds_exactly_the_case_table(golden):
+    assert sorted(golden) == sorted(c["id"] for c in CASES)
+
+
+def _fields(line):
+    kind, *kv = line.split()
+    return kind, dict(x.split("=") for x in kv)
+
+
+def _check_sound(lines, shape):
+    """every WAIT names an event an earlier step of the list records; the CHAIN steps, the BINV steps and the expansion steps
+    each cover the ops of the program exactly once; no piece or expansion index beyond what the context has events for"""
+    num_ops, fb_begin, fb_windows, loop_begin, loop_iters, stride, max_seg, max_expand = shape
+    recorded = set()
+    cover = {k: [0] * num_ops for k in ("CHAIN", "BINV", "EXPAND")}
+
+    def mark(what, lo, hi):
+        assert 0 <= lo < hi <= num_ops, (what, lo, hi)
+        for t in range(lo, hi):
+            cover[what][t] += 1
+
+    kind, end = _fields(lines[-1])
+    assert kind == "END" and 0 < int(end["n_seg"]) <= max_seg
+    for line in lines[:-1]:
+        kind, f = _fields(line)
+        if kind in ("RECORD", "WAIT"):
+            name, _, idx = f["ev"].partition("[")
+            if idx:
+                assert int(idx[:-1]) < (max_seg if name in ("piece", "binv") else max_expand), line
+            if kind == "RECORD":
+                recorded.add(f["ev"])
+            else:
+                assert f["ev"] in recorded, line + ": nothing before it records that event"
+        elif kind == "CHAIN":
+            lo = int(f["lo"])
+            mark("CHAIN", lo, lo + int(f["rows"]) * int(f["count"]) if f["form"] == "rows" else int(f["hi"]))
+        elif kind == "BINV":
+            mark("BINV", int(f["lo"]), int(f["hi"]))
+        elif kind == "EXPAND_OPS":
+            mark("EXPAND", int(f["s_lo"]), int(f["s_hi"]))
+        elif kind == "EXPAND_RUNS":
+            assert int(f["run_iters"]) > 0 and 0 <= int(f["it0"]) < int(f["it1"]) <= loop_iters
+            mark("EXPAND", loop_begin + stride * int(f["it0"]), loop_begin + stride * int(f["it1"]))
+        elif kind == "EXPAND_FB_RUN":
+            assert int(f["t_after"]) == fb_begin + fb_windows
+            mark("EXPAND", fb_begin, fb_begin + fb_windows)
+        else:
+            assert kind in ("SCALAR", "FINALIZE"), line
+    for what, c in cover.items():
+        assert c == [1] * num_ops, (what, [t for t in range(num_ops) if c[t] != 1][:8])
+
+
+@pytest.mark.parametrize("case", CASES + PIECE_OPS, ids=[c["id"] for c in CASES + PIECE_OPS])
+def test_plan_is_sound(plans, case):
+    """(a wait on an event this call has not recorded is no error to HIP: it counts as satisfied -- a silent race; a piece
+    beyond the capacity was once dropped silently.)  Where the pieces would not fit, build must refuse: pieces of p ops make at
+    least ceil(ops / p) of them and, with the table and the tail cut separately, at most four more."""
+    lines, shape = plans.of(case)
+    num_ops, max_seg = shape[0], shape[6]
+    piece_ops = int(case["env"].get("P2E_CP_PIECE_OPS_QUAD", 0))
+    least = -(-num_ops // piece_ops) if piece_ops else 0
+    if least > max_seg:
+        assert lines == TOO_MANY_PIECES
+        return
+    if isinstance(lines, int):
+        assert lines == TOO_MANY_PIECES and least + 4 > max_seg
+        return
+    _check_sound(lines, shape)
+
+
+def test_the_p256_verifier_in_pieces_of_8_ops_is_refused(plans):
+    """429 ops in pieces of 8 are more than the 34 pieces a context has events for: the call fails (P2E_E_INVALID)"""
+    lines, shape = plans.dump(1, 3, 1, {"P2E_CP_PIECE_OPS_QUAD": "8"}, plan_cases.N)
+    assert shape[0] == 429 and shape[6] == 34 and lines == TOO_MANY_PIECES
