@@ -23,6 +23,7 @@
  *   Return value: < 0 API misuse / HIP failure (p2e_last_error() has the text); >= 0 number of batch
  *   elements whose err byte is non-zero.  err[i] is a bit mask of P2E_ERR_* -- the conditions under
  *   which the reference generator panics.  Outputs of a flagged element are unspecified.
+ *   (The four wire-form calls, p2e_point_decode_batch .. p2e_sig_encode_batch, write a P2E_WIRE_* CODE instead.)
  *   Nothing ever unwinds or aborts across this boundary.
  *
  * THREADING  A p2e_ctx is not thread-safe: one context per (host thread, device).  Calls are
@@ -601,6 +602,90 @@ long p2e_ecdsa_sign_deterministic_batch(p2e_ctx *ctx, int curve, unsigned plan, 
                                         size_t n, uint8_t *err);
 long p2e_eth_address_batch(p2e_ctx *ctx, const uint8_t *pkx32, const uint8_t *pky32, const uint8_t *err /* nullable */,
                            uint8_t *addr20, size_t n);
+
+/* ---- keys and signatures in wire form: SEC1 public keys and DER / compact ECDSA signatures, decoded and encoded on the
+ * device, on either curve (P2E_CURVE_*).  A Bitcoin-style batch carries a DER signature and a 33-byte key, a WebAuthn /
+ * X.509 / TLS batch a DER signature and a SEC1 key, an Ethereum typed transaction 65 bytes r || s || v: these calls turn
+ * them into the 32-byte little-endian r32, s32, px32, py32 of every other entry point and back.  Everything in wire form
+ * is big-endian as its standard defines.  The reference has no counterpart (curve/ecdsa.rs:7-23 holds field elements).
+ * Below, p is the curve's field prime and n its group order.
+ *
+ * ERROR CODES.  P2E_ERR_NOT_RECOVERABLE took the last free bit of the error byte, so for these four calls err[i] is a
+ * CODE (P2E_WIRE_*), NOT a set of P2E_ERR_* bits: the code of the first failing check in the order given below, 0 where
+ * the element is fine.  A flagged element writes zeros to all its outputs.  The return value is the number of flagged
+ * elements.
+ *
+ * VARIABLE-LENGTH INPUT (keys; DER signatures) follows p2e_hash_batch: element i = data[offsets[i], offsets[i + 1]),
+ * offsets holds n + 1 entries, elements are concatenated without padding and need no alignment; offsets[i + 1] <
+ * offsets[i] is an empty element (P2E_WIRE_BAD_LENGTH).  A lane reads aligned 4-byte words and only those that hold at
+ * least one byte of its own element; it reads nothing for an element that is empty or longer than the form's maximum
+ * (P2E_WIRE_BAD_LENGTH is decided from the offsets alone), and no word beyond those holding the bytes its checks have
+ * admitted so far.
+ *
+ * p2e_point_decode_batch   SEC1 2.3.4.  Checks in order:
+ *     1. length not in {1, 33, 65}: BAD_LENGTH;
+ *     2. length 1: the byte 00 is the neutral element -- zeros and INFINITY (flagged: no key is the neutral element) --
+ *        any other byte BAD_PREFIX;
+ *     3. length 33 with a prefix other than 02 / 03, length 65 with a prefix other than 04: BAD_PREFIX (the hybrid
+ *        prefixes 06 / 07 are refused here);
+ *     4. x >= p, or for length 65 y >= p: COORD_RANGE;
+ *     5. length 33: x^3 + a x + b is not a square: NOT_ON_CURVE; otherwise y is the root whose parity is prefix & 1
+ *        (the recovery's square root, about 270 field multiplications);
+ *     6. length 65: y^2 != x^3 + a x + b: NOT_ON_CURVE.   (Both curves have cofactor 1: on the curve is enough.)
+ * p2e_point_encode_batch   form P2E_SEC1_COMPRESSED (stride 33) or P2E_SEC1_UNCOMPRESSED (stride 65): element i at
+ *     out + stride i, no alignment needed.  (0, 0): zeros and INFINITY; a coordinate >= p: COORD_RANGE; off the curve:
+ *     NOT_ON_CURVE.
+ * p2e_sig_decode_batch     form P2E_SIG_DER (variable length, offsets required), P2E_SIG_COMPACT64 (r || s, stride 64,
+ *     offsets NULL) or P2E_SIG_COMPACT65 (r || s || v, stride 65, offsets NULL).  COMPACT65: v[i] is the 65th byte as it
+ *     is -- no 27 and no EIP-155 offset is subtracted, nothing about it is checked (see p2e_ecdsa_recover_batch); v is
+ *     nullable there and ignored in the other forms.  flags: 0, P2E_SIG_REQUIRE_LOW_S or P2E_SIG_NORMALIZE_S (both:
+ *     P2E_E_INVALID).  DER is strict, BIP-66's rules; a trailing sighash-type byte is not part of the element (the
+ *     caller's offsets leave it out).  For an element b of length L, in order:
+ *     1. L < 8 or L > 72: BAD_LENGTH;
+ *     2. b[0] != 30 or b[1] != L - 2: DER_SYNTAX (long-form lengths are refused by this);
+ *     3. b[2] != 02;  with lr = b[3]:  lr = 0, lr > 33 or lr + 7 > L: DER_SYNTAX;
+ *     4. b[4 + lr] != 02;  with ls = b[5 + lr]:  ls = 0, ls > 33 or lr + ls + 6 != L: DER_SYNTAX;
+ *     5. for r, then s: first byte >= 80 (negative), or length > 1 with first byte 00 and second byte < 80 (padded):
+ *        DER_INTEGER;
+ *     6. for r, then s: value >= 2^256 (33 bytes with a non-zero first byte), value = 0 or value >= n: SCALAR_RANGE.
+ *     The compact forms start at check 6.  Then, s being high where s > (n - 1) / 2:  P2E_SIG_REQUIRE_LOW_S: HIGH_S;
+ *     P2E_SIG_NORMALIZE_S: s := n - s, and in COMPACT65 v ^= 1 (the same key is recovered).
+ * p2e_sig_encode_batch     the same forms.  DER writes the minimal encoding at stride P2E_SIG_DER_STRIDE (72), zeros
+ *     behind it, and its length (8 .. 72) into out_len[i]; out_len is n bytes, required for DER and ignored otherwise.
+ *     COMPACT65 needs v.  flags: 0 or P2E_SIG_NORMALIZE_S, as in decoding.  r or s zero or >= n: SCALAR_RANGE, zeros,
+ *     out_len[i] = 0.
+ * Each call is one kernel on the context's caller stream, one lane per element: no internal streams, no LDS, no scratch.
+ * P2E_E_INVALID on a null pointer (other than the nullable ones), an unknown curve, form or flag combination; n == 0
+ * returns 0.  Host pointers (the staging copy of data[offsets[0], offsets[n]) included), async mode, the current device
+ * and failed calls behave as for p2e_hash_batch. */
+#define P2E_WIRE_OK 0
+#define P2E_WIRE_BAD_LENGTH 1
+#define P2E_WIRE_BAD_PREFIX 2
+#define P2E_WIRE_COORD_RANGE 3
+#define P2E_WIRE_NOT_ON_CURVE 4
+#define P2E_WIRE_INFINITY 5
+#define P2E_WIRE_DER_SYNTAX 6
+#define P2E_WIRE_DER_INTEGER 7
+#define P2E_WIRE_SCALAR_RANGE 8
+#define P2E_WIRE_HIGH_S 9
+#define P2E_SEC1_COMPRESSED 0     /* 02 / 03 || x, 33 bytes */
+#define P2E_SEC1_UNCOMPRESSED 1   /* 04 || x || y, 65 bytes */
+#define P2E_SIG_DER 0
+#define P2E_SIG_COMPACT64 1       /* r || s */
+#define P2E_SIG_COMPACT65 2       /* r || s || v */
+#define P2E_SIG_REQUIRE_LOW_S 1u
+#define P2E_SIG_NORMALIZE_S 2u
+#define P2E_SIG_DER_STRIDE 72     /* bytes per element of an encoded DER batch: the longest strict signature */
+long p2e_point_decode_batch(p2e_ctx *ctx, int curve, const uint8_t *data, const uint64_t *offsets /* n + 1 */,
+                            uint8_t *px32, uint8_t *py32, size_t n, uint8_t *err);
+long p2e_point_encode_batch(p2e_ctx *ctx, int curve, int form, const uint8_t *px32, const uint8_t *py32, uint8_t *out,
+                            size_t n, uint8_t *err);
+long p2e_sig_decode_batch(p2e_ctx *ctx, int curve, int form, unsigned flags, const uint8_t *data,
+                          const uint64_t *offsets /* n + 1; DER only */, uint8_t *r32, uint8_t *s32,
+                          uint8_t *v /* nullable */, size_t n, uint8_t *err);
+long p2e_sig_encode_batch(p2e_ctx *ctx, int curve, int form, unsigned flags, const uint8_t *r32, const uint8_t *s32,
+                          const uint8_t *v /* COMPACT65 only */, uint8_t *out, uint8_t *out_len /* DER only */, size_t n,
+                          uint8_t *err);
 
 /* ---- multi-scalar multiplication: out = sum_i k_i P_i over n points of one curve (P2E_CURVE_*), by the bucket
  * (Pippenger) method; the native many-point sum of curve/curve_msm.rs (msm_parallel / msm_execute) without its

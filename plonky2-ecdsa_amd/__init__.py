@@ -43,6 +43,13 @@ HASH_SHA256, HASH_SHA256D, HASH_KECCAK256 = 0, 1, 2        # include/p2e.h P2E_H
 DIGEST_BYTES, DIGEST_SCALAR = 0, 1                         # include/p2e.h P2E_DIGEST_*
 MSM_WINDOW_AUTO, MSM_WINDOW_MIN, MSM_WINDOW_MAX = 0, 4, 12  # include/p2e.h P2E_MSM_WINDOW_*
 MSM_OK, MSM_NEUTRAL, MSM_BAD_POINT = 0, 1, 2               # include/p2e.h P2E_MSM_* (the status byte of point_msm)
+# include/p2e.h P2E_WIRE_*: the err CODE (not a bit set) of point_decode_batch, point_encode_batch, sig_decode_batch, sig_encode_batch
+(WIRE_OK, WIRE_BAD_LENGTH, WIRE_BAD_PREFIX, WIRE_COORD_RANGE, WIRE_NOT_ON_CURVE, WIRE_INFINITY, WIRE_DER_SYNTAX, WIRE_DER_INTEGER,
+ WIRE_SCALAR_RANGE, WIRE_HIGH_S) = range(10)
+SEC1_COMPRESSED, SEC1_UNCOMPRESSED = 0, 1                  # include/p2e.h P2E_SEC1_*
+SIG_DER, SIG_COMPACT64, SIG_COMPACT65 = 0, 1, 2            # include/p2e.h P2E_SIG_*
+SIG_REQUIRE_LOW_S, SIG_NORMALIZE_S = 1, 2
+SIG_DER_STRIDE = 72
 CTX_HOST_POINTERS, CTX_ASYNC, CTX_PHASE_TIMING = 1, 2, 4
 VERIFY_COLS = 82615
 GLV_MUL_COLS = 65243
@@ -85,6 +92,7 @@ EXPORTS = (
     "p2e_ecdsa_recover_batch", "p2e_ecdsa_sign_recoverable_batch",
     "p2e_hash_batch", "p2e_ecdsa_nonce_rfc6979_batch", "p2e_ecdsa_sign_deterministic_batch", "p2e_eth_address_batch",
     "p2e_point_msm", "p2e_point_msm_plan",
+    "p2e_point_decode_batch", "p2e_point_encode_batch", "p2e_sig_decode_batch", "p2e_sig_encode_batch",
 )
 
 
@@ -1141,6 +1149,67 @@ class Context:
                 addr = torch.empty((n, 20), dtype=torch.uint8, device=f"cuda:{self.device}")
         rc = self._check(self._L.p2e_eth_address_batch(self._h, _ptr(pkx), _ptr(pky), _ptr(err), _ptr(addr), C.c_size_t(n)))
         return addr, rc
+
+    # ---- keys and signatures in wire form (include/p2e.h p2e_point_decode_batch and the three after it) ---------------
+    def _bytes(self, *shape):
+        if self.host_pointers:
+            return np.zeros(shape, dtype=np.uint8)
+        import torch
+        return torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def point_decode_batch(self, data, offsets, curve=CURVE_SECP256K1, px=None, py=None, err=None):
+        """SEC1 public keys (00 | 02 x | 03 x | 04 x y, big-endian) -> little-endian coordinates.  Key i =
+        data[offsets[i]:offsets[i + 1]] as in hash_batch.  (px (n, 32), py (n, 32), err (n,), flagged count); err[i] is a
+        WIRE_* code, zeros are written where it is not 0."""
+        n = self._shape(offsets)[0] - 1
+        px = px if px is not None else self._packed(n)
+        py = py if py is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_decode_batch(self._h, C.c_int(curve), _ptr(data), _ptr(offsets), _ptr(px), _ptr(py),
+                                                         C.c_size_t(n), _ptr(err)))
+        return px, py, err, bad
+
+    def point_encode_batch(self, px, py, curve=CURVE_SECP256K1, form=SEC1_COMPRESSED, out=None, err=None):
+        """Little-endian coordinates -> SEC1 keys at a fixed stride: (out (n, 33 | 65), err (n,) WIRE_* codes, flagged count)."""
+        n = self._shape(px)[0]
+        out = out if out is not None else self._bytes(n, 33 if form == SEC1_COMPRESSED else 65)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_encode_batch(self._h, C.c_int(curve), C.c_int(form), _ptr(px), _ptr(py), _ptr(out),
+                                                         C.c_size_t(n), _ptr(err)))
+        return out, err, bad
+
+    def sig_decode_batch(self, data, offsets=None, curve=CURVE_SECP256K1, form=SIG_DER, flags=0, n=None, r=None, s=None, v=None,
+                         err=None, want_v=True):
+        """Signatures in wire form -> (r, s, v, err, flagged count).  SIG_DER: strict DER, element i = data[offsets[i]:
+        offsets[i + 1]];  SIG_COMPACT64 / SIG_COMPACT65: (n, 64) r || s or (n, 65) r || s || v, no offsets.  v is the 65th
+        byte as it is (None outside SIG_COMPACT65 or with want_v=False).  flags: 0, SIG_REQUIRE_LOW_S or SIG_NORMALIZE_S."""
+        if n is None:
+            n = self._shape(offsets)[0] - 1 if form == SIG_DER else self._shape(data)[0]
+        r = r if r is not None else self._packed(n)
+        s = s if s is not None else self._packed(n)
+        if form == SIG_COMPACT65 and want_v:
+            v = v if v is not None else self._vec(n, np.uint8)
+        else:
+            v = None
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_sig_decode_batch(self._h, C.c_int(curve), C.c_int(form), C.c_uint(flags), _ptr(data),
+                                                       _ptr(offsets), _ptr(r), _ptr(s), _ptr(v), C.c_size_t(n), _ptr(err)))
+        return r, s, v, err, bad
+
+    def sig_encode_batch(self, r, s, v=None, curve=CURVE_SECP256K1, form=SIG_DER, flags=0, out=None, out_len=None, err=None):
+        """(r, s[, v]) -> wire form: (out, out_len, err, flagged count).  SIG_DER: out (n, 72), the minimal encoding
+        zero-filled, out_len (n,) its length;  SIG_COMPACT64 / SIG_COMPACT65: out (n, 64 | 65), out_len None.
+        flags: 0 or SIG_NORMALIZE_S."""
+        n = self._shape(r)[0]
+        out = out if out is not None else self._bytes(n, {SIG_DER: SIG_DER_STRIDE, SIG_COMPACT64: 64}.get(form, 65))
+        if form == SIG_DER:
+            out_len = out_len if out_len is not None else self._vec(n, np.uint8)
+        else:
+            out_len = None
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_sig_encode_batch(self._h, C.c_int(curve), C.c_int(form), C.c_uint(flags), _ptr(r), _ptr(s),
+                                                       _ptr(v), _ptr(out), _ptr(out_len), C.c_size_t(n), _ptr(err)))
+        return out, out_len, err, bad
 
     def _compact_out(self, program, n, narrow, wide, ld_narrow, ld_wide):
         _m, nn, nw = compact_layout(program)

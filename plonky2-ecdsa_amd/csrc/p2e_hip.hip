@@ -27,6 +27,7 @@
 #include "recover.hpp"
 #include "pmsm.hpp"
 #include "hash.hpp"
+#include "wire.hpp"
 
 using namespace p2e;
 using host::COMPACT_WIDE;
@@ -35,7 +36,7 @@ using host::COMPACT_WIDE;
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
 // streaming passes, descriptions;  1 = the fused pipeline of the two built-in programs (run_program);  2 / 3 = the
 // curve-program pipeline instantiated for secp256k1 / P-256 (run_curve_program<CV>).  Undefined = everything in one
-// unit.  The hashing, nonce and address kernels (hash.hpp) ride in part 1, the part that builds fastest.  Small static helpers (error text, staging, scratch) are compiled into every part.
+// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest.  Small static helpers (error text, staging, scratch) are compiled into every part.
 #ifndef P2E_PART
 #define P2E_PART (-1)
 #endif
@@ -2539,6 +2540,222 @@ extern "C" long p2e_eth_address_batch(p2e_ctx* c, const uint8_t* pkx32, const ui
     c->have_phases = false;
     ZERO_COUNTER(c);
     launch_eth_address(c, pkx32, pky32, err, addr20, n);
+    return S.done(finish_call(c));
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// SEC1 keys and DER / compact signatures in wire form (wire.hpp)
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 1 beside the hashing kernels, called from part 0
+void launch_point_decode(p2e_ctx* c, int curve, const uint8_t* data, const uint64_t* offsets, uint8_t* px32, uint8_t* py32, size_t n,
+                         uint8_t* err);
+void launch_point_encode(p2e_ctx* c, int curve, int form, const uint8_t* px32, const uint8_t* py32, uint8_t* out, size_t n, uint8_t* err);
+void launch_sig_decode(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* data, const uint64_t* offsets, uint8_t* r32,
+                       uint8_t* s32, uint8_t* v, size_t n, uint8_t* err);
+void launch_sig_encode(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* r32, const uint8_t* s32, const uint8_t* v,
+                       uint8_t* out, uint8_t* out_len, size_t n, uint8_t* err);
+#if P2E_HAS(1)
+void launch_point_decode(p2e_ctx* c, int curve, const uint8_t* data, const uint64_t* offsets, uint8_t* px32, uint8_t* py32, size_t n,
+                         uint8_t* err) {
+    if (curve == P2E_CURVE_P256)
+        hipLaunchKernelGGL((k_point_decode<P256>), grid1(n), dim3(BS), 0, c->stream, data, offsets, px32, py32, n, err, c->d_counter);
+    else
+        hipLaunchKernelGGL((k_point_decode<Secp256k1>), grid1(n), dim3(BS), 0, c->stream, data, offsets, px32, py32, n, err, c->d_counter);
+}
+template <class CV>
+static void launch_point_encode_cv(p2e_ctx* c, int form, const uint8_t* px32, const uint8_t* py32, uint8_t* out, size_t n, uint8_t* err) {
+    if (form == P2E_SEC1_COMPRESSED)
+        hipLaunchKernelGGL((k_point_encode<CV, SEC1_COMPRESSED>), grid1(n), dim3(BS), 0, c->stream, px32, py32, out, n, err, c->d_counter);
+    else
+        hipLaunchKernelGGL((k_point_encode<CV, SEC1_UNCOMPRESSED>), grid1(n), dim3(BS), 0, c->stream, px32, py32, out, n, err, c->d_counter);
+}
+void launch_point_encode(p2e_ctx* c, int curve, int form, const uint8_t* px32, const uint8_t* py32, uint8_t* out, size_t n, uint8_t* err) {
+    if (curve == P2E_CURVE_P256)
+        launch_point_encode_cv<P256>(c, form, px32, py32, out, n, err);
+    else
+        launch_point_encode_cv<Secp256k1>(c, form, px32, py32, out, n, err);
+}
+template <class CV>
+static void launch_sig_decode_cv(p2e_ctx* c, int form, unsigned flags, const uint8_t* data, const uint64_t* offsets, uint8_t* r32,
+                                 uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
+    if (form == P2E_SIG_DER)
+        hipLaunchKernelGGL((k_sig_decode<CV, SIG_DER>), grid1(n), dim3(BS), 0, c->stream, flags, data, offsets, r32, s32, v, n, err,
+                           c->d_counter);
+    else if (form == P2E_SIG_COMPACT64)
+        hipLaunchKernelGGL((k_sig_decode<CV, SIG_COMPACT64>), grid1(n), dim3(BS), 0, c->stream, flags, data, offsets, r32, s32, v, n, err,
+                           c->d_counter);
+    else
+        hipLaunchKernelGGL((k_sig_decode<CV, SIG_COMPACT65>), grid1(n), dim3(BS), 0, c->stream, flags, data, offsets, r32, s32, v, n, err,
+                           c->d_counter);
+}
+void launch_sig_decode(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* data, const uint64_t* offsets, uint8_t* r32,
+                       uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
+    if (curve == P2E_CURVE_P256)
+        launch_sig_decode_cv<P256>(c, form, flags, data, offsets, r32, s32, v, n, err);
+    else
+        launch_sig_decode_cv<Secp256k1>(c, form, flags, data, offsets, r32, s32, v, n, err);
+}
+template <class CV>
+static void launch_sig_encode_cv(p2e_ctx* c, int form, unsigned flags, const uint8_t* r32, const uint8_t* s32, const uint8_t* v, uint8_t* out,
+                                 uint8_t* out_len, size_t n, uint8_t* err) {
+    if (form == P2E_SIG_DER)
+        hipLaunchKernelGGL((k_sig_encode<CV, SIG_DER>), grid1(n), dim3(BS), 0, c->stream, flags, r32, s32, v, out, out_len, n, err,
+                           c->d_counter);
+    else if (form == P2E_SIG_COMPACT64)
+        hipLaunchKernelGGL((k_sig_encode<CV, SIG_COMPACT64>), grid1(n), dim3(BS), 0, c->stream, flags, r32, s32, v, out, out_len, n, err,
+                           c->d_counter);
+    else
+        hipLaunchKernelGGL((k_sig_encode<CV, SIG_COMPACT65>), grid1(n), dim3(BS), 0, c->stream, flags, r32, s32, v, out, out_len, n, err,
+                           c->d_counter);
+}
+void launch_sig_encode(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* r32, const uint8_t* s32, const uint8_t* v,
+                       uint8_t* out, uint8_t* out_len, size_t n, uint8_t* err) {
+    if (curve == P2E_CURVE_P256)
+        launch_sig_encode_cv<P256>(c, form, flags, r32, s32, v, out, out_len, n, err);
+    else
+        launch_sig_encode_cv<Secp256k1>(c, form, flags, r32, s32, v, out, out_len, n, err);
+}
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static_assert(P2E_WIRE_OK == WIRE_OK && P2E_WIRE_BAD_LENGTH == WIRE_BAD_LENGTH && P2E_WIRE_BAD_PREFIX == WIRE_BAD_PREFIX &&
+                  P2E_WIRE_COORD_RANGE == WIRE_COORD_RANGE && P2E_WIRE_NOT_ON_CURVE == WIRE_NOT_ON_CURVE &&
+                  P2E_WIRE_INFINITY == WIRE_INFINITY && P2E_WIRE_DER_SYNTAX == WIRE_DER_SYNTAX &&
+                  P2E_WIRE_DER_INTEGER == WIRE_DER_INTEGER && P2E_WIRE_SCALAR_RANGE == WIRE_SCALAR_RANGE && P2E_WIRE_HIGH_S == WIRE_HIGH_S,
+              "include/p2e.h and wire.hpp");
+static_assert(P2E_SEC1_COMPRESSED == SEC1_COMPRESSED && P2E_SEC1_UNCOMPRESSED == SEC1_UNCOMPRESSED && P2E_SIG_DER == SIG_DER &&
+                  P2E_SIG_COMPACT64 == SIG_COMPACT64 && P2E_SIG_COMPACT65 == SIG_COMPACT65 && P2E_SIG_REQUIRE_LOW_S == SIG_REQUIRE_LOW_S &&
+                  P2E_SIG_NORMALIZE_S == SIG_NORMALIZE_S && P2E_SIG_DER_STRIDE == SIG_DER_STRIDE,
+              "include/p2e.h and wire.hpp");
+static bool wire_bad_curve(int curve, size_t n) {
+    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
+        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
+        return true;
+    }
+    return hash_batch_too_large(n);
+}
+static bool wire_bad_sig_form(int form) {
+    if (form == P2E_SIG_DER || form == P2E_SIG_COMPACT64 || form == P2E_SIG_COMPACT65) return false;
+    set_error("unknown form (P2E_SIG_DER, P2E_SIG_COMPACT64 or P2E_SIG_COMPACT65)");
+    return true;
+}
+// the variable-length input of a staged call: the copy holds data[offsets[0], offsets[n]) and `data` becomes that copy moved
+// back by offsets[0], as in p2e_hash_batch.  false: offsets[n] < offsets[0] (the error text is set)
+static bool wire_stage_elements(Staged& S, const uint8_t*& data, const uint64_t* offsets, size_t n) {
+    if (!S.host) return true;
+    const uint64_t first = offsets[0], last = offsets[n];
+    if (last < first) {
+        set_error("offsets[n] < offsets[0]");
+        return false;
+    }
+    const uint8_t* d = S.in(data + first, (size_t)(last - first));
+    data = d ? d - first : nullptr;
+    return true;
+}
+extern "C" long p2e_point_decode_batch(p2e_ctx* c, int curve, const uint8_t* data, const uint64_t* offsets, uint8_t* px32, uint8_t* py32,
+                                       size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!data || !offsets || !px32 || !py32 || !err) {
+        set_error("null pointer (data, offsets, px32, py32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    if (wire_bad_curve(curve, n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    Staged S(c);
+    if (!wire_stage_elements(S, data, offsets, n)) return S.done(P2E_E_INVALID);
+    offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
+    px32 = S.out(px32, n * 32);
+    py32 = S.out(py32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_point_decode(c, curve, data, offsets, px32, py32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_point_encode_batch(p2e_ctx* c, int curve, int form, const uint8_t* px32, const uint8_t* py32, uint8_t* out, size_t n,
+                                       uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!px32 || !py32 || !out || !err) {
+        set_error("null pointer (px32, py32, out and err are all required)");
+        return P2E_E_INVALID;
+    }
+    if (wire_bad_curve(curve, n)) return P2E_E_INVALID;
+    if (form != P2E_SEC1_COMPRESSED && form != P2E_SEC1_UNCOMPRESSED) {
+        set_error("unknown form (P2E_SEC1_COMPRESSED or P2E_SEC1_UNCOMPRESSED)");
+        return P2E_E_INVALID;
+    }
+    if (n == 0) return 0;
+    Staged S(c);
+    px32 = S.in(px32, n * 32);
+    py32 = S.in(py32, n * 32);
+    out = S.out(out, n * (form == P2E_SEC1_COMPRESSED ? 33 : 65));
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_point_encode(c, curve, form, px32, py32, out, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_sig_decode_batch(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* data, const uint64_t* offsets,
+                                     uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (wire_bad_curve(curve, n) || wire_bad_sig_form(form)) return P2E_E_INVALID;
+    if (!data || !r32 || !s32 || !err || (form == P2E_SIG_DER && !offsets)) {
+        set_error("null pointer (data, r32, s32 and err are all required, offsets with P2E_SIG_DER; v may be null)");
+        return P2E_E_INVALID;
+    }
+    if (flags != 0 && flags != P2E_SIG_REQUIRE_LOW_S && flags != P2E_SIG_NORMALIZE_S) {
+        set_error("unknown flags (0, P2E_SIG_REQUIRE_LOW_S or P2E_SIG_NORMALIZE_S)");
+        return P2E_E_INVALID;
+    }
+    if (n == 0) return 0;
+    Staged S(c);
+    if (form == P2E_SIG_DER) {
+        if (!wire_stage_elements(S, data, offsets, n)) return S.done(P2E_E_INVALID);
+        offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
+    } else {
+        data = S.in(data, n * (form == P2E_SIG_COMPACT64 ? 64 : 65));
+        offsets = nullptr;
+    }
+    if (form != P2E_SIG_COMPACT65) v = nullptr;
+    r32 = S.out(r32, n * 32);
+    s32 = S.out(s32, n * 32);
+    v = S.out(v, n);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_sig_decode(c, curve, form, flags, data, offsets, r32, s32, v, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_sig_encode_batch(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* r32, const uint8_t* s32,
+                                     const uint8_t* v, uint8_t* out, uint8_t* out_len, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (wire_bad_curve(curve, n) || wire_bad_sig_form(form)) return P2E_E_INVALID;
+    if (!r32 || !s32 || !out || !err || (form == P2E_SIG_DER && !out_len) || (form == P2E_SIG_COMPACT65 && !v)) {
+        set_error("null pointer (r32, s32, out and err are all required, out_len with P2E_SIG_DER, v with P2E_SIG_COMPACT65)");
+        return P2E_E_INVALID;
+    }
+    if (flags != 0 && flags != P2E_SIG_NORMALIZE_S) {
+        set_error("unknown flags (0 or P2E_SIG_NORMALIZE_S)");
+        return P2E_E_INVALID;
+    }
+    if (n == 0) return 0;
+    if (form != P2E_SIG_COMPACT65) v = nullptr;
+    if (form != P2E_SIG_DER) out_len = nullptr;
+    Staged S(c);
+    r32 = S.in(r32, n * 32);
+    s32 = S.in(s32, n * 32);
+    v = S.in(v, n);
+    out = S.out(out, n * (form == P2E_SIG_DER ? P2E_SIG_DER_STRIDE : form == P2E_SIG_COMPACT64 ? 64 : 65));
+    out_len = S.out(out_len, n);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_sig_encode(c, curve, form, flags, r32, s32, v, out, out_len, n, err);
     return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)

@@ -245,6 +245,72 @@ pub fn eth_addresses(ctx: *mut P2eCtx, keys: &[Option<(BigUint, BigUint)>]) -> R
     Ok((0..n).map(|i| keys[i].as_ref().map(|_| addr[20 * i..20 * i + 20].try_into().unwrap())).collect())
 }
 
+/// SEC1 public keys as they arrive on the wire (33-byte compressed, 65-byte uncompressed) to coordinates
+/// (`p2e_point_decode_batch`, host-pointer context): `Err(code)` carries the `P2E_WIRE_*` code of the first failed check.
+pub fn decode_public_keys(ctx: *mut P2eCtx, curve: i32, keys: &[&[u8]]) -> Result<Vec<std::result::Result<(BigUint, BigUint), u8>>> {
+    let n = keys.len();
+    let (mut offsets, mut data) = (vec![0u64], Vec::new());
+    for k in keys {
+        data.extend_from_slice(k);
+        offsets.push(data.len() as u64);
+    }
+    data.push(0); // never read: keeps the pointer of an all-empty batch valid
+    let (mut px, mut py, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n]);
+    let rc = unsafe { p2e_point_decode_batch(ctx, curve, data.as_ptr(), offsets.as_ptr(), px.as_mut_ptr(), py.as_mut_ptr(), n, err.as_mut_ptr()) };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n)
+        .map(|i| match err[i] {
+            P2E_WIRE_OK => Ok((BigUint::from_bytes_le(&px[32 * i..32 * i + 32]), BigUint::from_bytes_le(&py[32 * i..32 * i + 32]))),
+            code => Err(code),
+        })
+        .collect())
+}
+
+/// Strict-DER signatures (BIP-66's rules) to `(r, s)` (`p2e_sig_decode_batch`, `P2E_SIG_DER`); `flags` is 0,
+/// `P2E_SIG_REQUIRE_LOW_S` or `P2E_SIG_NORMALIZE_S`.  `Err(code)` as in `decode_public_keys`.
+pub fn decode_der_signatures(ctx: *mut P2eCtx, curve: i32, flags: u32, sigs: &[&[u8]]) -> Result<Vec<std::result::Result<(BigUint, BigUint), u8>>> {
+    let n = sigs.len();
+    let (mut offsets, mut data) = (vec![0u64], Vec::new());
+    for s in sigs {
+        data.extend_from_slice(s);
+        offsets.push(data.len() as u64);
+    }
+    data.push(0);
+    let (mut r, mut s, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_sig_decode_batch(ctx, curve, P2E_SIG_DER, flags, data.as_ptr(), offsets.as_ptr(), r.as_mut_ptr(), s.as_mut_ptr(),
+                             std::ptr::null_mut(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n)
+        .map(|i| match err[i] {
+            P2E_WIRE_OK => Ok((BigUint::from_bytes_le(&r[32 * i..32 * i + 32]), BigUint::from_bytes_le(&s[32 * i..32 * i + 32]))),
+            code => Err(code),
+        })
+        .collect())
+}
+
+/// Keys and signatures leaving the library: compressed SEC1 keys (`p2e_point_encode_batch`) and minimal DER signatures with
+/// a low s (`p2e_sig_encode_batch`, `P2E_SIG_NORMALIZE_S`).  Any flagged element is an error here.
+pub fn encode_keys_and_signatures(ctx: *mut P2eCtx, curve: i32, keys: &[(BigUint, BigUint)], sigs: &[(BigUint, BigUint)]) -> Result<(Vec<[u8; 33]>, Vec<Vec<u8>>)> {
+    let (nk, ns) = (keys.len(), sigs.len());
+    let (px, py) = (pack32(keys.iter().map(|k| k.0.clone()), nk), pack32(keys.iter().map(|k| k.1.clone()), nk));
+    let (r, s) = (pack32(sigs.iter().map(|g| g.0.clone()), ns), pack32(sigs.iter().map(|g| g.1.clone()), ns));
+    let (mut kout, mut kerr) = (vec![0u8; 33 * nk], vec![0u8; nk]);
+    let (mut sout, mut slen, mut serr) = (vec![0u8; P2E_SIG_DER_STRIDE * ns], vec![0u8; ns], vec![0u8; ns]);
+    let rc = unsafe { p2e_point_encode_batch(ctx, curve, P2E_SEC1_COMPRESSED, px.as_ptr(), py.as_ptr(), kout.as_mut_ptr(), nk, kerr.as_mut_ptr()) };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    ensure!(rc == 0, "{rc} keys have no SEC1 form, the first at index {:?}", kerr.iter().position(|&e| e != 0));
+    let rc = unsafe {
+        p2e_sig_encode_batch(ctx, curve, P2E_SIG_DER, P2E_SIG_NORMALIZE_S, r.as_ptr(), s.as_ptr(), std::ptr::null(), sout.as_mut_ptr(),
+                             slen.as_mut_ptr(), ns, serr.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    ensure!(rc == 0, "{rc} signatures are out of range, the first at index {:?}", serr.iter().position(|&e| e != 0));
+    Ok(((0..nk).map(|i| kout[33 * i..33 * i + 33].try_into().unwrap()).collect(),
+        (0..ns).map(|i| sout[P2E_SIG_DER_STRIDE * i..P2E_SIG_DER_STRIDE * i + slen[i] as usize].to_vec()).collect()))
+}
+
 /// One built circuit of `verify_p256_message_circuit` (gadgets/ecdsa.rs:55-78): its hot-path output targets in
 /// registration order (len == 115 557 = `p2e_curve_program_num_cols`) and the library's program object, which carries
 /// the point `precompute_window` drew with `rand()` while THIS circuit was built (gadgets/curve_windowed_mul.rs:57).

@@ -86,6 +86,25 @@ pub const P2E_HASH_SHA256D: i32 = 1;
 pub const P2E_HASH_KECCAK256: i32 = 2;
 pub const P2E_DIGEST_BYTES: u32 = 0;
 pub const P2E_DIGEST_SCALAR: u32 = 1;
+// err CODES (not bits) of the four wire-form calls
+pub const P2E_WIRE_OK: u8 = 0;
+pub const P2E_WIRE_BAD_LENGTH: u8 = 1;
+pub const P2E_WIRE_BAD_PREFIX: u8 = 2;
+pub const P2E_WIRE_COORD_RANGE: u8 = 3;
+pub const P2E_WIRE_NOT_ON_CURVE: u8 = 4;
+pub const P2E_WIRE_INFINITY: u8 = 5;
+pub const P2E_WIRE_DER_SYNTAX: u8 = 6;
+pub const P2E_WIRE_DER_INTEGER: u8 = 7;
+pub const P2E_WIRE_SCALAR_RANGE: u8 = 8;
+pub const P2E_WIRE_HIGH_S: u8 = 9;
+pub const P2E_SEC1_COMPRESSED: i32 = 0;
+pub const P2E_SEC1_UNCOMPRESSED: i32 = 1;
+pub const P2E_SIG_DER: i32 = 0;
+pub const P2E_SIG_COMPACT64: i32 = 1;
+pub const P2E_SIG_COMPACT65: i32 = 2;
+pub const P2E_SIG_REQUIRE_LOW_S: u32 = 1;
+pub const P2E_SIG_NORMALIZE_S: u32 = 2;
+pub const P2E_SIG_DER_STRIDE: usize = 72;
 pub const P2E_MSM_WINDOW_AUTO: u32 = 0;
 pub const P2E_MSM_WINDOW_MIN: u32 = 4;
 pub const P2E_MSM_WINDOW_MAX: u32 = 12;
@@ -227,6 +246,16 @@ extern "C" {
         r32: *mut u8, s32: *mut u8, v: *mut u8, n: usize, err: *mut u8) -> i64;
     pub fn p2e_eth_address_batch(ctx: *mut P2eCtx, pkx32: *const u8, pky32: *const u8, err: *const u8, addr20: *mut u8,
         n: usize) -> i64;
+
+    // ---- keys and signatures in wire form: SEC1 keys, strict DER / compact signatures; err[i] is a P2E_WIRE_* code
+    pub fn p2e_point_decode_batch(ctx: *mut P2eCtx, curve: i32, data: *const u8, offsets: *const u64, px32: *mut u8, py32: *mut u8,
+        n: usize, err: *mut u8) -> i64;
+    pub fn p2e_point_encode_batch(ctx: *mut P2eCtx, curve: i32, form: i32, px32: *const u8, py32: *const u8, out: *mut u8, n: usize,
+        err: *mut u8) -> i64;
+    pub fn p2e_sig_decode_batch(ctx: *mut P2eCtx, curve: i32, form: i32, flags: u32, data: *const u8, offsets: *const u64,
+        r32: *mut u8, s32: *mut u8, v: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_sig_encode_batch(ctx: *mut P2eCtx, curve: i32, form: i32, flags: u32, r32: *const u8, s32: *const u8, v: *const u8,
+        out: *mut u8, out_len: *mut u8, n: usize, err: *mut u8) -> i64;
 
     // ---- bucket-method multi-scalar multiplication sum k_i P_i (curve/curve_msm.rs msm_parallel / msm_execute); `plan`:
     // P2E_MSM_PLAN_WORDS words indexed by P2E_MSM_PLAN_*
