@@ -40,11 +40,12 @@ class Probe:
     """ctypes face of libp2e_probe.so (device=True) or libp2e_probe_host.so; builds the library if it is missing and
     raises if that fails"""
 
-    def __init__(self, device):
-        target = "libp2e_probe.so" if device else "libp2e_probe_host.so"
-        path = os.path.join(PROBE_DIR, target)
+    def __init__(self, device, directory=PROBE_DIR, stem="p2e_probe"):
+        """directory, stem: another probe built to the same scheme (tests/probe_point)"""
+        target = f"lib{stem}.so" if device else f"lib{stem}_host.so"
+        path = os.path.join(directory, target)
         if not os.path.exists(path):
-            subprocess.check_call(["make", "-s", "-C", PROBE_DIR, target])
+            subprocess.check_call(["make", "-s", "-C", directory, target])
         self.L = C.CDLL(path)
         self.L.probe_ops.restype = C.c_long
         self.L.probe_ops.argtypes = [C.c_long, C.c_char_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5

@@ -42,6 +42,24 @@ def edges(cv):
     return e
 
 
+def group_patterns(cv, seed=0x6707):
+    """33 raw scalars: for each of the 16 empty / non-empty patterns of the four 64-bit groups (bit j of the index: group j is
+    not empty; the six with exactly two empty groups are those where one level of the quad plan's tree adds and the other
+    only selects) two values below 2^254 < n, pattern by pattern; then one more of pattern 1111 so that the batch ends in a
+    lone quad"""
+    rng = R.SplitMix64(seed + (cv.name == "p256"))
+    out = []
+    for mask in list(range(16)) * 2 + [15]:
+        g = [(rng.next() | 1) if (mask >> j) & 1 else 0 for j in range(4)]
+        g[3] = (g[3] >> 2) | ((mask >> 3) & 1)
+        out.append(sum(v << (64 * j) for j, v in enumerate(g)))
+    return out
+
+
+def group_mask(v):
+    return sum(1 << j for j in range(4) if (v >> (64 * j)) & ((1 << 64) - 1))
+
+
 def batch(cv, total, seed, shift=0):
     """E (rotated by `shift`) at the start, random filler, E reversed at the end: `total` raw 256-bit values"""
     e = edges(cv)

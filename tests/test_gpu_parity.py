@@ -908,3 +908,16 @@ def test_other_stream_layouts_give_the_same_witness(ora, monkeypatch, layout):
         want, _, wflags = ora.verify(*sigs)
         assert bad == 0 and np.array_equal(cols.cpu().numpy().view(np.uint64), want) and np.array_equal(valid.cpu().numpy(), wflags)
         assert len(ctx.segments()) >= 6
+
+
+def test_glv_rounding_boundaries(gpu):
+    """the 16 scalars whose products with B2 and -B1 leave a remainder where glv_round_div rounds (0, 1, the four values
+    around n / 2, n - 2, n - 1) and their neighbours k - 1, k + 1, against Python integers (p2e_ref.glv_decompose);
+    test_host.py asserts on the CPU that every boundary class is in the batch"""
+    import point_probe_inputs as PP
+    ks, _kinds = PP.rounding_batch()
+    want = [R.glv_decompose(k) for k in ks]
+    k1, k2, n1, n2, err = (np.asarray(v) for v in gpu.glv(oracle_c.limbs_cols(ks)))
+    assert not err.any()
+    assert np.array_equal(k1, oracle_c.limbs_cols([w[0] for w in want])[:5]) and np.array_equal(k2, oracle_c.limbs_cols([w[1] for w in want])[:5])
+    assert [int(v) for v in n1] == [w[2] for w in want] and [int(v) for v in n2] == [w[3] for w in want]

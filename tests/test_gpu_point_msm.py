@@ -164,3 +164,12 @@ def test_plain_c_client_sums_keys(tmp_path):
     r = subprocess.run([exe, "1000"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("1000 keys (0 flagged)") == 2 and r.stdout.count("the sum equals the key of the summed scalar") == 2
+
+
+@pytest.mark.parametrize("width", [7, 11])
+@pytest.mark.parametrize("curve_id", [0, 1])
+def test_widths_seven_and_eleven(curve_id, width, ctx, mixed_cases):
+    """the two forced widths no other device test takes (AUTO gives 5, 6, 9 or 10 at the sizes used): neither divides 256, and
+    their windows have two (7 bits) and thirty-two (11 bits) chunks"""
+    check(ctx, curve_id, mixed_cases[curve_id], width)
+    check(ctx, curve_id, M.uniform(curve_id, 257, 0x57 + 257), width)

@@ -222,3 +222,22 @@ def test_plain_c_client_signs_and_verifies(tmp_path):
     r = subprocess.run([exe, "300"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "300 keys (0 flagged), 300 signatures (0 flagged), 299 verify, 0 flagged by the verifier" in r.stdout
+
+
+@pytest.mark.parametrize("plan", PLANS)
+@pytest.mark.parametrize("curve_id", [0, 1])
+def test_the_sixteen_group_patterns(curve_id, plan, ctx):
+    """all 16 empty / non-empty patterns of the scalar's four 64-bit groups as one small batch (sign_inputs.edges has none of
+    the six with exactly two empty groups): the secret key and the nonce walk the patterns, in opposite directions"""
+    cv = S.CURVES[curve_id]
+    sk = S.group_patterns(cv)
+    k = S.group_patterns(cv, 0x6717)[::-1]
+    rng = S.R.SplitMix64(0x6727 + curve_id)
+    msg = [rng.below(1 << 256) for _ in sk]
+    assert sorted({S.group_mask(v) for v in sk}) == list(range(16)) == sorted({S.group_mask(v) for v in k})
+    pkx, pky, e1, bad1, r, s, e2, bad2 = _run(ctx, curve_id, plan, *[S.pack(v) for v in (msg, sk, k)])
+    wx, wy, we1 = S.expect_keys(curve_id, sk)
+    wr, ws, we2 = S.expect_sigs(curve_id, msg, sk, k)
+    assert np.array_equal(e1, we1) and np.array_equal(e2, we2) and (bad1, bad2) == (2, 2)   # pattern 0000, twice
+    for got, want, what in ((pkx, wx, "pkx"), (pky, wy, "pky"), (r, wr, "r"), (s, ws, "s")):
+        _assert_equal(got, want, (curve_id, plan, what))

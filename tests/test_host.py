@@ -506,3 +506,22 @@ def test_kernel_bodies_under_the_plan_of_a_nominal_batch(mixed, nominal, contain
     assert bad == int((werr != 0).sum()) and np.array_equal(err, werr)
     assert np.array_equal(valid[clean], wverdict[clean]) and (pid != 0 or not valid[~clean].any())
     assert np.array_equal(np.asarray(got)[:, clean], want[:, clean])
+
+
+@pytest.mark.parametrize("backend", [EmuBackend, OracleBackend], ids=["emu", "oracle"])
+def test_glv_rounding_boundaries(backend):
+    """the 16 scalars k = r c^-1 mod n, c in {B2, -B1}, whose product c k leaves the remainder r in {0, 1, (n-1)/2 - 1,
+    (n-1)/2, (n+1)/2, (n+1)/2 + 1, n - 2, n - 1} -- where glv_round_div rounds -- and their neighbours k - 1, k + 1, against
+    Python integers (p2e_ref.glv_decompose); test_gpu_parity.py runs the same batch on the device"""
+    import point_probe_inputs as PP
+    ks, kinds = PP.rounding_batch()
+    rems = PP.rounding_rems()
+    for cn, c in PP.GLV_CONSTS.items():                                # every boundary class is present, from the inputs alone
+        for rn, r in rems.items():
+            assert [k for k, kind in zip(ks, kinds) if kind == f"{cn}_rem_{rn}" and c * k % R.N == r], (cn, rn)
+    assert len(ks) == 48 and all(0 <= k < R.N for k in ks)
+    want = [R.glv_decompose(k) for k in ks]
+    k1, k2, n1, n2, err = backend().glv(oracle_c.limbs_cols(ks))
+    assert not np.asarray(err).any()
+    assert np.array_equal(k1, oracle_c.limbs_cols([w[0] for w in want])[:5]) and np.array_equal(k2, oracle_c.limbs_cols([w[1] for w in want])[:5])
+    assert [int(v) for v in n1] == [w[2] for w in want] and [int(v) for v in n2] == [w[3] for w in want]

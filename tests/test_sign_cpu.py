@@ -116,3 +116,30 @@ def test_entry_points_exist_and_refuse_misuse_without_a_device():
     assert L.p2e_ecdsa_public_key_batch(None, 0, 0, _p(buf), _p(buf), _p(buf), C.c_size_t(1), _p(buf)) == -1
     assert L.p2e_ecdsa_sign_batch(None, 0, 0, _p(buf), _p(buf), _p(buf), _p(buf), _p(buf), C.c_size_t(1), _p(buf)) == -1
     assert (p2e.ERR_POINT_AT_INFINITY, p2e.SIGN_PLAN_AUTO, p2e.SIGN_PLAN_LANE, p2e.SIGN_PLAN_QUAD) == (64, 0, 1, 2)
+
+
+@pytest.mark.parametrize("plan", [S.PLAN_LANE, S.PLAN_QUAD])
+@pytest.mark.parametrize("curve_id", [0, 1])
+def test_the_sixteen_group_patterns(curve_id, plan, emu):
+    """all 16 empty / non-empty patterns of the scalar's four 64-bit groups as one small batch (the edge set has none of the
+    six with exactly two empty groups, where one level of the quad tree adds and the other only selects)"""
+    cv = S.CURVES[curve_id]
+    sk_i = S.group_patterns(cv)
+    k_i = S.group_patterns(cv, 0x6717)[::-1]
+    rng = R.SplitMix64(0x6727 + curve_id)
+    msg_i = [rng.below(1 << 256) for _ in sk_i]
+    masks = [S.group_mask(v) for v in sk_i]
+    assert sorted(set(masks)) == list(range(16)) and sum(1 for m in set(masks) if bin(m).count("1") == 2) == 6
+    assert sorted({S.group_mask(v) for v in k_i}) == list(range(16)) and all(v < cv.n for v in sk_i + k_i)
+    msg, sk, k = (S.pack(v) for v in (msg_i, sk_i, k_i))
+    n = sk.shape[0]
+    fill = lambda: np.full((n, 32), 0xAA, np.uint8)
+    pkx, pky, r, s, e1, e2 = fill(), fill(), fill(), fill(), np.full(n, 0xAA, np.uint8), np.full(n, 0xAA, np.uint8)
+    bad1 = emu.emus_public_key(curve_id, plan, _p(sk), _p(pkx), _p(pky), C.c_size_t(n), _p(e1))
+    bad2 = emu.emus_sign(curve_id, plan, _p(msg), _p(sk), _p(k), _p(r), _p(s), C.c_size_t(n), _p(e2))
+    wx, wy, we1 = S.expect_keys(curve_id, sk_i)
+    wr, ws, we2 = S.expect_sigs(curve_id, msg_i, sk_i, k_i)
+    assert np.array_equal(e1, we1) and np.array_equal(e2, we2) and (bad1, bad2) == (2, 2)   # pattern 0000, twice
+    for got, want, what in ((pkx, wx, "pkx"), (pky, wy, "pky"), (r, wr, "r"), (s, ws, "s")):
+        diff = np.nonzero((got != want).any(axis=1))[0]
+        assert diff.size == 0, (curve_id, plan, what, diff[:8].tolist())
