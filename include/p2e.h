@@ -23,7 +23,8 @@
  *   Return value: < 0 API misuse / HIP failure (p2e_last_error() has the text); >= 0 number of batch
  *   elements whose err byte is non-zero.  err[i] is a bit mask of P2E_ERR_* -- the conditions under
  *   which the reference generator panics.  Outputs of a flagged element are unspecified.
- *   (The four wire-form calls, p2e_point_decode_batch .. p2e_sig_encode_batch, write a P2E_WIRE_* CODE instead.)
+ *   (The four wire-form calls, p2e_point_decode_batch .. p2e_sig_encode_batch, and the three point-arithmetic calls,
+ *   p2e_point_mul_batch .. p2e_point_add_batch, write a P2E_WIRE_* CODE instead.)
  *   Nothing ever unwinds or aborts across this boundary.
  *
  * THREADING  A p2e_ctx is not thread-safe: one context per (host thread, device).  Calls are
@@ -729,6 +730,43 @@ long p2e_point_msm(p2e_ctx *ctx, int curve, unsigned window_bits, const uint8_t 
                    const uint8_t *py32, size_t n, uint8_t *outx32, uint8_t *outy32, uint8_t *status /* 1 byte */,
                    uint8_t *point_err /* nullable, n bytes */);
 int p2e_point_msm_plan(int curve, size_t n, unsigned window_bits, uint64_t *plan /* P2E_MSM_PLAN_WORDS words */);
+
+/* ---- per-element point arithmetic on either curve (P2E_CURVE_*): the native point layer under the calls above.
+ *     p2e_point_mul_batch      out_i = k_i P_i          CurveScalar * ProjectivePoint (curve/curve_multiplication.rs:86-100),
+ *                                                       on secp256k1 also the native glv_mul (curve/glv.rs:84-102)
+ *     p2e_point_lincomb_batch  out_i = a_i G + b_i P_i  the verification equation with the caller's own scalars; P + t G
+ *     p2e_point_add_batch      out_i = P_i + Q_i        the additions of curve/curve_adds.rs
+ * All 32-byte values little-endian, element i at +32 i.
+ *     scalars  taken modulo the group order with one conditional subtraction, exactly as p2e_ecdsa_sign_batch takes its
+ *              scalars (reduced, not flagged).
+ *     points   (0, 0) is the neutral element and a legal operand, as in p2e_point_msm -- what the key and recovery calls
+ *              write for flagged elements, so the output of any call of this library can be fed in.  Any other point with a
+ *              coordinate >= p, or not on the curve, is invalid.
+ *     err[i]   all eight P2E_ERR_* bits are taken: a P2E_WIRE_* CODE, as for the four wire-form calls.  The first failing
+ *              check of P2E_WIRE_COORD_RANGE, then P2E_WIRE_NOT_ON_CURVE (p2e_point_add_batch: P before Q; operands are
+ *              checked whatever the scalars are); P2E_WIRE_INFINITY where the operands are fine and the RESULT is the
+ *              neutral element, which 64 bytes cannot express (flagged as sk = 0 is by p2e_ecdsa_public_key_batch: an ECDH
+ *              caller must see it).  Every non-zero code writes zeros to both outputs -- still the valid neutral operand
+ *              of a next call.  Return value: the number of elements with a non-zero code.
+ *     defined, none an error by itself: k = 0 (mod n), P neutral, a = 0, b = 0, a G = -b P, a G = b P (the last addition
+ *              doubles), P = Q, P = -Q, P or Q neutral.
+ *     plan     P2E_MUL_PLAN_AUTO (the library chooses), or a forced walk for k P / b P; all plans give the same bytes.
+ *              P2E_MUL_PLAN_GLV on P2E_CURVE_P256 is P2E_E_INVALID.
+ * P2E_E_INVALID on a null pointer, an unknown curve or plan; n == 0 returns 0.  One kernel per call on the context's caller
+ * stream, one lane per element (csrc/point_arith.hpp): no internal streams, no scratch block, no table in LDS, nothing in the
+ * private segment.  Host pointers, async mode (the return value then comes from p2e_sync), the current device and failed calls
+ * behave as for the signing calls.  A zero Z at the end of a walk (impossible, see csrc/point_arith.hpp) would set
+ * P2E_WIRE_INFINITY and write zeros. */
+#define P2E_MUL_PLAN_AUTO 0
+#define P2E_MUL_PLAN_PLAIN 1   /* 128 two-bit windows over the 256-bit scalar (recover.hpp's walk), both curves */
+#define P2E_MUL_PLAN_GLV 2     /* secp256k1 only: k = +-k1 +- k2 lambda, two 128-bit halves walked together */
+long p2e_point_mul_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *k32, const uint8_t *px32,
+                         const uint8_t *py32, uint8_t *outx32, uint8_t *outy32, size_t n, uint8_t *err);
+long p2e_point_lincomb_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *a32, const uint8_t *b32,
+                             const uint8_t *px32, const uint8_t *py32, uint8_t *outx32, uint8_t *outy32, size_t n,
+                             uint8_t *err);
+long p2e_point_add_batch(p2e_ctx *ctx, int curve, const uint8_t *px32, const uint8_t *py32, const uint8_t *qx32,
+                         const uint8_t *qy32, uint8_t *outx32, uint8_t *outy32, size_t n, uint8_t *err);
 
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */

@@ -46,6 +46,7 @@ MSM_OK, MSM_NEUTRAL, MSM_BAD_POINT = 0, 1, 2               # include/p2e.h P2E_M
 # include/p2e.h P2E_WIRE_*: the err CODE (not a bit set) of point_decode_batch, point_encode_batch, sig_decode_batch, sig_encode_batch
 (WIRE_OK, WIRE_BAD_LENGTH, WIRE_BAD_PREFIX, WIRE_COORD_RANGE, WIRE_NOT_ON_CURVE, WIRE_INFINITY, WIRE_DER_SYNTAX, WIRE_DER_INTEGER,
  WIRE_SCALAR_RANGE, WIRE_HIGH_S) = range(10)
+MUL_PLAN_AUTO, MUL_PLAN_PLAIN, MUL_PLAN_GLV = 0, 1, 2       # include/p2e.h P2E_MUL_PLAN_* (point_mul_batch, point_lincomb_batch)
 SEC1_COMPRESSED, SEC1_UNCOMPRESSED = 0, 1                  # include/p2e.h P2E_SEC1_*
 SIG_DER, SIG_COMPACT64, SIG_COMPACT65 = 0, 1, 2            # include/p2e.h P2E_SIG_*
 SIG_REQUIRE_LOW_S, SIG_NORMALIZE_S = 1, 2
@@ -92,6 +93,7 @@ EXPORTS = (
     "p2e_ecdsa_recover_batch", "p2e_ecdsa_sign_recoverable_batch",
     "p2e_hash_batch", "p2e_ecdsa_nonce_rfc6979_batch", "p2e_ecdsa_sign_deterministic_batch", "p2e_eth_address_batch",
     "p2e_point_msm", "p2e_point_msm_plan",
+    "p2e_point_mul_batch", "p2e_point_lincomb_batch", "p2e_point_add_batch",
     "p2e_point_decode_batch", "p2e_point_encode_batch", "p2e_sig_decode_batch", "p2e_sig_encode_batch",
 )
 
@@ -1098,6 +1100,42 @@ class Context:
         bad = self._check(self._L.p2e_point_msm(self._h, C.c_int(curve), C.c_uint(window_bits), _ptr(k), _ptr(px), _ptr(py),
                                                 C.c_size_t(n), _ptr(outx), _ptr(outy), _ptr(status), _ptr(point_err)))
         return outx, outy, status, point_err, bad
+
+    # ---- per-element point arithmetic (include/p2e.h p2e_point_mul_batch and the two after it) ----------------------------------
+    def point_mul_batch(self, k, px, py, curve=CURVE_SECP256K1, plan=MUL_PLAN_AUTO, outx=None, outy=None, err=None):
+        """k[i] * (px[i], py[i]) per element; k, px, py are (n, 32) little-endian, k taken modulo the group order, (0, 0) the
+        neutral element: (outx, outy, err, flagged count).  err holds WIRE_* codes: WIRE_COORD_RANGE / WIRE_NOT_ON_CURVE for
+        an invalid point, WIRE_INFINITY where the product is the neutral element (k = 0 mod n, P neutral); zeros are written
+        where it is not 0.  plan: MUL_PLAN_AUTO, MUL_PLAN_PLAIN, MUL_PLAN_GLV (secp256k1 only); the bytes do not depend on it."""
+        n = self._shape(k)[0]
+        outx = outx if outx is not None else self._packed(n)
+        outy = outy if outy is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_mul_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(k), _ptr(px), _ptr(py), _ptr(outx),
+                                                      _ptr(outy), C.c_size_t(n), _ptr(err)))
+        return outx, outy, err, bad
+
+    def point_lincomb_batch(self, a, b, px, py, curve=CURVE_SECP256K1, plan=MUL_PLAN_AUTO, outx=None, outy=None, err=None):
+        """a[i] * G + b[i] * (px[i], py[i]) per element, inputs and codes as for point_mul_batch (the point is checked whatever
+        b is): (outx, outy, err, flagged count).  WIRE_INFINITY where the sum is the neutral element."""
+        n = self._shape(a)[0]
+        outx = outx if outx is not None else self._packed(n)
+        outy = outy if outy is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_lincomb_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(a), _ptr(b), _ptr(px), _ptr(py),
+                                                          _ptr(outx), _ptr(outy), C.c_size_t(n), _ptr(err)))
+        return outx, outy, err, bad
+
+    def point_add_batch(self, px, py, qx, qy, curve=CURVE_SECP256K1, outx=None, outy=None, err=None):
+        """(px[i], py[i]) + (qx[i], qy[i]) per element, (0, 0) the neutral element: (outx, outy, err, flagged count).  P is
+        checked before Q; WIRE_INFINITY where the sum is the neutral element (P = -Q, both neutral)."""
+        n = self._shape(px)[0]
+        outx = outx if outx is not None else self._packed(n)
+        outy = outy if outy is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_add_batch(self._h, C.c_int(curve), _ptr(px), _ptr(py), _ptr(qx), _ptr(qy), _ptr(outx),
+                                                      _ptr(outy), C.c_size_t(n), _ptr(err)))
+        return outx, outy, err, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

@@ -26,6 +26,7 @@
 #include "sign.hpp"
 #include "recover.hpp"
 #include "pmsm.hpp"
+#include "point_arith.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
 
@@ -2856,6 +2857,160 @@ extern "C" long p2e_point_msm(p2e_ctx* c, int curve, unsigned window_bits, const
         launch_msm<P256>(c, a);
     else
         launch_msm<Secp256k1>(c, a);
+    return S.done(finish_call(c));
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// per-element point arithmetic (point_arith.hpp): k P, a G + b P, P + Q
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 1 beside the many-point sum, called from part 0.
+// plan: MUL_PLAN_PLAIN or MUL_PLAN_GLV (secp256k1 only), already chosen; table == nullptr: k P (b = the scalars), else a G + b P
+template <class CV>
+void launch_point_mul(p2e_ctx* c, int plan, const Aff* table, const uint8_t* a, const uint8_t* b, const uint8_t* px, const uint8_t* py,
+                      uint8_t* outx, uint8_t* outy, size_t n, uint8_t* err);
+template <class CV>
+void launch_point_add(p2e_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* qx, const uint8_t* qy, uint8_t* outx, uint8_t* outy,
+                      size_t n, uint8_t* err);
+#if P2E_HAS(1)
+template <class CV, int PLAN>
+static void launch_point_mul_plan(p2e_ctx* c, const Aff* table, const uint8_t* a, const uint8_t* b, const uint8_t* px, const uint8_t* py,
+                                  uint8_t* outx, uint8_t* outy, size_t n, uint8_t* err) {
+    if (table)
+        hipLaunchKernelGGL((k_point_lincomb<CV, PLAN>), grid1(n), dim3(BS), 0, c->stream, table, a, b, px, py, outx, outy, n, err,
+                           c->d_counter);
+    else
+        hipLaunchKernelGGL((k_point_mul<CV, PLAN>), grid1(n), dim3(BS), 0, c->stream, b, px, py, outx, outy, n, err, c->d_counter);
+}
+template <class CV>
+void launch_point_mul(p2e_ctx* c, int plan, const Aff* table, const uint8_t* a, const uint8_t* b, const uint8_t* px, const uint8_t* py,
+                      uint8_t* outx, uint8_t* outy, size_t n, uint8_t* err) {
+    if constexpr (CV::kAZero) {
+        if (plan == MUL_PLAN_GLV) return launch_point_mul_plan<CV, MUL_PLAN_GLV>(c, table, a, b, px, py, outx, outy, n, err);
+    }
+    launch_point_mul_plan<CV, MUL_PLAN_PLAIN>(c, table, a, b, px, py, outx, outy, n, err);
+}
+template <class CV>
+void launch_point_add(p2e_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* qx, const uint8_t* qy, uint8_t* outx, uint8_t* outy,
+                      size_t n, uint8_t* err) {
+    hipLaunchKernelGGL((k_point_add<CV>), grid1(n), dim3(BS), 0, c->stream, px, py, qx, qy, outx, outy, n, err, c->d_counter);
+}
+template void launch_point_mul<Secp256k1>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*,
+                                          uint8_t*, size_t, uint8_t*);
+template void launch_point_mul<P256>(p2e_ctx*, int, const Aff*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*,
+                                     uint8_t*, size_t, uint8_t*);
+template void launch_point_add<Secp256k1>(p2e_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, size_t,
+                                          uint8_t*);
+template void launch_point_add<P256>(p2e_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, size_t,
+                                     uint8_t*);
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static_assert(P2E_MUL_PLAN_AUTO == MUL_PLAN_AUTO && P2E_MUL_PLAN_PLAIN == MUL_PLAN_PLAIN && P2E_MUL_PLAN_GLV == MUL_PLAN_GLV,
+              "include/p2e.h and point_arith.hpp");
+// curve / plan checks of the two multiplying calls; *chosen = the walk.  AUTO on secp256k1 is GLV at every n: it is faster
+// than PLAIN by far more than the spread at each measured size (MEASUREMENTS.md section 16: 0.83 of PLAIN's time at 2^12,
+// 0.84 at 2^16, 0.63 at 2^20), and below 2^12 the call is one wave's dependent chain, which GLV halves.  P-256 has PLAIN only.
+static int point_mul_prepare(int curve, unsigned plan, size_t n, int* chosen) {
+    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
+        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
+        return P2E_E_INVALID;
+    }
+    if (plan != P2E_MUL_PLAN_AUTO && plan != P2E_MUL_PLAN_PLAIN && plan != P2E_MUL_PLAN_GLV) {
+        set_error("unknown plan (P2E_MUL_PLAN_AUTO, P2E_MUL_PLAN_PLAIN or P2E_MUL_PLAN_GLV)");
+        return P2E_E_INVALID;
+    }
+    if (plan == P2E_MUL_PLAN_GLV && curve != P2E_CURVE_SECP256K1) {
+        set_error("P2E_MUL_PLAN_GLV needs the endomorphism of secp256k1");
+        return P2E_E_INVALID;
+    }
+    if (n > ((size_t)1 << 31)) {
+        set_error("batch too large for one launch");
+        return P2E_E_INVALID;
+    }
+    *chosen = plan == P2E_MUL_PLAN_AUTO ? (curve == P2E_CURVE_SECP256K1 ? MUL_PLAN_GLV : MUL_PLAN_PLAIN) : (int)plan;
+    return 0;
+}
+extern "C" long p2e_point_mul_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* k32, const uint8_t* px32, const uint8_t* py32,
+                                    uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!k32 || !px32 || !py32 || !outx32 || !outy32 || !err) {
+        set_error("null pointer (k32, px32, py32, outx32, outy32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    int chosen = 0;
+    if (int rc = point_mul_prepare(curve, plan, n, &chosen)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    k32 = S.in(k32, n * 32);
+    px32 = S.in(px32, n * 32);
+    py32 = S.in(py32, n * 32);
+    outx32 = S.out(outx32, n * 32);
+    outy32 = S.out(outy32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (curve == P2E_CURVE_P256)
+        launch_point_mul<P256>(c, chosen, nullptr, nullptr, k32, px32, py32, outx32, outy32, n, err);
+    else
+        launch_point_mul<Secp256k1>(c, chosen, nullptr, nullptr, k32, px32, py32, outx32, outy32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_point_lincomb_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* a32, const uint8_t* b32, const uint8_t* px32,
+                                        const uint8_t* py32, uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!a32 || !b32 || !px32 || !py32 || !outx32 || !outy32 || !err) {
+        set_error("null pointer (a32, b32, px32, py32, outx32, outy32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    int chosen = 0, lane = 0;
+    if (int rc = point_mul_prepare(curve, plan, n, &chosen)) return rc;
+    const Aff* table = nullptr;
+    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &lane)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    a32 = S.in(a32, n * 32);
+    b32 = S.in(b32, n * 32);
+    px32 = S.in(px32, n * 32);
+    py32 = S.in(py32, n * 32);
+    outx32 = S.out(outx32, n * 32);
+    outy32 = S.out(outy32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (curve == P2E_CURVE_P256)
+        launch_point_mul<P256>(c, chosen, table, a32, b32, px32, py32, outx32, outy32, n, err);
+    else
+        launch_point_mul<Secp256k1>(c, chosen, table, a32, b32, px32, py32, outx32, outy32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_point_add_batch(p2e_ctx* c, int curve, const uint8_t* px32, const uint8_t* py32, const uint8_t* qx32, const uint8_t* qy32,
+                                    uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!px32 || !py32 || !qx32 || !qy32 || !outx32 || !outy32 || !err) {
+        set_error("null pointer (px32, py32, qx32, qy32, outx32, outy32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    int chosen = 0;
+    if (int rc = point_mul_prepare(curve, P2E_MUL_PLAN_PLAIN, n, &chosen)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    px32 = S.in(px32, n * 32);
+    py32 = S.in(py32, n * 32);
+    qx32 = S.in(qx32, n * 32);
+    qy32 = S.in(qy32, n * 32);
+    outx32 = S.out(outx32, n * 32);
+    outy32 = S.out(outy32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (curve == P2E_CURVE_P256)
+        launch_point_add<P256>(c, px32, py32, qx32, qy32, outx32, outy32, n, err);
+    else
+        launch_point_add<Secp256k1>(c, px32, py32, qx32, qy32, outx32, outy32, n, err);
     return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)

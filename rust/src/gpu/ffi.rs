@@ -263,6 +263,14 @@ extern "C" {
         n: usize, outx32: *mut u8, outy32: *mut u8, status: *mut u8, point_err: *mut u8) -> i64;
     pub fn p2e_point_msm_plan(curve: i32, n: usize, window_bits: u32, plan: *mut u64) -> i32;
 
+    // ---- per-element point arithmetic: k P (plan: P2E_MUL_PLAN_*), a G + b P, P + Q; err[i] is a P2E_WIRE_* code
+    pub fn p2e_point_mul_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, k32: *const u8, px32: *const u8, py32: *const u8,
+        outx32: *mut u8, outy32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_point_lincomb_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, a32: *const u8, b32: *const u8, px32: *const u8,
+        py32: *const u8, outx32: *mut u8, outy32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_point_add_batch(ctx: *mut P2eCtx, curve: i32, px32: *const u8, py32: *const u8, qx32: *const u8, qy32: *const u8,
+        outx32: *mut u8, outy32: *mut u8, n: usize, err: *mut u8) -> i64;
+
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
         pky32: *mut u8) -> i32;
