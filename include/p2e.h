@@ -23,8 +23,9 @@
  *   Return value: < 0 API misuse / HIP failure (p2e_last_error() has the text); >= 0 number of batch
  *   elements whose err byte is non-zero.  err[i] is a bit mask of P2E_ERR_* -- the conditions under
  *   which the reference generator panics.  Outputs of a flagged element are unspecified.
- *   (The four wire-form calls, p2e_point_decode_batch .. p2e_sig_encode_batch, and the three point-arithmetic calls,
- *   p2e_point_mul_batch .. p2e_point_add_batch, write a P2E_WIRE_* CODE instead.)
+ *   (The four wire-form calls, p2e_point_decode_batch .. p2e_sig_encode_batch, the three point-arithmetic calls,
+ *   p2e_point_mul_batch .. p2e_point_add_batch, and the point-table calls, p2e_point_table_create ..
+ *   p2e_ecdsa_verify_table_batch, write a P2E_WIRE_* CODE instead.)
  *   Nothing ever unwinds or aborts across this boundary.
  *
  * THREADING  A p2e_ctx is not thread-safe: one context per (host thread, device).  Calls are
@@ -767,6 +768,59 @@ long p2e_point_lincomb_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8
                              uint8_t *err);
 long p2e_point_add_batch(p2e_ctx *ctx, int curve, const uint8_t *px32, const uint8_t *py32, const uint8_t *qx32,
                          const uint8_t *qy32, uint8_t *outx32, uint8_t *outy32, size_t n, uint8_t *err);
+
+/* ---- point tables on either curve: precompute the window table of m caller points once, then multiply and verify
+ * without doublings (csrc/point_table.hpp; the reference's mul_precompute / mul_with_precomputation,
+ * curve/curve_multiplication.rs:18-73, and MsmPrecomputation, curve/curve_msm.rs:19-54).  For batches with few distinct
+ * points and many elements: a validator set, one CA key, the H of a Pedersen commitment, a static ECDH peer.
+ *   table    Aff[m][66][16] in device memory, P2E_POINT_TABLE_BYTES_PER_POINT bytes per point: entry [j][w][d] =
+ *            d 16^w P_j as 64 bytes (x then y, little-endian, canonical) for d = 1 .. 15; slot 0 is a copy of slot 1 --
+ *            for P_j = G exactly the generator's table of the signing calls.  Built on the device.
+ *   handle   p2e_point_table is an opaque object; the prototypes spell its pointer `void *` (p2e_point_table is a typedef
+ *            of void), so `p2e_point_table *t; p2e_point_table_create(..., &t);` is what a caller writes.  A table
+ *            belongs to the device of the context that made it and may be used by any context of that device.
+ *   create   1 <= m <= P2E_POINT_TABLE_MAX_POINTS.  point_err[j] (nullable) is the P2E_WIRE_* code of point j, first
+ *            failing check of: (0, 0) P2E_WIRE_INFINITY (the neutral element has no table), a coordinate >= p
+ *            P2E_WIRE_COORD_RANGE, off the curve P2E_WIRE_NOT_ON_CURVE.  If any point is rejected nothing is built,
+ *            *out = NULL and the return value is the number of rejected points (p2e_point_msm's rule); otherwise 0 and
+ *            *out is set.  SYNCHRONOUS even on a P2E_CTX_ASYNC context (it counts rejections).  Honours
+ *            P2E_CTX_HOST_POINTERS (px32, py32, point_err), restores the caller's current device.  P2E_E_NOMEM when the
+ *            allocation fails (the context stays usable); P2E_E_INVALID on a null pointer, an unknown curve or a bad m.
+ *   destroy  waits for the context's stream first, so a queued call cannot outlive its table.  NULL table: no-op.
+ *   read_window  the 16 entries x 64 bytes of window w (0 .. 65) of point j to HOST memory (synchronous): for tests and
+ *            for callers that persist a table.
+ *   the three batch calls   idx == NULL means point 0 for every element; idx[i] >= m gives err[i] = P2E_WIRE_BAD_INDEX,
+ *            zeros in the outputs, and no table word is read for that lane.  Scalars are taken modulo n with one
+ *            conditional subtraction; outputs are canonical affine coordinates.  One kernel per call on the caller's
+ *            stream, one lane per element: no internal streams, no LDS table, nothing in the private segment.  Host
+ *            pointers, async mode, n == 0, null pointers (only idx may be null) and failed calls behave as for the
+ *            point-arithmetic calls above.  The return value counts the non-zero err bytes.
+ *     p2e_point_table_mul_batch      out_i = k_i T[idx_i]; k = 0 (mod n): zeros and P2E_WIRE_INFINITY.  Byte for byte
+ *            what p2e_point_mul_batch writes for (k_i, P_idx_i) under every plan.
+ *     p2e_point_table_lincomb_batch  out_i = a_i G + b_i T[idx_i]: two window sums and one complete addition (a G = b P
+ *            doubles, a G = -b P is P2E_WIRE_INFINITY, either half may be empty).  The bytes of p2e_point_lincomb_batch.
+ *     p2e_ecdsa_verify_table_batch   the textbook verdict of curve/ecdsa.rs:42-62 under key T[idx_i].  err[i]:
+ *            P2E_WIRE_BAD_INDEX, then P2E_WIRE_SCALAR_RANGE for r = 0, r >= n, s = 0 or s >= n (r, s are not reduced,
+ *            msg is).  Where err[i] = 0: c = 1 / s, X = (msg c) G + (r c) P, valid[i] = 1 iff X is not the neutral
+ *            element and X.x mod n == r.  valid[i] = 0 wherever err[i] != 0; an invalid signature is NOT counted. */
+#define P2E_WIRE_BAD_INDEX 10
+#define P2E_POINT_TABLE_MAX_POINTS 65536
+#define P2E_POINT_TABLE_BYTES_PER_POINT 67584
+typedef void p2e_point_table;
+long p2e_point_table_create(p2e_ctx *ctx, int curve, const uint8_t *px32, const uint8_t *py32, size_t m,
+                            uint8_t *point_err /* nullable, m bytes */, void **out);
+void p2e_point_table_destroy(p2e_ctx *ctx, void *table);
+long p2e_point_table_num_points(const void *table);
+int p2e_point_table_curve(const void *table);
+int p2e_point_table_read_window(p2e_ctx *ctx, const void *table, size_t j, int w, uint8_t *out1024);
+long p2e_point_table_mul_batch(p2e_ctx *ctx, const void *table, const uint32_t *idx /* nullable */, const uint8_t *k32,
+                               uint8_t *outx32, uint8_t *outy32, size_t n, uint8_t *err);
+long p2e_point_table_lincomb_batch(p2e_ctx *ctx, const void *table, const uint32_t *idx /* nullable */,
+                                   const uint8_t *a32, const uint8_t *b32, uint8_t *outx32, uint8_t *outy32, size_t n,
+                                   uint8_t *err);
+long p2e_ecdsa_verify_table_batch(p2e_ctx *ctx, const void *table, const uint32_t *idx /* nullable */,
+                                  const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32, size_t n, uint8_t *err,
+                                  uint8_t *valid);
 
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */

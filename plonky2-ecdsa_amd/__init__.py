@@ -46,6 +46,8 @@ MSM_OK, MSM_NEUTRAL, MSM_BAD_POINT = 0, 1, 2               # include/p2e.h P2E_M
 # include/p2e.h P2E_WIRE_*: the err CODE (not a bit set) of point_decode_batch, point_encode_batch, sig_decode_batch, sig_encode_batch
 (WIRE_OK, WIRE_BAD_LENGTH, WIRE_BAD_PREFIX, WIRE_COORD_RANGE, WIRE_NOT_ON_CURVE, WIRE_INFINITY, WIRE_DER_SYNTAX, WIRE_DER_INTEGER,
  WIRE_SCALAR_RANGE, WIRE_HIGH_S) = range(10)
+WIRE_BAD_INDEX = 10                                        # the three point-table calls: idx[i] >= the table's point count
+POINT_TABLE_MAX_POINTS, POINT_TABLE_BYTES_PER_POINT = 65536, 67584   # include/p2e.h P2E_POINT_TABLE_*
 MUL_PLAN_AUTO, MUL_PLAN_PLAIN, MUL_PLAN_GLV = 0, 1, 2       # include/p2e.h P2E_MUL_PLAN_* (point_mul_batch, point_lincomb_batch)
 SEC1_COMPRESSED, SEC1_UNCOMPRESSED = 0, 1                  # include/p2e.h P2E_SEC1_*
 SIG_DER, SIG_COMPACT64, SIG_COMPACT65 = 0, 1, 2            # include/p2e.h P2E_SIG_*
@@ -95,6 +97,8 @@ EXPORTS = (
     "p2e_point_msm", "p2e_point_msm_plan",
     "p2e_point_mul_batch", "p2e_point_lincomb_batch", "p2e_point_add_batch",
     "p2e_point_decode_batch", "p2e_point_encode_batch", "p2e_sig_decode_batch", "p2e_sig_encode_batch",
+    "p2e_point_table_create", "p2e_point_table_destroy", "p2e_point_table_num_points", "p2e_point_table_curve",
+    "p2e_point_table_read_window", "p2e_point_table_mul_batch", "p2e_point_table_lincomb_batch", "p2e_ecdsa_verify_table_batch",
 )
 
 
@@ -168,7 +172,7 @@ def lib():
         for name in EXPORTS:
             if experimental and not hasattr(_lib, name):
                 continue
-            if name.endswith("_batch") or name in ("p2e_point_msm", "p2e_limb_split", "p2e_limb_pack", "p2e_columns_to_rows", "p2e_schedule_describe",
+            if name.endswith("_batch") or name in ("p2e_point_msm", "p2e_point_table_create", "p2e_point_table_num_points", "p2e_limb_split", "p2e_limb_pack", "p2e_columns_to_rows", "p2e_schedule_describe",
                                                    "p2e_schedule_num_cols", "p2e_aux_describe", "p2e_aux_num_cols", "p2e_compact_layout",
                                                    "p2e_columns_compact", "p2e_compact_to_rows", "p2e_curve_program_num_cols",
                                                    "p2e_curve_program_num_aux_cols", "p2e_curve_program_describe",
@@ -178,6 +182,10 @@ def lib():
                                                    "p2e_assemble_wires", "p2e_assemble_wires_compact"):
                 getattr(_lib, name).restype = C.c_long
         _lib.p2e_curve_program_scratch_bytes.restype = C.c_size_t
+        if hasattr(_lib, "p2e_point_table_destroy"):
+            _lib.p2e_point_table_destroy.restype = None
+            _lib.p2e_point_table_destroy.argtypes = [C.c_void_p, C.c_void_p]
+            _lib.p2e_point_table_num_points.argtypes = _lib.p2e_point_table_curve.argtypes = [C.c_void_p]
     return _lib
 
 
@@ -672,6 +680,45 @@ class _WireMap:
     __del__ = close
 
 
+class PointTable:
+    """The window tables of m caller points on one curve (include/p2e.h p2e_point_table_create): built once on the device,
+    then walked by Context.point_table_mul_batch, point_table_lincomb_batch and ecdsa_verify_table_batch without doublings.
+    px, py: (m, 32) little-endian, numpy on a host-pointer context, torch tensors otherwise.  A rejected point ((0, 0), a
+    coordinate >= p, off the curve) builds nothing and raises P2EError; its `codes` attribute holds the WIRE_* code of every
+    point and `rejected` their count.  The table lives until close() (or the context's end) and keeps its context alive."""
+
+    def __init__(self, ctx, px, py, curve=CURVE_SECP256K1, point_err=None):
+        self._ctx, self._h, self.curve = ctx, None, curve
+        m = ctx._shape(px)[0]
+        point_err = point_err if point_err is not None else ctx._vec(max(m, 1), np.uint8)[:m]
+        h = C.c_void_p()
+        rc = ctx._L.p2e_point_table_create(ctx._h, C.c_int(curve), _ptr(px), _ptr(py), C.c_size_t(m), _ptr(point_err), C.byref(h))
+        if rc != 0:
+            e = P2EError(f"p2e_point_table_create failed ({rc}): " +
+                         (ctx._L.p2e_last_error().decode() if rc < 0 else f"{rc} of {m} points rejected"))
+            e.rejected, e.codes = (int(rc), point_err) if rc > 0 else (0, None)
+            raise e
+        self._h = h
+        self.point_err = point_err
+
+    def __len__(self):
+        return int(self._ctx._L.p2e_point_table_num_points(self._h)) if self._h else 0
+
+    def read_window(self, j, w):
+        """(16, 2, 32) uint8: entries d = 0 .. 15 of window w of point j, x then y, little-endian (entry 0 copies entry 1)"""
+        out = np.zeros((16, 2, 32), np.uint8)
+        self._ctx._check(self._ctx._L.p2e_point_table_read_window(self._ctx._h, self._h, C.c_size_t(j), C.c_int(w),
+                                                                  out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def close(self):
+        if self._h and getattr(self._ctx, "_h", None):
+            self._ctx._L.p2e_point_table_destroy(self._ctx._h, self._h)
+        self._h = None
+
+    __del__ = close
+
+
 class Context:
     """One p2e_ctx: one per (host thread, device).
 
@@ -1136,6 +1183,51 @@ class Context:
         bad = self._check(self._L.p2e_point_add_batch(self._h, C.c_int(curve), _ptr(px), _ptr(py), _ptr(qx), _ptr(qy), _ptr(outx),
                                                       _ptr(outy), C.c_size_t(n), _ptr(err)))
         return outx, outy, err, bad
+
+    # ---- point tables (include/p2e.h p2e_point_table_create and the calls after it) -----------------------------------------
+    def point_table(self, px, py, curve=CURVE_SECP256K1, point_err=None):
+        """PointTable of the m points (px[j], py[j]), (m, 32) little-endian: see the class."""
+        return PointTable(self, px, py, curve, point_err)
+
+    def _table_args(self, table, idx, n):
+        if table._h is None:
+            raise P2EError("the point table is closed")
+        if idx is not None and (self._shape(idx)[0] != n or not _is_u32(idx)):
+            raise P2EError("idx must be (n,) uint32 (numpy) / int32 (torch)")
+
+    def point_table_mul_batch(self, table, k, idx=None, outx=None, outy=None, err=None):
+        """k[i] * T[idx[i]] per element (idx None: point 0 everywhere; (n,) uint32 / torch int32): (outx, outy, err, flagged
+        count), the bytes of point_mul_batch.  WIRE_BAD_INDEX where idx[i] >= len(table), WIRE_INFINITY where k = 0 (mod n)."""
+        n = self._shape(k)[0]
+        self._table_args(table, idx, n)
+        outx = outx if outx is not None else self._packed(n)
+        outy = outy if outy is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_table_mul_batch(self._h, table._h, _ptr(idx), _ptr(k), _ptr(outx), _ptr(outy),
+                                                            C.c_size_t(n), _ptr(err)))
+        return outx, outy, err, bad
+
+    def point_table_lincomb_batch(self, table, a, b, idx=None, outx=None, outy=None, err=None):
+        """a[i] * G + b[i] * T[idx[i]] per element: (outx, outy, err, flagged count), the bytes of point_lincomb_batch."""
+        n = self._shape(a)[0]
+        self._table_args(table, idx, n)
+        outx = outx if outx is not None else self._packed(n)
+        outy = outy if outy is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_table_lincomb_batch(self._h, table._h, _ptr(idx), _ptr(a), _ptr(b), _ptr(outx), _ptr(outy),
+                                                                C.c_size_t(n), _ptr(err)))
+        return outx, outy, err, bad
+
+    def ecdsa_verify_table_batch(self, table, msg, r, s, idx=None, err=None, valid=None):
+        """The textbook verdict of (msg[i], r[i], s[i]) under key T[idx[i]]: (err, valid, flagged count).  err: WIRE_BAD_INDEX,
+        then WIRE_SCALAR_RANGE for r or s outside [1, n); valid is 0 wherever err is not; invalid signatures are not counted."""
+        n = self._shape(msg)[0]
+        self._table_args(table, idx, n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        valid = valid if valid is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_ecdsa_verify_table_batch(self._h, table._h, _ptr(idx), _ptr(msg), _ptr(r), _ptr(s), C.c_size_t(n),
+                                                               _ptr(err), _ptr(valid)))
+        return err, valid, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

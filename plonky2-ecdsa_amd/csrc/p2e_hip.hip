@@ -27,6 +27,7 @@
 #include "recover.hpp"
 #include "pmsm.hpp"
 #include "point_arith.hpp"
+#include "point_table.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
 
@@ -3012,6 +3013,203 @@ extern "C" long p2e_point_add_batch(p2e_ctx* c, int curve, const uint8_t* px32, 
     else
         launch_point_add<Secp256k1>(c, px32, py32, qx32, qy32, outx32, outy32, n, err);
     return S.done(finish_call(c));
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// point tables (point_table.hpp): precomputed window tables of the caller's points, and the calls that walk them
+// ====================================================================================================
+// A table belongs to the device of the context that made it; `tab` is Aff[m][FB_WINDOWS][16].
+struct PointTable {
+    int curve = 0, device = 0;
+    size_t m = 0;
+    DeviceArray<Aff> tab;
+};
+// defined in part 1 beside the per-element point arithmetic, called from part 0.  All on the caller's stream.
+// scratch: TABLE_POW_BYTES per (point, window), then one u32 flag per point (zeroed), then one err byte per point
+template <class CV>
+void launch_table_powers(p2e_ctx* c, const uint8_t* px, const uint8_t* py, void* pow, size_t m, uint8_t* perr);
+template <class CV>
+void launch_table_rows(p2e_ctx* c, const void* pow, Aff* tab, size_t m, u32* flag, uint8_t* perr);
+// what: 0 = k T[idx] (b = the scalars), 1 = a G + b T[idx], 2 = the verdict (a = msg, b = r, s; out = valid)
+template <class CV>
+void launch_table_call(p2e_ctx* c, int what, const Aff* G, const Aff* tab, const u32* idx, u32 m, const uint8_t* a, const uint8_t* b,
+                       const uint8_t* s, uint8_t* outx, uint8_t* outy, size_t n, uint8_t* err);
+#if P2E_HAS(1)
+template <class CV>
+void launch_table_powers(p2e_ctx* c, const uint8_t* px, const uint8_t* py, void* pow, size_t m, uint8_t* perr) {
+    hipLaunchKernelGGL((k_table_powers<CV>), grid1(m), dim3(BS), 0, c->stream, px, py, pow, m, perr, c->d_counter);
+}
+template <class CV>
+void launch_table_rows(p2e_ctx* c, const void* pow, Aff* tab, size_t m, u32* flag, uint8_t* perr) {
+    const size_t rows = m * FB_WINDOWS;
+    hipLaunchKernelGGL((k_table_rows<CV>), grid1(rows), dim3(BS), 0, c->stream, pow, tab, rows, flag, perr, c->d_counter);
+}
+template <class CV>
+void launch_table_call(p2e_ctx* c, int what, const Aff* G, const Aff* tab, const u32* idx, u32 m, const uint8_t* a, const uint8_t* b,
+                       const uint8_t* s, uint8_t* outx, uint8_t* outy, size_t n, uint8_t* err) {
+    if (what == 0)
+        hipLaunchKernelGGL((k_table_mul<CV>), grid1(n), dim3(BS), 0, c->stream, tab, idx, m, b, outx, outy, n, err, c->d_counter);
+    else if (what == 1)
+        hipLaunchKernelGGL((k_table_lincomb<CV>), grid1(n), dim3(BS), 0, c->stream, G, tab, idx, m, a, b, outx, outy, n, err,
+                           c->d_counter);
+    else
+        hipLaunchKernelGGL((k_table_verify<CV>), grid1(n), dim3(BS), 0, c->stream, G, tab, idx, m, a, b, s, n, err, outx, c->d_counter);
+}
+template void launch_table_powers<Secp256k1>(p2e_ctx*, const uint8_t*, const uint8_t*, void*, size_t, uint8_t*);
+template void launch_table_powers<P256>(p2e_ctx*, const uint8_t*, const uint8_t*, void*, size_t, uint8_t*);
+template void launch_table_rows<Secp256k1>(p2e_ctx*, const void*, Aff*, size_t, u32*, uint8_t*);
+template void launch_table_rows<P256>(p2e_ctx*, const void*, Aff*, size_t, u32*, uint8_t*);
+template void launch_table_call<Secp256k1>(p2e_ctx*, int, const Aff*, const Aff*, const u32*, u32, const uint8_t*, const uint8_t*,
+                                           const uint8_t*, uint8_t*, uint8_t*, size_t, uint8_t*);
+template void launch_table_call<P256>(p2e_ctx*, int, const Aff*, const Aff*, const u32*, u32, const uint8_t*, const uint8_t*, const uint8_t*,
+                                      uint8_t*, uint8_t*, size_t, uint8_t*);
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static_assert(P2E_WIRE_BAD_INDEX == WIRE_BAD_INDEX && P2E_POINT_TABLE_MAX_POINTS == TABLE_MAX_POINTS &&
+                  P2E_POINT_TABLE_BYTES_PER_POINT == TABLE_POINT_ENTRIES * sizeof(Aff),
+              "include/p2e.h and point_table.hpp");
+// the stream's work done and the flagged count on the host, whatever the context's mode (create must count rejections)
+static long table_wait_count(p2e_ctx* c) {
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        set_error(std::string("kernel launch: ") + hipGetErrorString(le));
+        return P2E_E_HIP;
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_counter, c->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return (long)*c->h_counter;
+}
+extern "C" long p2e_point_table_create(p2e_ctx* c, int curve, const uint8_t* px32, const uint8_t* py32, size_t m, uint8_t* point_err,
+                                       void** out) {
+    if (out) *out = nullptr;
+    if (bad_common(c, m, m)) return P2E_E_INVALID;
+    if (!px32 || !py32 || !out) {
+        set_error("null pointer (px32, py32 and out are all required; point_err may be null)");
+        return P2E_E_INVALID;
+    }
+    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
+        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
+        return P2E_E_INVALID;
+    }
+    if (m < 1 || m > P2E_POINT_TABLE_MAX_POINTS) {
+        set_error("a table holds 1 .. P2E_POINT_TABLE_MAX_POINTS points");
+        return P2E_E_INVALID;
+    }
+    Staged S(c);   // (its guard puts the context's device in place and restores the caller's)
+    px32 = S.in(px32, m * 32);
+    py32 = S.in(py32, m * 32);
+    if (S.rc) return S.done(S.rc);
+    std::unique_ptr<PointTable> t(new PointTable());
+    t->curve = curve, t->device = c->device, t->m = m;
+    const size_t rows = m * FB_WINDOWS, flag_off = (rows * TABLE_POW_BYTES + 3) & ~(size_t)3, err_off = flag_off + 4 * m;
+    DeviceArray<unsigned char> scratch;
+    hipError_t e = scratch.alloc(err_off + m);
+    if (e == hipSuccess) e = t->tab.alloc(m * TABLE_POINT_ENTRIES);
+    if (e != hipSuccess) {
+        set_error("allocation of a table of " + std::to_string(m) + " points failed: " + hipGetErrorString(e));
+        return S.done(P2E_E_NOMEM);
+    }
+    u32* flag = reinterpret_cast<u32*>(scratch.get() + flag_off);
+    uint8_t* perr = scratch.get() + err_off;
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    HIP_TRY(hipMemsetAsync(flag, 0, 4 * m, c->stream));
+    if (curve == P2E_CURVE_P256)
+        launch_table_powers<P256>(c, px32, py32, scratch.get(), m, perr);
+    else
+        launch_table_powers<Secp256k1>(c, px32, py32, scratch.get(), m, perr);
+    long bad = table_wait_count(c);
+    if (bad == 0) {   // every point is fine: build the rows (a zero Z there rejects its point, see point_table.hpp)
+        if (curve == P2E_CURVE_P256)
+            launch_table_rows<P256>(c, scratch.get(), t->tab.get(), m, flag, perr);
+        else
+            launch_table_rows<Secp256k1>(c, scratch.get(), t->tab.get(), m, flag, perr);
+        bad = table_wait_count(c);
+    }
+    if (bad >= 0 && point_err) HIP_TRY(hipMemcpy(point_err, perr, m, hipMemcpyDefault));
+    if (bad == 0) *out = t.release();
+    return S.done(bad);
+}
+extern "C" void p2e_point_table_destroy(p2e_ctx* c, void* table) {
+    PointTable* t = static_cast<PointTable*>(table);
+    if (!t) return;
+    DeviceGuard guard(t->device);
+    if (c && c->stream) (void)hipStreamSynchronize(c->stream);   // a queued call must not outlive its table
+    delete t;
+}
+extern "C" long p2e_point_table_num_points(const void* table) {
+    return table ? (long)static_cast<const PointTable*>(table)->m : P2E_E_INVALID;
+}
+extern "C" int p2e_point_table_curve(const void* table) {
+    return table ? static_cast<const PointTable*>(table)->curve : P2E_E_INVALID;
+}
+extern "C" int p2e_point_table_read_window(p2e_ctx* c, const void* table, size_t j, int w, uint8_t* out1024) {
+    const PointTable* t = static_cast<const PointTable*>(table);
+    if (!c || !t || !out1024) {
+        set_error("null pointer (ctx, table and out1024 are all required)");
+        return P2E_E_INVALID;
+    }
+    if (t->device != c->device || j >= t->m || w < 0 || w >= FB_WINDOWS) {
+        set_error("no such window (the context's device, j < num_points, 0 <= w < 66)");
+        return P2E_E_INVALID;
+    }
+    DeviceGuard guard(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out1024, t->tab.get() + (j * FB_WINDOWS + (size_t)w) * 16, 16 * sizeof(Aff), hipMemcpyDefault));
+    return 0;
+}
+// what: as for launch_table_call; a = a32 / msg32 (null for what == 0), b = k32 / b32 / r32, s = s32 (what == 2 only),
+// out1 = outx32 / valid, out2 = outy32 (null for what == 2)
+static long table_call(p2e_ctx* c, const PointTable* t, int what, const uint32_t* idx, const uint8_t* a, const uint8_t* b,
+                       const uint8_t* s, uint8_t* out1, uint8_t* out2, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!t || !b || !out1 || !err || (what != 0 && !a) || (what == 2 ? !s : !out2)) {
+        set_error("null pointer (only idx may be null)");
+        return P2E_E_INVALID;
+    }
+    if (t->device != c->device) {
+        set_error("the table belongs to another device than the context");
+        return P2E_E_INVALID;
+    }
+    if (n > ((size_t)1 << 31)) {
+        set_error("batch too large for one launch");
+        return P2E_E_INVALID;
+    }
+    const Aff* G = nullptr;
+    int lane = 0;
+    if (what != 0)
+        if (int rc = sign_prepare(c, t->curve, P2E_SIGN_PLAN_LANE, n, &G, &lane)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    idx = S.in(idx, n * 4);
+    a = S.in(a, n * 32);
+    b = S.in(b, n * 32);
+    s = S.in(s, n * 32);
+    out1 = S.out(out1, what == 2 ? n : n * 32);
+    out2 = S.out(out2, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    if (t->curve == P2E_CURVE_P256)
+        launch_table_call<P256>(c, what, G, t->tab.get(), idx, (u32)t->m, a, b, s, out1, out2, n, err);
+    else
+        launch_table_call<Secp256k1>(c, what, G, t->tab.get(), idx, (u32)t->m, a, b, s, out1, out2, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_point_table_mul_batch(p2e_ctx* c, const void* table, const uint32_t* idx, const uint8_t* k32, uint8_t* outx32,
+                                          uint8_t* outy32, size_t n, uint8_t* err) {
+    return table_call(c, static_cast<const PointTable*>(table), 0, idx, nullptr, k32, nullptr, outx32, outy32, n, err);
+}
+extern "C" long p2e_point_table_lincomb_batch(p2e_ctx* c, const void* table, const uint32_t* idx, const uint8_t* a32, const uint8_t* b32,
+                                              uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
+    return table_call(c, static_cast<const PointTable*>(table), 1, idx, a32, b32, nullptr, outx32, outy32, n, err);
+}
+extern "C" long p2e_ecdsa_verify_table_batch(p2e_ctx* c, const void* table, const uint32_t* idx, const uint8_t* msg32, const uint8_t* r32,
+                                             const uint8_t* s32, size_t n, uint8_t* err, uint8_t* valid) {
+    return table_call(c, static_cast<const PointTable*>(table), 2, idx, msg32, r32, s32, valid, nullptr, n, err);
 }
 #endif   // P2E_HAS(0)
 

@@ -193,6 +193,82 @@ pub fn point_msm(ctx: *mut P2eCtx, curve: i32, scalars: &[BigUint], points: &[Op
     Ok((status == P2E_MSM_OK).then(|| (BigUint::from_bytes_le(&outx), BigUint::from_bytes_le(&outy))))
 }
 
+/// The window tables of a set of keys (`p2e_point_table_create`, host-pointer context): built once, then every
+/// multiplication by one of the keys is at most 64 mixed additions.  The borrow of the context keeps it alive for as long
+/// as the table exists; dropping the table waits for the context's stream and frees the device memory.
+pub struct PointTable<'c> {
+    ctx: &'c P2eCtx,
+    table: *mut std::ffi::c_void,
+}
+
+impl<'c> PointTable<'c> {
+    fn raw(&self) -> *mut P2eCtx {
+        self.ctx as *const P2eCtx as *mut P2eCtx
+    }
+
+    /// `Err`: the call failed, or some key is the neutral element, out of range or off the curve (nothing is built then;
+    /// the message names the first such key and its `P2E_WIRE_*` code).
+    pub fn new(ctx: &'c P2eCtx, curve: i32, keys: &[(BigUint, BigUint)]) -> Result<Self> {
+        let m = keys.len();
+        let (px, py) = (pack32(keys.iter().map(|k| k.0.clone()), m), pack32(keys.iter().map(|k| k.1.clone()), m));
+        let mut err = vec![0u8; m];
+        let mut table = std::ptr::null_mut();
+        let rc = unsafe {
+            p2e_point_table_create(ctx as *const P2eCtx as *mut P2eCtx, curve, px.as_ptr(), py.as_ptr(), m, err.as_mut_ptr(), &mut table)
+        };
+        ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+        let first = err.iter().position(|&e| e != 0);
+        ensure!(rc == 0, "{rc} keys rejected, the first at index {first:?} with code {:?}", first.map(|i| err[i]));
+        Ok(PointTable { ctx, table })
+    }
+
+    pub fn len(&self) -> usize {
+        unsafe { p2e_point_table_num_points(self.table) as usize }
+    }
+
+    /// `k_i · key[idx_i]` (`p2e_point_table_mul_batch`); `None`: the product is the neutral element.
+    pub fn mul(&self, idx: &[u32], scalars: &[BigUint]) -> Result<Vec<Option<(BigUint, BigUint)>>> {
+        let n = scalars.len();
+        ensure!(idx.len() == n);
+        let k = pack32(scalars.iter().cloned(), n);
+        let (mut ox, mut oy, mut err) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n]);
+        let rc = unsafe {
+            p2e_point_table_mul_batch(self.raw(), self.table, idx.as_ptr(), k.as_ptr(), ox.as_mut_ptr(), oy.as_mut_ptr(), n, err.as_mut_ptr())
+        };
+        ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+        (0..n)
+            .map(|i| match err[i] {
+                P2E_WIRE_OK => Ok(Some((BigUint::from_bytes_le(&ox[32 * i..32 * i + 32]), BigUint::from_bytes_le(&oy[32 * i..32 * i + 32])))),
+                P2E_WIRE_INFINITY => Ok(None),
+                code => Err(anyhow::anyhow!("element {i}: code {code} (index {} of {} keys)", idx[i], self.len())),
+            })
+            .collect()
+    }
+
+    /// The verdicts of `(msg_i, r_i, s_i)` under `key[idx_i]` (`p2e_ecdsa_verify_table_batch`); a signature with `r` or `s`
+    /// outside `[1, n)` is simply invalid here, a bad index is an error.
+    pub fn verify(&self, idx: &[u32], sigs: &[(BigUint, BigUint, BigUint)]) -> Result<Vec<bool>> {
+        let n = sigs.len();
+        ensure!(idx.len() == n);
+        let msg = pack32(sigs.iter().map(|g| g.0.clone()), n);
+        let (r, s) = (pack32(sigs.iter().map(|g| g.1.clone()), n), pack32(sigs.iter().map(|g| g.2.clone()), n));
+        let (mut err, mut valid) = (vec![0u8; n], vec![0u8; n]);
+        let rc = unsafe {
+            p2e_ecdsa_verify_table_batch(self.raw(), self.table, idx.as_ptr(), msg.as_ptr(), r.as_ptr(), s.as_ptr(), n, err.as_mut_ptr(),
+                                         valid.as_mut_ptr())
+        };
+        ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+        ensure!(!err.contains(&P2E_WIRE_BAD_INDEX), "a key index is out of range ({} keys)", self.len());
+        Ok(valid.iter().map(|&v| v != 0).collect())
+    }
+}
+
+impl Drop for PointTable<'_> {
+    fn drop(&mut self) {
+        unsafe { p2e_point_table_destroy(self.raw(), self.table) }
+    }
+}
+
 /// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
 /// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
 /// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).

@@ -97,6 +97,9 @@ pub const P2E_WIRE_DER_SYNTAX: u8 = 6;
 pub const P2E_WIRE_DER_INTEGER: u8 = 7;
 pub const P2E_WIRE_SCALAR_RANGE: u8 = 8;
 pub const P2E_WIRE_HIGH_S: u8 = 9;
+pub const P2E_WIRE_BAD_INDEX: u8 = 10; // the point-table calls: idx[i] >= the table's point count
+pub const P2E_POINT_TABLE_MAX_POINTS: usize = 65536;
+pub const P2E_POINT_TABLE_BYTES_PER_POINT: usize = 67584;
 pub const P2E_SEC1_COMPRESSED: i32 = 0;
 pub const P2E_SEC1_UNCOMPRESSED: i32 = 1;
 pub const P2E_SIG_DER: i32 = 0;
@@ -270,6 +273,21 @@ extern "C" {
         py32: *const u8, outx32: *mut u8, outy32: *mut u8, n: usize, err: *mut u8) -> i64;
     pub fn p2e_point_add_batch(ctx: *mut P2eCtx, curve: i32, px32: *const u8, py32: *const u8, qx32: *const u8, qy32: *const u8,
         outx32: *mut u8, outy32: *mut u8, n: usize, err: *mut u8) -> i64;
+
+    // ---- point tables: window tables of caller points, built once on the device (the handle is an opaque `void *` in the
+    // header; bind.rs wraps it in `PointTable`)
+    pub fn p2e_point_table_create(ctx: *mut P2eCtx, curve: i32, px32: *const u8, py32: *const u8, m: usize, point_err: *mut u8,
+        out: *mut *mut c_void) -> i64;
+    pub fn p2e_point_table_destroy(ctx: *mut P2eCtx, table: *mut c_void);
+    pub fn p2e_point_table_num_points(table: *const c_void) -> i64;
+    pub fn p2e_point_table_curve(table: *const c_void) -> i32;
+    pub fn p2e_point_table_read_window(ctx: *mut P2eCtx, table: *const c_void, j: usize, w: i32, out1024: *mut u8) -> i32;
+    pub fn p2e_point_table_mul_batch(ctx: *mut P2eCtx, table: *const c_void, idx: *const u32, k32: *const u8, outx32: *mut u8,
+        outy32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_point_table_lincomb_batch(ctx: *mut P2eCtx, table: *const c_void, idx: *const u32, a32: *const u8, b32: *const u8,
+        outx32: *mut u8, outy32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_ecdsa_verify_table_batch(ctx: *mut P2eCtx, table: *const c_void, idx: *const u32, msg32: *const u8, r32: *const u8,
+        s32: *const u8, n: usize, err: *mut u8, valid: *mut u8) -> i64;
 
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
