@@ -822,6 +822,59 @@ long p2e_ecdsa_verify_table_batch(p2e_ctx *ctx, const void *table, const uint32_
                                   const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32, size_t n, uint8_t *err,
                                   uint8_t *valid);
 
+/* ---- BIP-340 Schnorr signatures on secp256k1 (csrc/schnorr.hpp): x-only keys, default signing, the per-element verdict
+ * and the standard's batch verification.  The curve is secp256k1 alone (no curve argument, as p2e_eth_address_batch).
+ *   bytes    EVERY argument of these calls is the standard's byte string, BIG-endian (this header's rule for wire forms:
+ *            these objects exist only in wire form and the tagged hashes consume exactly those bytes): sk32, msg32, aux32,
+ *            the x-only pk32 (element i at +32 i) and sig64 = bytes(r) || bytes(s) (element i at +64 i); every array
+ *            4-byte aligned.  msg32 is 32 opaque bytes, never reduced.  The only little-endian values are the px32, py32
+ *            that p2e_xonly_decode_batch writes.
+ *   err[i]   a P2E_WIRE_* CODE: the first failing check in the order given below; a flagged element writes zeros to all
+ *            its outputs.  The return value counts the non-zero err bytes.  Null pointers, n == 0 (returns 0), host
+ *            pointers, async mode, the current device and failed calls behave as for the point-arithmetic calls.
+ *   p2e_schnorr_public_key_batch   d = int(sk); d = 0 or d >= n: P2E_WIRE_SCALAR_RANGE (the standard fails here, nothing is
+ *            reduced).  Otherwise pk = bytes(x(d G)).
+ *   p2e_schnorr_sign_batch   the standard's "Default Signing"; all pointers required.  The range check of d as above; P = d G,
+ *            d := n - d where P.y is odd; t = bytes(d) xor H_aux(aux); k' = int(H_nonce(t || bytes(P.x) || msg)) mod n,
+ *            k' = 0: P2E_WIRE_INFINITY; R = k' G, k = n - k' where R.y is odd; e = int(H_challenge(bytes(R.x) || bytes(P.x)
+ *            || msg)) mod n; sig = bytes(R.x) || bytes((k + e d) mod n).  The verification of the fresh signature that the
+ *            standard recommends as a last step is NOT done: a caller that wants it runs p2e_schnorr_verify_batch.  d, t,
+ *            k' and k never leave the lane's registers.
+ *   p2e_schnorr_verify_batch   err[i], in order: pk >= p P2E_WIRE_COORD_RANGE; pk^3 + 7 not a square P2E_WIRE_NOT_ON_CURVE;
+ *            r >= p P2E_WIRE_COORD_RANGE; s >= n P2E_WIRE_SCALAR_RANGE.  Where err[i] = 0: P = lift_x(pk) (even y), e as
+ *            above, X = s G + (n - e) P; valid[i] = 1 iff X is not the neutral element, X.y is even and X.x == r.  A
+ *            well-formed but wrong signature -- an r that is on no curve point and s G = e P among them -- has err = 0,
+ *            valid = 0 and is NOT counted.  valid[i] = 0 wherever err[i] != 0.
+ *   p2e_xonly_decode_batch   lift_x(pk) with even y as the library's little-endian affine point (px32, py32): the bridge to
+ *            p2e_point_lincomb_batch (Taproot's P + t G), p2e_point_table_create, p2e_point_msm and
+ *            p2e_point_encode_batch.  err[i]: the first two checks of the verifier.
+ *   p2e_schnorr_verify_aggregate   the standard's "Batch Verification": ONE verdict byte for the whole batch.
+ *            *verdict = 1 iff no element is flagged and
+ *                (sum a_i s_i mod n) G + sum a_i (-R_i) + sum (a_i e_i mod n) (-P_i)   is the neutral element,
+ *            R_i = lift_x(r_i), P_i = lift_x(pk_i), with the randomisers fixed here so that every implementation gives the
+ *            same bytes: a_i = the first 16 bytes of SHA-256(seed32 || LE64(i)) read as a big-endian integer, 0 replaced
+ *            by 1; no a_i is fixed at 1.  seed32 is the CALLER's and must be unpredictable to whoever produced the
+ *            signatures -- fresh randomness, or a hash of the whole batch (every msg, pk and sig); with a seed the signer
+ *            knows, cancelling errors pass.  The library neither draws nor checks it.
+ *            err[i] (nullable): the verifier's four checks, then r^3 + 7 not a square: P2E_WIRE_NOT_ON_CURVE (the lift of r
+ *            must exist here).  A flagged element contributes the neutral element and makes the verdict 0.  Return value:
+ *            the number of flagged elements.  n == 0 gives verdict 1 (no pointer but err may be null even then);
+ *            2 n + 1 > 2^24 is P2E_E_INVALID.  window_bits is p2e_point_msm's, taken for 2 n + 1 points.
+ *            One preparation kernel (one lane per signature) and one small
+ *            finishing kernel write the 2 n + 1 terms into a scratch block of the context (kept, regrown on need), then
+ *            p2e_point_msm's seven launches and one verdict kernel run on the same stream; verdict is a device pointer
+ *            unless the context stages host pointers.  There is NO fallback that locates a bad element: on verdict 0 the
+ *            caller runs p2e_schnorr_verify_batch on the batch. */
+long p2e_schnorr_public_key_batch(p2e_ctx *ctx, const uint8_t *sk32, uint8_t *pk32, size_t n, uint8_t *err);
+long p2e_schnorr_sign_batch(p2e_ctx *ctx, const uint8_t *msg32, const uint8_t *sk32, const uint8_t *aux32, uint8_t *sig64,
+                            size_t n, uint8_t *err);
+long p2e_schnorr_verify_batch(p2e_ctx *ctx, const uint8_t *msg32, const uint8_t *pk32, const uint8_t *sig64, size_t n,
+                              uint8_t *err, uint8_t *valid);
+long p2e_xonly_decode_batch(p2e_ctx *ctx, const uint8_t *pk32, uint8_t *px32, uint8_t *py32, size_t n, uint8_t *err);
+long p2e_schnorr_verify_aggregate(p2e_ctx *ctx, const uint8_t *msg32, const uint8_t *pk32, const uint8_t *sig64, size_t n,
+                                  const uint8_t *seed32, unsigned window_bits, uint8_t *verdict,
+                                  uint8_t *err /* nullable */);
+
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */
 int p2e_synth_signatures(uint64_t seed, size_t first, size_t n, uint8_t *msg32, uint8_t *r32, uint8_t *s32,

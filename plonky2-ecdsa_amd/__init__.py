@@ -99,6 +99,8 @@ EXPORTS = (
     "p2e_point_decode_batch", "p2e_point_encode_batch", "p2e_sig_decode_batch", "p2e_sig_encode_batch",
     "p2e_point_table_create", "p2e_point_table_destroy", "p2e_point_table_num_points", "p2e_point_table_curve",
     "p2e_point_table_read_window", "p2e_point_table_mul_batch", "p2e_point_table_lincomb_batch", "p2e_ecdsa_verify_table_batch",
+    "p2e_schnorr_public_key_batch", "p2e_schnorr_sign_batch", "p2e_schnorr_verify_batch", "p2e_xonly_decode_batch",
+    "p2e_schnorr_verify_aggregate",
 )
 
 
@@ -172,7 +174,7 @@ def lib():
         for name in EXPORTS:
             if experimental and not hasattr(_lib, name):
                 continue
-            if name.endswith("_batch") or name in ("p2e_point_msm", "p2e_point_table_create", "p2e_point_table_num_points", "p2e_limb_split", "p2e_limb_pack", "p2e_columns_to_rows", "p2e_schedule_describe",
+            if name.endswith("_batch") or name in ("p2e_point_msm", "p2e_schnorr_verify_aggregate", "p2e_point_table_create", "p2e_point_table_num_points", "p2e_limb_split", "p2e_limb_pack", "p2e_columns_to_rows", "p2e_schedule_describe",
                                                    "p2e_schedule_num_cols", "p2e_aux_describe", "p2e_aux_num_cols", "p2e_compact_layout",
                                                    "p2e_columns_compact", "p2e_compact_to_rows", "p2e_curve_program_num_cols",
                                                    "p2e_curve_program_num_aux_cols", "p2e_curve_program_describe",
@@ -1228,6 +1230,64 @@ class Context:
         bad = self._check(self._L.p2e_ecdsa_verify_table_batch(self._h, table._h, _ptr(idx), _ptr(msg), _ptr(r), _ptr(s), C.c_size_t(n),
                                                                _ptr(err), _ptr(valid)))
         return err, valid, bad
+
+    # ---- BIP-340 Schnorr signatures on secp256k1 (include/p2e.h p2e_schnorr_public_key_batch and the four calls after it) ------
+    def _sig64(self, n):
+        if self.host_pointers:
+            return np.zeros((n, 64), dtype=np.uint8)
+        import torch
+        return torch.empty((n, 64), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def schnorr_public_key_batch(self, sk, pk=None, err=None):
+        """The x-only public keys of (n, 32) BIG-endian secret keys: (pk (n, 32) big-endian, err, flagged count).  sk = 0 or
+        sk >= n: zeros and WIRE_SCALAR_RANGE (nothing is reduced)."""
+        n = self._shape(sk)[0]
+        pk = pk if pk is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_schnorr_public_key_batch(self._h, _ptr(sk), _ptr(pk), C.c_size_t(n), _ptr(err)))
+        return pk, err, bad
+
+    def schnorr_sign_batch(self, msg, sk, aux, sig=None, err=None):
+        """BIP-340 default signing of (n, 32) messages under (n, 32) secret keys with (n, 32) auxiliary randomness, all the
+        standard's big-endian byte strings: (sig (n, 64) = r || s, err, flagged count).  WIRE_SCALAR_RANGE for a key out of
+        range, WIRE_INFINITY for a zero nonce; the fresh signature is not verified."""
+        n = self._shape(msg)[0]
+        sig = sig if sig is not None else self._sig64(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_schnorr_sign_batch(self._h, _ptr(msg), _ptr(sk), _ptr(aux), _ptr(sig), C.c_size_t(n), _ptr(err)))
+        return sig, err, bad
+
+    def schnorr_verify_batch(self, msg, pk, sig, err=None, valid=None):
+        """The BIP-340 verdict of every (msg (n, 32), pk (n, 32) x-only, sig (n, 64)): (err, valid, flagged count).  err holds
+        WIRE_* codes for a malformed key or signature; a well-formed wrong signature has err 0, valid 0 and is not counted."""
+        n = self._shape(msg)[0]
+        err = err if err is not None else self._vec(n, np.uint8)
+        valid = valid if valid is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_schnorr_verify_batch(self._h, _ptr(msg), _ptr(pk), _ptr(sig), C.c_size_t(n), _ptr(err), _ptr(valid)))
+        return err, valid, bad
+
+    def xonly_decode_batch(self, pk, px=None, py=None, err=None):
+        """lift_x of (n, 32) big-endian x-only keys: (px, py, err, flagged count), the library's LITTLE-endian affine point
+        with even y -- what point_lincomb_batch, point_table, point_msm and point_encode_batch take."""
+        n = self._shape(pk)[0]
+        px = px if px is not None else self._packed(n)
+        py = py if py is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_xonly_decode_batch(self._h, _ptr(pk), _ptr(px), _ptr(py), C.c_size_t(n), _ptr(err)))
+        return px, py, err, bad
+
+    def schnorr_verify_aggregate(self, msg, pk, sig, seed, window_bits=MSM_WINDOW_AUTO, verdict=None, err=None, want_err=True, n=None):
+        """BIP-340 batch verification: ONE verdict for the whole batch, (verdict (1,), err (n,) or None, flagged count).
+        seed (32,) uint8 must be unpredictable to whoever made the signatures (fresh randomness or a hash of the whole
+        batch).  verdict 1 iff nothing is flagged and the randomised sum is the neutral element; on 0 run
+        schnorr_verify_batch to find the element.  n: the batch size where it is not msg's first dimension (n = 0)."""
+        n = self._shape(msg)[0] if n is None else n
+        verdict = verdict if verdict is not None else self._vec(1, np.uint8)
+        if err is None and want_err:
+            err = self._vec(max(n, 1), np.uint8)[:n]
+        bad = self._check(self._L.p2e_schnorr_verify_aggregate(self._h, _ptr(msg), _ptr(pk), _ptr(sig), C.c_size_t(n), _ptr(seed),
+                                                                C.c_uint(window_bits), _ptr(verdict), _ptr(err)))
+        return verdict, err, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

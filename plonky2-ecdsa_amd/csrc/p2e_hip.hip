@@ -28,6 +28,7 @@
 #include "pmsm.hpp"
 #include "point_arith.hpp"
 #include "point_table.hpp"
+#include "schnorr.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
 
@@ -38,7 +39,7 @@ using host::COMPACT_WIDE;
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
 // streaming passes, descriptions;  1 = the fused pipeline of the two built-in programs (run_program);  2 / 3 = the
 // curve-program pipeline instantiated for secp256k1 / P-256 (run_curve_program<CV>).  Undefined = everything in one
-// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest.  Small static helpers (error text, staging, scratch) are compiled into every part.
+// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 kernels (schnorr.hpp) ride in part 3.  Small static helpers (error text, staging, scratch) are compiled into every part.
 #ifndef P2E_PART
 #define P2E_PART (-1)
 #endif
@@ -604,6 +605,8 @@ struct p2e_ctx {
     size_t scratch_bytes = 0;
     DeviceArray<unsigned char> d_msm;   // scratch of p2e_point_msm (pmsm.hpp MsmPlan): allocated on first need, kept, regrown
     size_t msm_bytes = 0;
+    DeviceArray<unsigned char> d_schnorr;   // the 2 n + 1 terms of p2e_schnorr_verify_aggregate (SchnorrAggLayout): kept and regrown like d_msm
+    size_t schnorr_bytes = 0;
     unsigned long long* d_counter = nullptr;
     unsigned long long* h_counter = nullptr;  // pinned
     hipEvent_t ev[6] = {};   // [0],[1] around k_scalar, [5] end of the call (2..4 unused)
@@ -3210,6 +3213,224 @@ extern "C" long p2e_point_table_lincomb_batch(p2e_ctx* c, const void* table, con
 extern "C" long p2e_ecdsa_verify_table_batch(p2e_ctx* c, const void* table, const uint32_t* idx, const uint8_t* msg32, const uint8_t* r32,
                                              const uint8_t* s32, size_t n, uint8_t* err, uint8_t* valid) {
     return table_call(c, static_cast<const PointTable*>(table), 2, idx, msg32, r32, s32, valid, nullptr, n, err);
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// BIP-340 Schnorr signatures on secp256k1 (schnorr.hpp): keys, signing, the per-element verdict, the aggregate check
+// ====================================================================================================
+// The scratch block of the aggregate check: the 2 n + 1 terms in the MSM's input layout, the preparation kernel's per-block
+// partial sums, and what the MSM writes besides its own scratch (the sum's coordinates, its status, its rejected count).
+struct SchnorrAggLayout {
+    size_t o_k, o_px, o_py, o_partial, o_outx, o_outy, o_status, o_rejected, total;
+    u32 blocks;
+    explicit SchnorrAggLayout(size_t n) {
+        size_t at = 0;
+        auto take = [&](size_t bytes) {
+            const size_t o = at;
+            at += (bytes + 255) & ~(size_t)255;
+            return o;
+        };
+        const size_t terms = 2 * n + 1;
+        blocks = (u32)((n + SCHNORR_AGG_LANES - 1) / SCHNORR_AGG_LANES);
+        o_k = take(terms * 32), o_px = take(terms * 32), o_py = take(terms * 32);
+        o_partial = take((size_t)(blocks ? blocks : 1) * sizeof(U256));
+        o_outx = take(32), o_outy = take(32), o_status = take(1), o_rejected = take(sizeof(unsigned long long));
+        total = at;
+    }
+};
+// one launch each on the caller's stream, the aggregate's three kernels around launch_msm<Secp256k1>; defined in part 3,
+// the part with the least code of its own, called from part 0
+void launch_schnorr_public_key(p2e_ctx* c, const Aff* table, const uint8_t* sk, uint8_t* pk, size_t n, uint8_t* err);
+void launch_schnorr_sign(p2e_ctx* c, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* aux, uint8_t* sig, size_t n,
+                         uint8_t* err);
+void launch_schnorr_verify(p2e_ctx* c, const Aff* table, const uint8_t* msg, const uint8_t* pk, const uint8_t* sig, size_t n, uint8_t* err,
+                           uint8_t* valid);
+void launch_xonly_decode(p2e_ctx* c, const uint8_t* pk, uint8_t* px, uint8_t* py, size_t n, uint8_t* err);
+void launch_schnorr_agg_prepare(p2e_ctx* c, const Aff* table, const SchnorrAggLayout& L, unsigned char* block, const uint8_t* msg,
+                                const uint8_t* pk, const uint8_t* sig, const uint8_t* seed, size_t n, uint8_t* err);
+void launch_schnorr_agg_verdict(p2e_ctx* c, const SchnorrAggLayout& L, const unsigned char* block, uint8_t* verdict);
+#if P2E_HAS(3)
+void launch_schnorr_public_key(p2e_ctx* c, const Aff* table, const uint8_t* sk, uint8_t* pk, size_t n, uint8_t* err) {
+    hipLaunchKernelGGL((k_schnorr_public_key<0>), grid1(n), dim3(BS), 0, c->stream, table, sk, pk, n, err, c->d_counter);
+}
+void launch_schnorr_sign(p2e_ctx* c, const Aff* table, const uint8_t* msg, const uint8_t* sk, const uint8_t* aux, uint8_t* sig, size_t n,
+                         uint8_t* err) {
+    hipLaunchKernelGGL((k_schnorr_sign<0>), grid1(n), dim3(BS), 0, c->stream, table, msg, sk, aux, sig, n, err, c->d_counter);
+}
+void launch_schnorr_verify(p2e_ctx* c, const Aff* table, const uint8_t* msg, const uint8_t* pk, const uint8_t* sig, size_t n, uint8_t* err,
+                           uint8_t* valid) {
+    hipLaunchKernelGGL((k_schnorr_verify<0>), grid1(n), dim3(BS), 0, c->stream, table, msg, pk, sig, n, err, valid, c->d_counter);
+}
+void launch_xonly_decode(p2e_ctx* c, const uint8_t* pk, uint8_t* px, uint8_t* py, size_t n, uint8_t* err) {
+    hipLaunchKernelGGL((k_xonly_decode<0>), grid1(n), dim3(BS), 0, c->stream, pk, px, py, n, err, c->d_counter);
+}
+// the preparation kernel (n > 0) and the finishing kernel: afterwards the block holds all 2 n + 1 terms
+void launch_schnorr_agg_prepare(p2e_ctx* c, const Aff* table, const SchnorrAggLayout& L, unsigned char* block, const uint8_t* msg,
+                                const uint8_t* pk, const uint8_t* sig, const uint8_t* seed, size_t n, uint8_t* err) {
+    static_assert(SCHNORR_AGG_LANES == BS, "the preparation kernel's block is the library's block");
+    U256* partial = reinterpret_cast<U256*>(block + L.o_partial);
+    if (n)
+        hipLaunchKernelGGL((k_schnorr_agg_prepare<0>), dim3(L.blocks), dim3(SCHNORR_AGG_LANES), 0, c->stream, msg, pk, sig, seed, n,
+                           block + L.o_k, block + L.o_px, block + L.o_py, partial, err, c->d_counter);
+    hipLaunchKernelGGL((k_schnorr_agg_finish<0>), dim3(1), dim3(SCHNORR_AGG_LANES), 0, c->stream, table, partial, L.blocks, block + L.o_k,
+                       block + L.o_px, block + L.o_py);
+}
+void launch_schnorr_agg_verdict(p2e_ctx* c, const SchnorrAggLayout& L, const unsigned char* block, uint8_t* verdict) {
+    hipLaunchKernelGGL((k_schnorr_agg_verdict<0>), dim3(1), dim3(64), 0, c->stream, block + L.o_status, c->d_counter, verdict);
+}
+#endif   // P2E_HAS(3)
+
+#if P2E_HAS(0)
+// the generator's table; n beyond one launch is refused (sign_prepare's rule)
+static int schnorr_prepare(p2e_ctx* c, size_t n, const Aff** table) {
+    int lane = 0;
+    return sign_prepare(c, P2E_CURVE_SECP256K1, P2E_SIGN_PLAN_LANE, n, table, &lane);
+}
+extern "C" long p2e_schnorr_public_key_batch(p2e_ctx* c, const uint8_t* sk32, uint8_t* pk32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!sk32 || !pk32 || !err) {
+        set_error("null pointer (sk32, pk32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    sk32 = S.in(sk32, n * 32);
+    pk32 = S.out(pk32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_schnorr_public_key(c, table, sk32, pk32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_schnorr_sign_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* aux32, uint8_t* sig64, size_t n,
+                                       uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !sk32 || !aux32 || !sig64 || !err) {
+        set_error("null pointer (msg32, sk32, aux32, sig64 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    msg32 = S.in(msg32, n * 32);
+    sk32 = S.in(sk32, n * 32);
+    aux32 = S.in(aux32, n * 32);
+    sig64 = S.out(sig64, n * 64);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_schnorr_sign(c, table, msg32, sk32, aux32, sig64, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_schnorr_verify_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* pk32, const uint8_t* sig64, size_t n, uint8_t* err,
+                                         uint8_t* valid) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !pk32 || !sig64 || !err || !valid) {
+        set_error("null pointer (msg32, pk32, sig64, err and valid are all required)");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    msg32 = S.in(msg32, n * 32);
+    pk32 = S.in(pk32, n * 32);
+    sig64 = S.in(sig64, n * 64);
+    err = S.out(err, n);
+    valid = S.out(valid, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_schnorr_verify(c, table, msg32, pk32, sig64, n, err, valid);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_xonly_decode_batch(p2e_ctx* c, const uint8_t* pk32, uint8_t* px32, uint8_t* py32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!pk32 || !px32 || !py32 || !err) {
+        set_error("null pointer (pk32, px32, py32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    if (n > ((size_t)1 << 31)) {
+        set_error("batch too large for one launch");
+        return P2E_E_INVALID;
+    }
+    if (n == 0) return 0;
+    Staged S(c);
+    pk32 = S.in(pk32, n * 32);
+    px32 = S.out(px32, n * 32);
+    py32 = S.out(py32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_xonly_decode(c, pk32, px32, py32, n, err);
+    return S.done(finish_call(c));
+}
+// `have` bytes of `block` become at least `want`, behind a stream sync: an earlier asynchronous call may still use the block that goes
+static long schnorr_grow(p2e_ctx* c, DeviceArray<unsigned char>& block, size_t& have, size_t want) {
+    if (want <= have) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    have = 0;
+    hipError_t e = block.alloc(want);
+    if (e != hipSuccess) {
+        set_error("scratch allocation of " + std::to_string(want) + " bytes failed: " + hipGetErrorString(e));
+        return P2E_E_NOMEM;
+    }
+    have = want;
+    return 0;
+}
+extern "C" long p2e_schnorr_verify_aggregate(p2e_ctx* c, const uint8_t* msg32, const uint8_t* pk32, const uint8_t* sig64, size_t n,
+                                             const uint8_t* seed32, unsigned window_bits, uint8_t* verdict, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!msg32 || !pk32 || !sig64 || !seed32 || !verdict) {
+        set_error("null pointer (msg32, pk32, sig64, seed32 and verdict are all required; err may be null)");
+        return P2E_E_INVALID;
+    }
+    if (n > MSM_MAX_N / 2) {   // 2 n + 1 > 2^24, without the overflow of 2 n
+        set_error("batch too large for one sum (2 n + 1 terms, at most 2^24)");
+        return P2E_E_INVALID;
+    }
+    const size_t terms = 2 * n + 1;
+    if (msm_bad_args(P2E_CURVE_SECP256K1, terms, window_bits)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    Staged S(c);
+    verdict = S.out(verdict, 1);
+    if (n == 0) {   // the empty batch holds: nothing to sum
+        if (S.rc) return S.done(S.rc);
+        c->have_phases = false;
+        ZERO_COUNTER(c);
+        HIP_TRY(hipMemsetAsync(verdict, 1, 1, c->stream));
+        return S.done(finish_call(c));
+    }
+    msg32 = S.in(msg32, n * 32);
+    pk32 = S.in(pk32, n * 32);
+    sig64 = S.in(sig64, n * 64);
+    seed32 = S.in(seed32, 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    const MsmPlan P = msm_plan(terms, window_bits == P2E_MSM_WINDOW_AUTO ? msm_auto_window(terms) : window_bits);
+    const SchnorrAggLayout L(n);
+    if (long rc = schnorr_grow(c, c->d_schnorr, c->schnorr_bytes, L.total)) return S.done(rc);
+    if (long rc = schnorr_grow(c, c->d_msm, c->msm_bytes, P.total)) return S.done(rc);
+    unsigned char* block = c->d_schnorr.get();
+    MsmArgs a = msm_args(P, c->d_msm.get());
+    a.k32 = block + L.o_k, a.px32 = block + L.o_px, a.py32 = block + L.o_py;
+    a.outx32 = block + L.o_outx, a.outy32 = block + L.o_outy, a.status = block + L.o_status, a.point_err = nullptr;
+    a.counter = reinterpret_cast<unsigned long long*>(block + L.o_rejected);   // (the context's counter holds the flag count)
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    HIP_TRY(hipMemsetAsync(c->d_msm.get(), 0, P.o_off, c->stream));   // meta, count, cursor
+    launch_schnorr_agg_prepare(c, table, L, block, msg32, pk32, sig64, seed32, n, err);
+    launch_msm<Secp256k1>(c, a);
+    launch_schnorr_agg_verdict(c, L, block, verdict);
+    return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)
 

@@ -269,6 +269,48 @@ impl Drop for PointTable<'_> {
     }
 }
 
+/// BIP-340 signatures of `msgs` under `sks` with auxiliary randomness `auxs` (`p2e_schnorr_sign_batch`, host-pointer
+/// context); everything is the standard's byte string.  `Err`: the call failed or a key is out of range.
+pub fn schnorr_sign(ctx: *mut P2eCtx, msgs: &[[u8; 32]], sks: &[[u8; 32]], auxs: &[[u8; 32]]) -> Result<Vec<[u8; 64]>> {
+    let n = msgs.len();
+    ensure!(sks.len() == n && auxs.len() == n);
+    let (mut sig, mut err) = (vec![[0u8; 64]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_schnorr_sign_batch(ctx, msgs.as_ptr().cast(), sks.as_ptr().cast(), auxs.as_ptr().cast(), sig.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    ensure!(rc == 0, "{rc} elements not signed, the first at index {:?}", err.iter().position(|&e| e != 0));
+    Ok(sig)
+}
+
+/// The BIP-340 verdict of every `(msg, x-only pk, sig)` (`p2e_schnorr_verify_batch`, host-pointer context); a malformed key
+/// or signature is simply invalid here.
+pub fn schnorr_verify(ctx: *mut P2eCtx, msgs: &[[u8; 32]], pks: &[[u8; 32]], sigs: &[[u8; 64]]) -> Result<Vec<bool>> {
+    let n = msgs.len();
+    ensure!(pks.len() == n && sigs.len() == n);
+    let (mut err, mut valid) = (vec![0u8; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_schnorr_verify_batch(ctx, msgs.as_ptr().cast(), pks.as_ptr().cast(), sigs.as_ptr().cast(), n, err.as_mut_ptr(), valid.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok(valid.iter().map(|&v| v != 0).collect())
+}
+
+/// One verdict for the whole batch (`p2e_schnorr_verify_aggregate`, host-pointer context).  `seed` must be unpredictable
+/// to whoever produced the signatures: fresh randomness, or a hash of every message, key and signature of the batch.
+/// `false` does not say which element failed: run `schnorr_verify` then.
+pub fn schnorr_verify_aggregate(ctx: *mut P2eCtx, msgs: &[[u8; 32]], pks: &[[u8; 32]], sigs: &[[u8; 64]], seed: &[u8; 32]) -> Result<bool> {
+    let n = msgs.len();
+    ensure!(pks.len() == n && sigs.len() == n);
+    let mut verdict = 0u8;
+    let rc = unsafe {
+        p2e_schnorr_verify_aggregate(ctx, msgs.as_ptr().cast(), pks.as_ptr().cast(), sigs.as_ptr().cast(), n, seed.as_ptr(),
+                                     P2E_MSM_WINDOW_AUTO, &mut verdict, std::ptr::null_mut())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok(verdict == 1)
+}
+
 /// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
 /// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
 /// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).

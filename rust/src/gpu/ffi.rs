@@ -289,6 +289,17 @@ extern "C" {
     pub fn p2e_ecdsa_verify_table_batch(ctx: *mut P2eCtx, table: *const c_void, idx: *const u32, msg32: *const u8, r32: *const u8,
         s32: *const u8, n: usize, err: *mut u8, valid: *mut u8) -> i64;
 
+    // ---- BIP-340 Schnorr signatures on secp256k1: every argument is the standard's BIG-endian byte string (sig64 = r || s);
+    // err[i] is a P2E_WIRE_* code; the aggregate call writes ONE verdict byte (seed32 must be unpredictable to the signers)
+    pub fn p2e_schnorr_public_key_batch(ctx: *mut P2eCtx, sk32: *const u8, pk32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_schnorr_sign_batch(ctx: *mut P2eCtx, msg32: *const u8, sk32: *const u8, aux32: *const u8, sig64: *mut u8, n: usize,
+        err: *mut u8) -> i64;
+    pub fn p2e_schnorr_verify_batch(ctx: *mut P2eCtx, msg32: *const u8, pk32: *const u8, sig64: *const u8, n: usize, err: *mut u8,
+        valid: *mut u8) -> i64;
+    pub fn p2e_xonly_decode_batch(ctx: *mut P2eCtx, pk32: *const u8, px32: *mut u8, py32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_schnorr_verify_aggregate(ctx: *mut P2eCtx, msg32: *const u8, pk32: *const u8, sig64: *const u8, n: usize,
+        seed32: *const u8, window_bits: u32, verdict: *mut u8, err: *mut u8) -> i64;
+
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
         pky32: *mut u8) -> i32;
