@@ -109,10 +109,13 @@ int p2e_last_phase_ms(p2e_ctx *ctx, float *out, int cap);
 /* The reference fills a PartialWitness generator by generator; a batch consumer -- the RCCL exchange that assembles the
  * columns of a sharded batch on every rank, a D2H copy, a prover that starts on finished columns -- need not wait for
  * the whole call either.  Every fused entry point (p2e_ecdsa_verify_witness[_compact]_batch, p2e_glv_mul_witness
- * [_compact]_batch, p2e_curve_mul_witness[_compact]_batch, p2e_p256_verify_witness[_compact]_batch) leaves behind, per launch that writes
- * witness columns, the block of columns [first_col, first_col + num_cols) it completes and a HIP event recorded behind
- * it.  Blocks are disjoint, cover all columns of the program, and are listed in the order the launches were issued
- * (the scalar phase first, then the expansion of every schedule piece as its chain and inversion batch finish).  In
+ * [_compact]_batch, p2e_curve_mul_witness[_compact]_batch, p2e_p256_verify_witness[_compact]_batch) leaves behind the blocks of
+ * columns [first_col, first_col + num_cols) its launches complete, each with a HIP event recorded behind the launch that
+ * completes it.  A launch may complete several blocks, which then share one event: the columns of consecutive curve ops
+ * are not always adjacent (the curve programs place a scalar generator between their last ops), and a block never spans
+ * columns another launch writes.  Blocks are disjoint, cover all columns of the program, and are listed in the order the
+ * launches were issued (the scalar phase first, then the expansion of every schedule piece as its chain and inversion
+ * batch finish; the blocks of one launch by ascending column).  In
  * the compact container block k is rows [narrow_before(first_col), narrow_before(first_col + num_cols)) of the narrow
  * matrix and the same of the wide one (p2e_compact_layout is monotonic in the column index).
  * p2e_segments_describe: returns the number of blocks of the LAST fused call issued on ctx (valid from the moment that

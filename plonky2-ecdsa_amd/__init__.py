@@ -774,7 +774,8 @@ class Context:
     # ---- column blocks of the last fused call, as they become final (include/p2e.h p2e_segments_describe) -------------
     def segments(self):
         """[(first_col, num_cols)] of the last fused call issued on this context, in issue order: the scalar phase's
-        blocks, then one block per expansion launch.  Disjoint; together every column of the program."""
+        blocks, then the blocks of every expansion launch (one per contiguous run of columns; they share the launch's
+        event).  Disjoint; together every column of the program."""
         self._L.p2e_segments_describe.restype = C.c_long
         k = self._L.p2e_segments_describe(self._h, None, C.c_size_t(0))
         buf = (C.c_uint32 * (2 * max(k, 1)))()

@@ -19,6 +19,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
+#include <utility>
+#include <vector>
 
 #include "knobs.hpp"
 #include "pipeline.hpp"
@@ -350,7 +353,9 @@ inline bool build_builtin(const Program& G, const BuiltinParams& P, Plan& pl) {
         // table, the fixed-base result under the final add): with one expansion stream the queue order implied
         // their inversion batches, with two it has to be said
         // (the inversion batches sit on two in-order streams: the most recent one of each implies every earlier one, so
-        // two waits say what q of them used to -- 28 barrier packets less on the expansion streams of a verify call)
+        // two waits say what q of them used to -- 28 barrier packets less on the expansion streams of a verify call;
+        // tests/test_plan_order_cpu.py drops each of them in turn: from the second loop piece on the wait on the OTHER
+        // inversion stream's batch is needed, the rest of the many-waits list is implied -- DESIGN.md section 5)
         if (quad) {
             if (P.few_waits) {
                 for (int sb = 0; sb < 2; sb++)
@@ -619,6 +624,66 @@ inline bool build_curve(const Program& G, const CurveParams& P, Plan& pl) {
     if (P.timing) pl.record(Event{EV_T5, 0}, ST_CALLER);
     pl.compute(FINALIZE, ST_CALLER);
     return pl.error == OK;
+}
+
+// ====================================================================================================
+// column blocks of a call (include/p2e.h p2e_segments_describe): a pure function of the program, its op table and the plan
+// ====================================================================================================
+// event: -1 = the scalar phase (EV_T1), otherwise the expansion launch e whose EV_C1[e] says the block is final
+struct ColumnBlock {
+    uint32_t first_col, num_cols;
+    int event;
+};
+inline uint32_t op_cols(const OpDesc& op) { return op.kind == OP_DBL ? COLS_DBL : op.kind == OP_CADD ? COLS_CADD : COLS_ADD; }
+// the ops an expansion step completes: [lo, hi)
+inline void expand_ops(const Program& G, const Step& s, int loop_stride, int& lo, int& hi) {
+    lo = hi = 0;
+    if (s.kind == EXPAND_OPS) {
+        lo = s.a;
+        hi = s.b;
+    } else if (s.kind == EXPAND_RUNS) {
+        lo = G.msm_loop_begin + loop_stride * s.a;
+        hi = G.msm_loop_begin + loop_stride * s.b;
+    } else if (s.kind == EXPAND_FB_RUN) {
+        lo = G.fb_begin;
+        hi = G.fb_begin + G.fb_windows;
+    }
+}
+// Disjoint blocks that cover every column of the program once.  First the columns no curve op owns (the scalar phase writes
+// them: the complement of the ops' column ranges), then, in issue order, the columns of every expansion launch -- one
+// block per contiguous run of columns, because consecutive ops of a launch are NOT always consecutive generators (the
+// curve programs place a 10-column scalar generator between their last ops); every block of a launch carries its event.
+// loop_stride: ops per iteration of the loop at G.msm_loop_begin (3 in the built-in programs, G.loop_dbls + 1 otherwise).
+inline std::vector<ColumnBlock> column_blocks(const Program& G, const std::vector<OpDesc>& ops, const Plan& pl, int loop_stride) {
+    std::vector<ColumnBlock> out;
+    std::vector<std::pair<uint32_t, uint32_t>> r;
+    auto runs_of = [&](int event) {   // r -> one block per maximal run of touching ranges
+        std::sort(r.begin(), r.end());
+        for (size_t k = 0; k < r.size();) {
+            uint32_t c0 = r[k].first, c1 = r[k].second;
+            for (k++; k < r.size() && r[k].first <= c1; k++) c1 = std::max(c1, r[k].second);
+            out.push_back({c0, c1 - c0, event});
+        }
+    };
+    r.reserve(ops.size());
+    for (const OpDesc& op : ops) r.push_back({op.col, op.col + op_cols(op)});
+    std::sort(r.begin(), r.end());
+    uint32_t at = 0;
+    for (const auto& x : r) {
+        if (x.first > at) out.push_back({at, x.first - at, -1});
+        at = std::max(at, x.second);
+    }
+    if (at < (uint32_t)G.num_cols) out.push_back({at, (uint32_t)G.num_cols - at, -1});
+    for (int k = 0; k < pl.n_steps; k++) {
+        const Step& s = pl.steps[k];
+        if (s.kind != EXPAND_OPS && s.kind != EXPAND_RUNS && s.kind != EXPAND_FB_RUN) continue;
+        int lo, hi;
+        expand_ops(G, s, loop_stride, lo, hi);
+        r.clear();
+        for (int t = lo; t < hi; t++) r.push_back({ops[(size_t)t].col, ops[(size_t)t].col + op_cols(ops[(size_t)t])});
+        runs_of(s.d);
+    }
+    return out;
 }
 
 // ====================================================================================================

@@ -589,13 +589,9 @@ struct p2e_ctx {
     int n_expand = 0, n_seg = 0;
     double expand_cols[MAX_EXPAND] = {};
     int expand_kind[MAX_EXPAND] = {};
-    // column blocks of the last fused call in issue order (p2e_segments_describe): ev < 0 = the scalar phase (ev[1]),
-    // otherwise the block is final when ev_c1[ev] has completed
-    struct SegBlock {
-        u32 col0, ncols;
-        int ev;
-    };
-    std::vector<SegBlock> seg_blocks;
+    // column blocks of the last fused call in issue order (p2e_segments_describe, plan::column_blocks): event < 0 = the
+    // scalar phase (ev[1]), otherwise the block is final when ev_c1[event] has completed
+    std::vector<plan::ColumnBlock> seg_blocks;
     Tuning tune;   // knobs.hpp: filled from the environment once, when the context is created
     DeviceArray<Aff> d_cpts, d_fbtab;
     DeviceArray<Aff> d_fbtab_p256;   // P-256 generator table of the key-derivation / signing calls: built and uploaded on first use
@@ -934,14 +930,14 @@ extern "C" int p2e_last_phase_ms(p2e_ctx* c, float* out, int cap) {
 extern "C" long p2e_segments_describe(p2e_ctx* c, p2e_segment_desc* out, size_t cap) {
     if (!c) return P2E_E_INVALID;
     for (size_t k = 0; out && k < c->seg_blocks.size() && k < cap; k++) {
-        out[k].first_col = c->seg_blocks[k].col0;
-        out[k].num_cols = c->seg_blocks[k].ncols;
+        out[k].first_col = c->seg_blocks[k].first_col;
+        out[k].num_cols = c->seg_blocks[k].num_cols;
     }
     return (long)c->seg_blocks.size();
 }
 static hipEvent_t segment_event(p2e_ctx* c, int k) {
     if (!c || k < 0 || (size_t)k >= c->seg_blocks.size()) return nullptr;
-    const int e = c->seg_blocks[(size_t)k].ev;
+    const int e = c->seg_blocks[(size_t)k].event;
     return e < 0 ? c->ev[1] : c->ev_c1[e];
 }
 extern "C" int p2e_segment_stream_wait(p2e_ctx* c, int k, void* stream) {
@@ -965,33 +961,6 @@ extern "C" int p2e_segment_sync(p2e_ctx* c, int k) {
     return 0;
 }
 #endif   // P2E_HAS(0)
-
-// ---- column blocks of a fused call (p2e_segments_describe) -------------------------------------------
-static inline u32 op_cols(const OpDesc& op) { return op.kind == OP_DBL ? COLS_DBL : op.kind == OP_CADD ? COLS_CADD : COLS_ADD; }
-// the scalar phase writes every column that no curve op owns: the complement of the ops' column ranges
-static void seg_begin_call(p2e_ctx* c, const std::vector<OpDesc>& h_ops, u32 num_cols) {
-    c->seg_blocks.clear();
-    std::vector<std::pair<u32, u32>> r;
-    r.reserve(h_ops.size());
-    for (const OpDesc& op : h_ops) r.push_back({op.col, op.col + op_cols(op)});
-    std::sort(r.begin(), r.end());
-    u32 at = 0;
-    for (const auto& x : r) {
-        if (x.first > at) c->seg_blocks.push_back({at, x.first - at, -1});
-        at = std::max(at, x.second);
-    }
-    if (at < num_cols) c->seg_blocks.push_back({at, num_cols - at, -1});
-}
-// expansion launch e (event pair ev_c0[e] / ev_c1[e]) completes the columns of ops [lo, hi) (consecutive ops of one chain
-// are consecutive generators: one contiguous block)
-static void seg_note_expand(p2e_ctx* c, int e, const std::vector<OpDesc>& h_ops, int lo, int hi) {
-    u32 c0 = 0xFFFFFFFFu, c1 = 0;
-    for (int t = lo; t < hi; t++) {
-        c0 = std::min(c0, h_ops[t].col);
-        c1 = std::max(c1, h_ops[t].col + op_cols(h_ops[t]));
-    }
-    if (hi > lo) c->seg_blocks.push_back({c0, c1 - c0, e});
-}
 
 static int ensure_scratch(p2e_ctx* c, size_t bytes) {
     if (bytes <= c->scratch_bytes) return 0;
@@ -1365,7 +1334,8 @@ static void set_plan_error(plan::Error e, const std::string& what, bool quad) {
 // a family (BuiltinKernels, CurveKernels<CV>); no decision is taken here except the kernel variant of an emitting launch
 // (EmitOf<MODE>: bit 0 = paired stores, bit 1 = compact container), which depends on pointer alignment (wide_ok): the
 // paired launch over the full workgroups, the narrow one over the ragged tail.
-// Keeps the books of p2e_segments_describe / p2e_last_phase_ms from the EXPAND_* steps.
+// Keeps the books of p2e_last_phase_ms from the EXPAND_* steps; the column blocks of p2e_segments_describe are
+// plan::column_blocks of the plan.
 template <class K>
 static long issue_plan(p2e_ctx* c, const plan::Plan& pl, const Program& G, const Buffers& B, const std::vector<OpDesc>& h_ops,
                        bool compact, bool wide_ok, uint8_t* err, uint8_t* valid) {
@@ -1418,11 +1388,10 @@ static long issue_plan(p2e_ctx* c, const plan::Plan& pl, const Program& G, const
         c->n_expand = e + 1;
         c->expand_kind[e] = kind;
         c->expand_cols[e] = cw;
-        seg_note_expand(c, e, h_ops, lo, hi);
     };
     c->n_seg = pl.n_seg;
     c->n_expand = 0;
-    seg_begin_call(c, h_ops, (u32)G.num_cols);
+    c->seg_blocks = column_blocks(G, h_ops, pl, K::loop_stride(G));
     const unsigned lds = pl.expand_lds;
     for (int k = 0; k < pl.n_steps; k++) {
         const Step& s = pl.steps[k];

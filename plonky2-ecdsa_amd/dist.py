@@ -7,8 +7,8 @@ The only exchange the north star names is the *assembly* of the witness columns 
 
 ``ColumnAssembly`` (the one bench.py's strong mode uses): every rank owns ONE tensor ``(world, cols, ld)``; its fill
 writes straight into ``[rank]`` (the C ABI takes any ``ld``, so no packing copy), and the blocks of columns are
-exchanged AS THE KERNELS FINISH THEM (include/p2e.h p2e_segments_describe: one block per launch that completes
-columns, each with its own HIP event): for block ``[c0, c0 + nc)`` a communication stream waits for the block's event
+exchanged AS THE KERNELS FINISH THEM (include/p2e.h p2e_segments_describe: the blocks every launch completes,
+each with the HIP event behind that launch): for block ``[c0, c0 + nc)`` a communication stream waits for the block's event
 and then one grouped send/recv (``batch_isend_irecv`` -> ncclGroupStart / ncclSend x (world-1) / ncclRecv x (world-1) /
 ncclGroupEnd) moves ``[rank, c0:c0+nc, :]`` to every peer's ``[rank, c0:c0+nc, :]``.  That is the direct (one-shot)
 all-gather on the fully connected xGMI mesh -- every link carries exactly one shard, no ring hops -- and it lands in

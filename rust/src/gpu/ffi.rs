@@ -48,7 +48,7 @@ pub struct P2eWireMapEntry {
     pub dst: u32, // wire * degree + row
 }
 
-/// a block of witness columns completed by one launch of a fused call (include/p2e.h p2e_segments_describe)
+/// a block of witness columns completed by one launch of a fused call; a launch may complete several (include/p2e.h p2e_segments_describe)
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct P2eSegmentDesc {

@@ -2,6 +2,7 @@
 // Compiles the very same per-lane bodies the HIP kernels run (pipeline.hpp / prims.hpp) with g++ and
 // drives them with plain loops, phase by phase, so kernel logic can be debugged in the GPU-less dev
 // container.  tests/ compare its output with the oracle; the GPU tests then compare the real kernels.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -80,16 +81,22 @@ struct CurveBodies {
     static void expand_fb_run(const Program& G, const Buffers& B, size_t i, int t_after) { body_expand_fb_run<E, CV>(G, B, i, t_after); }
 };
 
-// Executes the compute steps of a plan one after the other, in list order.  RECORD and WAIT are ignored: list order is
-// a valid execution order because every wait names an event recorded earlier in the list (tests/test_knobs_cpu.py).
+// Executes the compute steps of a plan one after the other: in list order, or (order != nullptr) the steps order[0 ..
+// n_order) in that order.  RECORD and WAIT are ignored: list order is a valid execution order because every wait names
+// an event recorded earlier in the list (tests/test_knobs_cpu.py); which OTHER orders the waits permit is worked out by
+// tests/test_plan_order_cpu.py, which runs them here.
 // How a BINV step is executed is a local matter (arbitrary batching must not change any output):
 //   split > 0          : the batch cut into `split` sub-ranges, whatever the step says (any count, not only 2^k)
 //   0 < chunk < hi - lo: the forward pass re-run inside phase B, `chunk` ops at a time
 //   otherwise          : what the step says (2^split_log2 sub-ranges, or one batch on phase A's prefix products)
 template <class K>
-static void exec_plan(const plan::Plan& pl, const Program& G, const Buffers& B, int chunk, int split) {
+static void exec_plan(const plan::Plan& pl, const Program& G, const Buffers& B, int chunk, int split, const int32_t* order = nullptr,
+                      size_t n_order = 0) {
     const long long n = (long long)B.n;
-    for (int k = 0; k < pl.n_steps; k++) {
+    const size_t count = order ? n_order : (size_t)pl.n_steps;
+    for (size_t at = 0; at < count; at++) {
+        const int k = order ? (int)order[at] : (int)at;
+        if (k < 0 || k >= pl.n_steps) continue;
         const plan::Step& s = pl.steps[k];
         switch (s.kind) {
         case plan::RECORD:
@@ -163,6 +170,20 @@ struct Scratch {
         B.PX = PX.data(); B.PY = PY.data(); B.PZ = PZ.data(); B.PW = PW.data(); B.PREF = PREF.data();
         B.AX = AX.data(); B.AY = AY.data();
         B.dig4 = dig4.data(); B.dig2 = dig2.data(); B.dyn = dyn.data(); B.src = src.data(); B.msrc = msrc.data();
+    }
+    // Every array holds a value no step of the call wrote: a step that runs before the step it reads from then computes
+    // on these and its columns come out wrong.  The values are ones the bodies accept from any input -- field elements
+    // below every modulus (canonical, non-zero; any 256-bit value passes the limb-bound tracker of f29_from_u256), digits
+    // below 16, source ids that name slot 2 -- so that a premature read never leaves an array or aborts.
+    void poison() {
+        U256 v;
+        for (int k = 0; k < 8; k++) v.w[k] = 0x01010101u * (u32)(k + 1);
+        for (auto* a : {&PX, &PY, &PZ, &PW, &PREF, &AX, &AY}) std::fill(a->begin(), a->end(), v);
+        std::fill(dig4.begin(), dig4.end(), (uint8_t)3);
+        std::fill(dig2.begin(), dig2.end(), (uint8_t)3);
+        std::fill(valid8.begin(), valid8.end(), (uint8_t)0xAA);
+        for (auto* a : {&dyn, &src, &msrc}) std::fill(a->begin(), a->end(), (uint16_t)2);
+        std::fill(err32.begin(), err32.end(), 0x40000000u);
     }
     // what k_finalize leaves: the flagged count
     long finalize(uint8_t* err, uint8_t* valid) const {
@@ -722,14 +743,20 @@ long emu_curve_program(int kind, int curve, const uint8_t* blind_x, const uint8_
     if (curve == 1) return run_curve<P256>(H, P, msg, r, s, pkx, pky, cols, n, ld, err, valid);
     return run_curve<Secp256k1>(H, P, msg, r, s, pkx, pky, cols, n, ld, err, valid);
 }
-// ---- launch plans (csrc/launch_plan.hpp) ------------------------------------------------------------------------------
+// a program, the op table its plan binds (the run marks of the plan's record), and the plan
+struct PlanCase {
+    int family = 0, prog = 0, curve = 0, loop_stride = 3;
+    host::CurveProgramHost H;
+    plan::Plan pl;
+    const Program& G() const { return H.sb.prog; }
+};
 // choose + build with the knobs and per-call switches read from `count` (name, value) pairs instead of the environment
-// (P2E_STREAM_LAYOUT and P2E_QUAD_EXPAND_CUS as p2e_ctx_create reads them), for a call of n elements: the plan's text
-// form in out[0..cap), its length returned; -(plan::Error) where build refuses.  family 0: built-in program `prog`;
-// family 1: curve program of kind `prog` on `curve` (blind: the gadget's rand() point).  shape (optional) receives
-// num_ops, fb_begin, fb_windows, msm_loop_begin, msm_loop_iters, ops per loop iteration, plan::MAX_SEG, plan::MAX_EXPAND.
-long emu_plan_dump(int family, int prog, int curve, const uint8_t* blind_x, const uint8_t* blind_y, size_t n, const char* const* names,
-                   const char* const* values, size_t count, int timing, char* out, size_t cap, int32_t* shape) {
+// (P2E_STREAM_LAYOUT and P2E_QUAD_EXPAND_CUS as p2e_ctx_create reads them), for a call of n elements.  family 0: built-in
+// program `prog`; family 1: curve program of kind `prog` on `curve` (blind: the gadget's rand() point).  *error: 0, or
+// -(plan::Error) where build refuses (the case is returned all the same, for its program), or -100 for an unknown program
+// (null).
+static PlanCase* make_case(int family, int prog, int curve, const uint8_t* blind_x, const uint8_t* blind_y, size_t n, const char* const* names,
+                           const char* const* values, size_t count, int timing, long* error) {
     auto env = [&](const char* name) -> const char* {
         for (size_t k = 0; k < count; k++)
             if (!std::strcmp(names[k], name)) return values[k];
@@ -741,31 +768,157 @@ long emu_plan_dump(int family, int prog, int curve, const uint8_t* blind_x, cons
     if (!layout || !*layout) layout = "M1FB2";
     const char* cus = env("P2E_QUAD_EXPAND_CUS");
     const plan::Layout L{std::strchr(layout, '1') != nullptr, cus && atoi(cus) > 0};
-    host::CurveProgramHost H;
-    host::ScheduleBuilder& sb = H.sb;
+    PlanCase* pc = new PlanCase;
+    pc->family = family;
+    pc->prog = prog;
+    pc->curve = curve;
+    host::ScheduleBuilder& sb = pc->H.sb;
+    long err = 0;
     if (family == 0) {
         if (prog == 0)
             sb.verify_secp256k1_message_circuit();
         else
             sb.glv_mul_circuit();
+        const plan::BuiltinParams P = plan::choose_builtin(sb.prog, t, n, L, timing != 0);
+        sb.mark_runs(P.run_iters, P.fb_run);   // (as p2e_ctx_create marks the op table this plan binds)
+        if (!plan::build_builtin(sb.prog, P, pc->pl)) err = -(long)pc->pl.error;
+        pc->loop_stride = 3;
     } else {
         Aff blind;
         memcpy(blind.x.w, blind_x, 32);
         memcpy(blind.y.w, blind_y, 32);
-        if (!host::make_curve_program(H, prog, curve, blind)) return -100;
+        if (!host::make_curve_program(pc->H, prog, curve, blind)) {
+            err = -100;
+        } else {
+            const Program& G = sb.prog;
+            const plan::CurveParams P = plan::choose_curve(G, t, n, G.msm_loop_iters > 0 || prog == CP_FIXED_BASE_MUL, L, timing != 0,
+                                                           read_call_switches(env));
+            if (!plan::build_curve(G, P, pc->pl))
+                err = -(long)pc->pl.error;
+            else if (pc->pl.ops == plan::OPS_RUNS)
+                sb.mark_runs(P.run_iters);
+            pc->loop_stride = G.loop_dbls + 1;
+        }
     }
-    const Program& G = sb.prog;
+    *error = err;
+    if (err == -100) {
+        delete pc;
+        return nullptr;
+    }
+    return pc;
+}
+// ---- launch plans (csrc/launch_plan.hpp) ------------------------------------------------------------------------------
+// choose + build with the knobs and per-call switches read from `count` (name, value) pairs instead of the environment
+// (P2E_STREAM_LAYOUT and P2E_QUAD_EXPAND_CUS as p2e_ctx_create reads them), for a call of n elements: the plan's text
+// form in out[0..cap), its length returned; -(plan::Error) where build refuses.  family 0: built-in program `prog`;
+// family 1: curve program of kind `prog` on `curve` (blind: the gadget's rand() point).  shape (optional) receives
+// num_ops, fb_begin, fb_windows, msm_loop_begin, msm_loop_iters, ops per loop iteration, plan::MAX_SEG, plan::MAX_EXPAND.
+long emu_plan_dump(int family, int prog, int curve, const uint8_t* blind_x, const uint8_t* blind_y, size_t n, const char* const* names,
+                   const char* const* values, size_t count, int timing, char* out, size_t cap, int32_t* shape) {
+    long err = 0;
+    PlanCase* pc = make_case(family, prog, curve, blind_x, blind_y, n, names, values, count, timing, &err);
+    if (!pc) return err;
+    const Program& G = pc->G();
     if (shape) {
-        const int32_t v[8] = {G.num_ops, G.fb_begin, G.fb_windows, G.msm_loop_begin, G.msm_loop_iters, family == 0 ? 3 : G.loop_dbls + 1,
-                              plan::MAX_SEG, plan::MAX_EXPAND};
+        const int32_t v[8] = {G.num_ops, G.fb_begin, G.fb_windows, G.msm_loop_begin, G.msm_loop_iters, pc->loop_stride, plan::MAX_SEG, plan::MAX_EXPAND};
         memcpy(shape, v, sizeof v);
     }
-    static plan::Plan pl;   // (test infrastructure: called from one thread)
-    const bool ok = family == 0 ? plan::build_builtin(G, plan::choose_builtin(G, t, n, L, timing != 0), pl)
-                                : plan::build_curve(G, plan::choose_curve(G, t, n, G.msm_loop_iters > 0 || prog == CP_FIXED_BASE_MUL, L,
-                                                                          timing != 0, read_call_switches(env)), pl);
-    if (!ok) return -(long)pl.error;
-    return (long)plan::dump(pl, out, cap);
+    const long len = err ? err : (long)plan::dump(pc->pl, out, cap);
+    delete pc;
+    return len;
+}
+// ---- one plan case held open (tests/test_plan_order_cpu.py): the program, the op table the plan binds and the plan, as
+// emu_plan_dump makes them; then its text form, its column blocks, its op table, and any number of executions in orders of
+// the caller's choosing.  drop_step >= 0: the plan WITHOUT that step (a mutation for the tests: never issued on a device).
+// *error receives -(plan::Error) where build refuses, -100 for an unknown program, -101 for a step the plan does not have;
+// the handle is then null.
+void* emu_case_open(int family, int prog, int curve, const uint8_t* blind_x, const uint8_t* blind_y, size_t n, const char* const* names,
+                    const char* const* values, size_t count, int timing, int drop_step, long* error) {
+    long err = 0;
+    PlanCase* pc = make_case(family, prog, curve, blind_x, blind_y, n, names, values, count, timing, &err);
+    if (pc && !err && drop_step >= 0) {
+        if (drop_step >= pc->pl.n_steps) {
+            err = -101;
+        } else {
+            for (int k = drop_step; k + 1 < pc->pl.n_steps; k++) pc->pl.steps[k] = pc->pl.steps[k + 1];
+            pc->pl.n_steps--;
+        }
+    }
+    if (error) *error = err;
+    if (err) {
+        delete pc;
+        return nullptr;
+    }
+    return pc;
+}
+void emu_case_close(void* h) { delete (PlanCase*)h; }
+long emu_case_dump(void* h, char* out, size_t cap) { return (long)plan::dump(((PlanCase*)h)->pl, out, cap); }
+// plan::column_blocks of the case: (first_col, num_cols, event) per block; returns the number of blocks
+long emu_case_blocks(void* h, int32_t* out, size_t cap) {
+    const PlanCase& pc = *(PlanCase*)h;
+    const std::vector<plan::ColumnBlock> b = plan::column_blocks(pc.G(), pc.H.sb.ops, pc.pl, pc.loop_stride);
+    for (size_t k = 0; k < b.size() && k < cap; k++) {
+        out[3 * k] = (int32_t)b[k].first_col;
+        out[3 * k + 1] = (int32_t)b[k].num_cols;
+        out[3 * k + 2] = b[k].event;
+    }
+    return (long)b.size();
+}
+// the host op table the plan binds: (kind, flags, ref1, ref2, col, number of columns, cadd_idx) per op; returns num_ops.
+// shape (optional): num_ops, num_slots, slot_p, slot_sp, num_cols, num_chains, chain_begin[4], chain_end[4], msm_loop_begin,
+// msm_loop_iters, ops per loop iteration, fb_begin, fb_windows, cp_table_ops, msm_tab[16]
+long emu_case_ops(void* h, uint32_t* out, size_t cap, int64_t* shape) {
+    const PlanCase& pc = *(PlanCase*)h;
+    const std::vector<OpDesc>& ops = pc.H.sb.ops;
+    for (size_t t = 0; t < ops.size() && t < cap; t++) {
+        const uint32_t v[7] = {ops[t].kind, ops[t].flags, ops[t].ref1, ops[t].ref2, ops[t].col, plan::op_cols(ops[t]), ops[t].cadd_idx};
+        memcpy(out + 7 * t, v, sizeof v);
+    }
+    if (shape) {
+        const Program& G = pc.G();
+        int k = 0;
+        for (int64_t v : {(int64_t)G.num_ops, (int64_t)G.num_slots, (int64_t)G.slot_p, (int64_t)G.slot_sp, (int64_t)G.num_cols, (int64_t)G.num_chains})
+            shape[k++] = v;
+        for (int c = 0; c < 4; c++) shape[k++] = G.chain_begin[c];
+        for (int c = 0; c < 4; c++) shape[k++] = G.chain_end[c];
+        for (int64_t v : {(int64_t)G.msm_loop_begin, (int64_t)G.msm_loop_iters, (int64_t)pc.loop_stride, (int64_t)G.fb_begin, (int64_t)G.fb_windows,
+                          (int64_t)G.cp_table_ops})
+            shape[k++] = v;
+        for (int c = 0; c < 16; c++) shape[k++] = G.msm_tab[c];
+    }
+    return (long)ops.size();
+}
+// The case's plan executed on n elements into the u64 column matrix: steps order[0 .. n_order) in that order (null: list
+// order; inputs as emu_curve_program / emu_curve_msm).  poison != 0: every scratch array and the output start from Scratch::poison / a fixed pattern.  Returns the
+// flagged count.
+long emu_case_exec(void* h, const uint8_t* msg, const uint8_t* r, const uint8_t* s, const uint8_t* pkx, const uint8_t* pky, const uint8_t* qx,
+                   const uint8_t* qy, uint64_t* cols, size_t n, size_t ld, uint8_t* err, uint8_t* valid, const int32_t* order, size_t n_order, int poison) {
+    const PlanCase& pc = *(PlanCase*)h;
+    const host::ScheduleBuilder& sb = pc.H.sb;
+    const Program& G = sb.prog;
+    Buffers B{};
+    Scratch scratch(G, n, B);
+    if (poison) {
+        scratch.poison();
+        for (size_t c = 0; c < (size_t)G.num_cols; c++)
+            for (size_t i = 0; i < n; i++) cols[c * ld + i] = 0xA5A5A5A5A5A5A5A5ull;
+    }
+    B.msg = msg; B.r = r; B.s = s; B.pkx = pkx; B.pky = pky;
+    B.qx = qx; B.qy = qy;   // the MSM program's second point (null for every other program)
+    B.sink = Sink{cols, ld, nullptr, 0, nullptr, 0, nullptr};
+    B.ops = sb.ops.data();
+    if (pc.family == 0) {
+        const host::Consts& C = host::consts();
+        B.cpts = C.cpts; B.fbtab = C.fbtab.data();
+        exec_plan<BuiltinBodies<Emit>>(pc.pl, G, B, 0, 0, order, n_order);
+    } else {
+        B.cpts = sb.gpts.data(); B.fbtab = sb.gfbtab.data();
+        if (pc.curve == 1)
+            exec_plan<CurveBodies<P256, Emit>>(pc.pl, G, B, 0, 0, order, n_order);
+        else
+            exec_plan<CurveBodies<Secp256k1, Emit>>(pc.pl, G, B, 0, 0, order, n_order);
+    }
+    return scratch.finalize(err, valid);
 }
 // The plan a call of `nominal` elements launches under the default knobs (default stream layout), executed on the n
 // elements given: what lets a CPU test run the plan of a 2^16 call on a few signatures.
