@@ -310,6 +310,83 @@ def curve_fixed_base(curve, base, k, nthreads=0, lockstep=0, want_aux=True):
     return cols, aux, err, flags
 
 
+# ---- the walks that also record the constraint-block (ux) and gate-internal matrices (p2e_oracle.h *_full) ----------
+PROG_VERIFY, PROG_GLV_MUL = 0, 6
+_LAYOUTS = {}
+
+
+def program_layout(kind, curve=0):
+    """dict(num_cols, num_aux, num_ux, num_gate, blocks) of a program by a dry walk (p2e_oracle.h
+    p2e_oracle_program_layout): kind PROG_VERIFY / PROG_GLV_MUL (curve 0) or a curve-program kind 1-5.  blocks: one
+    (first ux column, number of ux columns) per generator in registration order, 0 columns where it has no block."""
+    key = (int(kind), int(curve))
+    if key not in _LAYOUTS:
+        f = lib().p2e_oracle_program_layout
+        f.restype = C.c_long
+        na, nu, ng, gens = C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        nc = f(C.c_int(kind), C.c_int(curve), C.byref(na), C.byref(nu), C.byref(ng), None, C.c_size_t(0), C.byref(gens))
+        assert nc > 0, (kind, curve, nc)
+        blocks = np.zeros((gens.value, 2), dtype=np.uint32)
+        f(C.c_int(kind), C.c_int(curve), None, None, None, _p(blocks), C.c_size_t(gens.value), None)
+        _LAYOUTS[key] = dict(num_cols=int(nc), num_aux=int(na.value), num_ux=int(nu.value), num_gate=int(ng.value),
+                             blocks=[(int(a), int(b)) for a, b in blocks])
+    return _LAYOUTS[key]
+
+
+def _full(fn, name, lay, head, n, tail, want_ux, want_gate):
+    cols, aux = _cols(lay["num_cols"], n), _cols(lay["num_aux"], n)
+    ux = _cols(lay["num_ux"], n) if want_ux else None
+    gate = _cols(lay["num_gate"], n) if want_gate else None
+    err, flags = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    fn.restype = C.c_long
+    rc = fn(*head, _p(cols), C.c_size_t(n), C.c_size_t(n), _p(aux), C.c_size_t(n), _p(ux) if want_ux else None, C.c_size_t(n),
+            _p(gate) if want_gate else None, C.c_size_t(n), _p(err), _p(flags), *tail)
+    if rc < 0:
+        raise RuntimeError(f"{name}: {rc}")
+    return cols, aux, ux, gate, err, flags
+
+
+def verify_witness_full(msg, r, s, pkx, pky, nthreads=0, lockstep=0, want_ux=True, want_gate=True):
+    """(cols, aux, ux, gate, err, flags) of verify_secp256k1_message_circuit: ux (249 385, n), gate (10 703, n)"""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in (msg, r, s, pkx, pky)]
+    return _full(lib().p2e_oracle_verify_witness_full, "p2e_oracle_verify_witness_full", program_layout(PROG_VERIFY),
+                 [_p(a) for a in arrs], arrs[0].shape[0], (C.c_int(nthreads), C.c_int(lockstep)), want_ux, want_gate)
+
+
+def glv_mul_witness_full(px, py, k, nthreads=0, want_ux=True, want_gate=True):
+    arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in (px, py, k)]
+    return _full(lib().p2e_oracle_glv_mul_witness_full, "p2e_oracle_glv_mul_witness_full", program_layout(PROG_GLV_MUL),
+                 [_p(a) for a in arrs], arrs[0].shape[0], (C.c_int(nthreads),), want_ux, want_gate)
+
+
+def curve_program_full(kind, curve, blind, args, nthreads=0, lockstep=0, want_ux=True, want_gate=True):
+    """curve_program (kinds 1-3) returning (cols, aux, ux, gate, err, flags)"""
+    bx, by = _b32(blind[0]), _b32(blind[1])
+    if len(args) == 3:
+        px, py, k = [np.ascontiguousarray(a, dtype=np.uint8) for a in args]
+        msg = r = s = k
+    else:
+        msg, r, s, px, py = [np.ascontiguousarray(a, dtype=np.uint8) for a in args]
+    head = [C.c_int(kind), C.c_int(curve)] + [_p(a) for a in (bx, by, msg, r, s, px, py)]
+    return _full(lib().p2e_oracle_curve_program_full, "p2e_oracle_curve_program_full", program_layout(kind, curve), head,
+                 px.shape[0], (C.c_int(nthreads), C.c_int(lockstep)), want_ux, want_gate)
+
+
+def curve_msm_full(curve, px, py, qx, qy, n, m, nthreads=0, lockstep=0, want_ux=True, want_gate=True):
+    arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in (px, py, qx, qy, n, m)]
+    return _full(lib().p2e_oracle_curve_msm_full, "p2e_oracle_curve_msm_full", program_layout(CP_MSM, curve),
+                 [C.c_int(curve)] + [_p(a) for a in arrs], arrs[0].shape[0], (C.c_int(nthreads), C.c_int(lockstep)),
+                 want_ux, want_gate)
+
+
+def curve_fixed_base_full(curve, base, k, nthreads=0, lockstep=0, want_ux=True, want_gate=True):
+    bx, by = _b32(base[0]), _b32(base[1])
+    k = np.ascontiguousarray(k, dtype=np.uint8)
+    return _full(lib().p2e_oracle_curve_fixed_base_full, "p2e_oracle_curve_fixed_base_full",
+                 program_layout(CP_FIXED_BASE_MUL, curve), [C.c_int(curve), _p(bx), _p(by), _p(k)], k.shape[0],
+                 (C.c_int(nthreads), C.c_int(lockstep)), want_ux, want_gate)
+
+
 def rando():
     x = np.zeros(32, dtype=np.uint8)
     y = np.zeros(32, dtype=np.uint8)

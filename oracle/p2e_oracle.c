@@ -647,7 +647,9 @@ static void oracle_init(void) {
 /* ------------------------------------------------------------------------------------------ */
 typedef struct {
     u64 l[NL];
-} nn; /* always padded to 9 limbs; limb *counts* never change a generator output on this path */
+    int n; /* limbs the target really has (constants: convert_base drops zero limbs on top); l is padded with zeros.  The
+            * count never changes a generator output on this path, but it shapes the constraint blocks (ux_* below) */
+} nn;
 typedef struct {
     nn x, y;
 } pt;
@@ -661,6 +663,16 @@ typedef struct {
     u64 *aux;
     size_t ald, acol;
     const struct curve_t *cv; /* NULL = secp256k1 */
+    /* what the U29 gates return inside the constraint blocks (ux_* below), and the rest of rank 1:
+     * the gate-internal values of is_equal and the random accesses.  Separate column matrices, NULL = not recorded;
+     * want_ux / want_gate = 0 skips the work altogether (the walks bench.py times never ask for it). */
+    int want_ux, want_gate;
+    u64 *ux;
+    size_t uld, ucol;
+    u64 *gate;
+    size_t gld, gcol;
+    uint32_t *blocks; /* (first ux column, number of columns) per generator, in registration order; dry walks only */
+    size_t bcap, nblocks;
 } walker;
 static const curve_t *cv_of(const walker *w) { return w->cv ? w->cv : &SECP; }
 
@@ -674,9 +686,23 @@ static u64 w_not(walker *w, u64 b) { /* builder.not(b) = 1 - b */
     aux_emit(w, &v, 1);
     return v;
 }
-static u64 w_is_zero(walker *w, u64 x) { /* builder.is_equal(x, zero) */
+static void gate_emit(walker *w, const u64 *v, int n) {
+    if (w->gate)
+        for (int i = 0; i < n; i++) w->gate[(w->gcol + (size_t)i) * w->gld + w->idx] = v[i];
+    w->gcol += (size_t)n;
+}
+/* builder.is_equal(x, zero) [upstream-from-memory, as oracle/check_circuit.py is_equal_zero]: the bool goes to aux; the
+ * gadget's internal targets not(equal), the EqualityGenerator's inv = x^-1 in Goldilocks (0 for x = 0), diff = x,
+ * diff * inv and diff * (diff * inv) go to the gate-internal vector */
+static u64 w_is_zero(walker *w, u64 x) {
     u64 v = x == 0;
     aux_emit(w, &v, 1);
+    if (w->want_gate) {
+        u64 inv = x ? gl_pow(x, P_GL - 2) : 0;
+        u64 check = gl_mul(x, inv);
+        u64 g[5] = {1 - v, inv, x, check, gl_mul(x, check)};
+        gate_emit(w, g, 5);
+    }
     return v;
 }
 
@@ -685,66 +711,223 @@ static void emit(walker *w, const u64 *v, int n) {
         for (int i = 0; i < n; i++) w->out[(w->col + (size_t)i) * w->ld + w->idx] = v[i];
     w->col += (size_t)n;
 }
-static nn w_add(walker *w, const nn *a, const nn *b, int field) {
+/* ---- constraint blocks: gadgets/biguint.rs:240-323, 360-374 over the U29 gate model of oracle/check_circuit.py ----
+ * [upstream-from-memory: plonky2_ux is not in the container; a gate is modelled by what it constrains]
+ *   add_many_ux(xs) / add_uxs_with_carry(xs, c) -> (sum mod 2^29, sum >> 29)      mul_ux(a, b) -> (a b mod 2^29, a b >> 29)
+ *   sub_ux(x, y, borrow) -> (x - y - borrow + 2^29 borrow_out, borrow_out)        list_le(a, b) -> [a <= b]
+ * Every value such a call returns is recorded, in builder-call order.  Operands are the limb vectors the walk holds, with
+ * the limb COUNT each target has in the reference (a constant has no zero limbs on top, the zero constant has none). */
+#define BIG_MAX 24
+typedef struct {
+    u64 v[BIG_MAX];
+    int n;
+} big;
+static void ux_emit(walker *w, const u64 *v, int n) {
+    if (w->ux)
+        for (int i = 0; i < n; i++) w->ux[(w->ucol + (size_t)i) * w->uld + w->idx] = v[i];
+    w->ucol += (size_t)n;
+}
+static void ux_block_end(walker *w, size_t c0) { /* one record per generator, whether it has a block or not */
+    if (w->blocks && w->nblocks < w->bcap) {
+        w->blocks[2 * w->nblocks] = (uint32_t)c0;
+        w->blocks[2 * w->nblocks + 1] = (uint32_t)(w->ucol - c0);
+    }
+    w->nblocks++;
+}
+static big big_limbs(const u64 *l, int n) {
+    big r;
+    memset(&r, 0, sizeof r);
+    if (n) memcpy(r.v, l, sizeof(u64) * (size_t)n);
+    r.n = n;
+    return r;
+}
+static big big_of(const nn *a) { return big_limbs(a->l, a->n); }
+static big big_modulus(int field) { /* constant_biguint(modulus): all nine limbs, the top one is not zero */
+    u64 l[NL];
+    words_to_limbs(modulus_of(field), 8, l, NL);
+    return big_limbs(l, NL);
+}
+static u64 big_at(const big *a, int i) { return i < a->n ? a->v[i] : 0; }
+static big ux_add_biguint(walker *w, const big *a, const big *b) { /* gadgets/biguint.rs:240-270 */
+    big r;
+    memset(&r, 0, sizeof r);
+    const int n = a->n > b->n ? a->n : b->n;
+    u64 carry = 0;
+    for (int i = 0; i < n; i++) {
+        u64 s = carry + big_at(a, i) + big_at(b, i); /* add_many_ux([carry, a_i, b_i]) */
+        u64 o[2] = {s & MASK29, s >> BITS};
+        ux_emit(w, o, 2);
+        r.v[i] = o[0];
+        carry = o[1];
+    }
+    r.v[n] = carry;
+    r.n = n + 1;
+    return r;
+}
+static big ux_sub_biguint(walker *w, const big *a, const big *b) { /* :272-293; the last borrow is dropped */
+    big r;
+    memset(&r, 0, sizeof r);
+    const int n = a->n > b->n ? a->n : b->n;
+    int64_t borrow = 0;
+    for (int i = 0; i < n; i++) {
+        int64_t d = (int64_t)big_at(a, i) - (int64_t)big_at(b, i) - borrow;
+        borrow = d < 0;
+        u64 o[2] = {(u64)(d + borrow * ((int64_t)1 << BITS)), (u64)borrow};
+        ux_emit(w, o, 2);
+        r.v[i] = o[0];
+    }
+    r.n = n;
+    return r;
+}
+static big ux_mul_biguint(walker *w, const big *a, const big *b) { /* :295-323 */
+    big r;
+    u64 col[BIG_MAX];
+    memset(&r, 0, sizeof r);
+    memset(col, 0, sizeof col);
+    const int total = a->n + b->n;
+    for (int i = 0; i < a->n; i++)
+        for (int j = 0; j < b->n; j++) {
+            u64 p = a->v[i] * b->v[j]; /* mul_ux: both below 2^32 on every walk, the product fits */
+            u64 o[2] = {p & MASK29, p >> BITS};
+            ux_emit(w, o, 2);
+            col[i + j] += o[0];
+            col[i + j + 1] += o[1];
+        }
+    u64 carry = 0;
+    for (int k = 0; k < total; k++) {
+        u64 s = col[k] + carry; /* add_uxs_with_carry(to_add[k], carry) */
+        u64 o[2] = {s & MASK29, s >> BITS};
+        ux_emit(w, o, 2);
+        r.v[k] = o[0];
+        carry = o[1];
+    }
+    r.v[total] = carry;
+    r.n = total + 1;
+    return r;
+}
+static big ux_mul_by_bool(walker *w, const big *a, u64 b) { /* :360-374 inside a block: modulus * overflow */
+    big r = *a;
+    for (int i = 0; i < a->n; i++) r.v[i] = gl_mul(a->v[i], b);
+    ux_emit(w, r.v, a->n);
+    return r;
+}
+/* biguint_to_nonnative's range check gadgets/nonnative.rs:180-190: cmp_biguint(x, modulus) = list_le(x, modulus) */
+static void ux_range_check(walker *w, const big *x, int field) {
+    big m = big_modulus(field);
+    const int n = x->n > m.n ? x->n : m.n;
+    u64 le = 1;
+    for (int i = n - 1; i >= 0; i--)
+        if (big_at(x, i) != big_at(&m, i)) {
+            le = big_at(x, i) < big_at(&m, i);
+            break;
+        }
+    ux_emit(w, &le, 1);
+}
+
+static nn w_add_rc(walker *w, const nn *a, const nn *b, int field, int rc) { /* block: gadgets/nonnative.rs:262-273 */
     nn s;
     u64 ov;
     gen_add(a->l, NL, b->l, NL, modulus_of(field), s.l, &ov, &w->err);
+    s.n = NL;
     emit(w, s.l, NL);
     emit(w, &ov, 1);
+    if (w->want_ux) {
+        const size_t c0 = w->ucol;
+        big A = big_of(a), B = big_of(b), S = big_of(&s), M = big_modulus(field);
+        (void)ux_add_biguint(w, &A, &B);
+        big mo = ux_mul_by_bool(w, &M, ov);
+        (void)ux_add_biguint(w, &S, &mo);
+        if (rc) ux_range_check(w, &S, field);
+        ux_block_end(w, c0);
+    }
     return s;
 }
-static nn w_sub(walker *w, const nn *a, const nn *b, int field) {
+static nn w_add(walker *w, const nn *a, const nn *b, int field) { return w_add_rc(w, a, b, field, 0); }
+static nn w_sub_rc(walker *w, const nn *a, const nn *b, int field, int rc) { /* block: gadgets/nonnative.rs:373-386 */
     nn d;
     u64 ov;
     gen_sub(a->l, NL, b->l, NL, modulus_of(field), d.l, &ov, &w->err);
+    d.n = NL;
     emit(w, d.l, NL);
     emit(w, &ov, 1);
+    if (w->want_ux) {
+        const size_t c0 = w->ucol;
+        big B = big_of(b), D = big_of(&d), M = big_modulus(field);
+        big dpb = ux_add_biguint(w, &D, &B);
+        big mo = ux_mul_by_bool(w, &M, ov);
+        (void)ux_sub_biguint(w, &dpb, &mo);
+        if (rc) ux_range_check(w, &D, field);
+        ux_block_end(w, c0);
+    }
     return d;
 }
-static nn w_mul(walker *w, const nn *x, const nn *y, int field) {
+static nn w_sub(walker *w, const nn *a, const nn *b, int field) { return w_sub_rc(w, a, b, field, 0); }
+static nn w_mul_rc(walker *w, const nn *x, const nn *y, int field, int rc) { /* block: gadgets/nonnative.rs:462-463 */
     nn r;
     u64 q[NL], cs[2 * NL - 1], b[2 * NL - 2];
     gen_mul(x->l, y->l, modulus_of(field), r.l, q, cs, &w->err);
     gen_checksum(cs, b, &w->err);
+    r.n = NL;
     emit(w, r.l, NL);
     emit(w, q, NL);
     emit(w, cs, 2 * NL - 1);
     emit(w, b, 2 * NL - 2);
+    if (w->want_ux) {
+        const size_t c0 = w->ucol;
+        big R = big_of(&r);
+        if (rc) ux_range_check(w, &R, field);
+        ux_block_end(w, c0);
+    }
     return r;
 }
-static nn w_inv(walker *w, const nn *x, int field) {
+static nn w_mul(walker *w, const nn *x, const nn *y, int field) { return w_mul_rc(w, x, y, field, 0); }
+static nn w_inv(walker *w, const nn *x, int field) { /* block: gadgets/nonnative.rs:518-530; never range-checked here */
     nn inv;
     u64 div[NL];
     gen_inv(x->l, NL, modulus_of(field), inv.l, div, &w->err);
+    inv.n = NL;
     emit(w, inv.l, NL);
     emit(w, div, NL);
+    if (w->want_ux) {
+        const size_t c0 = w->ucol;
+        u64 one_l[1] = {1};
+        big X = big_limbs(x->l, NL), I = big_of(&inv), D = big_limbs(div, NL), M = big_modulus(field), one = big_limbs(one_l, 1);
+        (void)ux_mul_biguint(w, &X, &I);
+        big md = ux_mul_biguint(w, &M, &D);
+        (void)ux_add_biguint(w, &md, &one);
+        ux_block_end(w, c0);
+    }
     return inv;
 }
-static nn nn_zero(void) {
+static nn nn_zero(void) { /* the zero constant: no limbs (gadgets/nonnative.rs:496-499) */
     nn z;
     memset(&z, 0, sizeof z);
     return z;
 }
-static nn nn_from(const u64 *l) {
+static nn nn_from(const u64 *l) { /* a constant */
     nn z;
     memcpy(z.l, l, sizeof z.l);
+    z.n = const_nlimbs(l);
     return z;
 }
 /* gadgets/biguint.rs:360-374: one builder.mul per limb of `a`; nl = number of limbs the target really has */
 static nn w_mul_bool(walker *w, const nn *a, int nl, u64 b) {
     nn r;
     for (int i = 0; i < NL; i++) r.l[i] = gl_mul(a->l[i], b);
+    r.n = nl;
     aux_emit(w, r.l, nl);
     return r;
 }
-static nn w_cond_neg(walker *w, const nn *x, int nl, u64 b, int field) { /* gadgets/nonnative.rs:584-596 */
+/* gadgets/nonnative.rs:584-596; rc = the caller's range_check, which only the closing add gets */
+static nn w_cond_neg(walker *w, const nn *x, int nl, u64 b, int field, int rc) {
     u64 not_b = w_not(w, b);
     nn z = nn_zero();
     nn neg = w_sub(w, &z, x, field);
     nn t = w_mul_bool(w, &neg, NL, b), f = w_mul_bool(w, x, nl, not_b);
-    return w_add(w, &t, &f, field);
+    return w_add_rc(w, &t, &f, field, rc);
 }
-static pt w_curve_add(walker *w, const pt *p1, const pt *p2) { /* gadgets/curve.rs:202-223 */
+/* gadgets/curve.rs:202-223; rc = range_check, handed to the two subtractions that give the result */
+static pt w_curve_add_rc(walker *w, const pt *p1, const pt *p2, int rc) {
     const int F = cv_of(w)->fbase;
     nn u = w_sub(w, &p2->y, &p1->y, F);
     nn v = w_sub(w, &p2->x, &p1->x, F);
@@ -753,12 +936,13 @@ static pt w_curve_add(walker *w, const pt *p1, const pt *p2) { /* gadgets/curve.
     nn s2 = w_mul(w, &s, &s, F);
     nn xs = w_add(w, &p2->x, &p1->x, F);
     pt r;
-    r.x = w_sub(w, &s2, &xs, F);
+    r.x = w_sub_rc(w, &s2, &xs, F, rc);
     nn xd = w_sub(w, &p1->x, &r.x, F);
     nn pr = w_mul(w, &s, &xd, F);
-    r.y = w_sub(w, &pr, &p1->y, F);
+    r.y = w_sub_rc(w, &pr, &p1->y, F, rc);
     return r;
 }
+static pt w_curve_add(walker *w, const pt *p1, const pt *p2) { return w_curve_add_rc(w, p1, p2, 0); }
 static pt w_curve_double(walker *w, const pt *p) { /* gadgets/curve.rs:160-185 */
     const curve_t *cv = cv_of(w);
     const int F = cv->fbase;
@@ -774,8 +958,20 @@ static pt w_curve_double(walker *w, const pt *p) { /* gadgets/curve.rs:160-185 *
     nn t;
     u64 ov;
     gen_add_many((const u64(*)[NL])summ, nls, 4, cv->p, t.l, &ov, &w->err);
+    t.n = NL;
     emit(w, t.l, NL);
     emit(w, &ov, 1);
+    if (w->want_ux) { /* block: gadgets/nonnative.rs:330-351 */
+        const size_t c0 = w->ucol;
+        big acc = big_limbs(NULL, 0), S = big_of(&t), M = big_modulus(F), O = big_limbs(&ov, 1);
+        for (int i = 0; i < 4; i++) {
+            big x = big_limbs(summ[i], nls[i]);
+            acc = ux_add_biguint(w, &acc, &x);
+        }
+        big mo = ux_mul_biguint(w, &M, &O);
+        (void)ux_add_biguint(w, &S, &mo);
+        ux_block_end(w, c0);
+    }
     nn l = w_mul(w, &t, &idy, F);
     nn l2 = w_mul(w, &l, &l, F);
     nn xd2 = w_add(w, &p->x, &p->x, F);
@@ -803,6 +999,7 @@ static pt pt_from(u64 l[2][NL]) {
     pt p;
     memcpy(p.x.l, l[0], sizeof p.x.l);
     memcpy(p.y.l, l[1], sizeof p.y.l);
+    p.x.n = const_nlimbs(l[0]), p.y.n = const_nlimbs(l[1]); /* constant_affine_point gadgets/curve.rs:99-105 */
     return p;
 }
 /* digit t of width wbits (2 or 4) of a limb vector: bits of each 29-bit limb LE, limb-major
@@ -824,10 +1021,19 @@ static void aux_bits(walker *w, const u64 *limbs, int nl) {
             aux_emit(w, &b, 1);
         }
 }
-/* random_access_curve_points gadgets/curve_windowed_mul.rs:74-118: selected x limbs, then selected y limbs */
-static void aux_point(walker *w, const pt *p) {
-    aux_emit(w, p->x.l, NL);
-    aux_emit(w, p->y.l, NL);
+/* random_access_curve_points gadgets/curve_windowed_mul.rs:74-118: selected x limbs, then selected y limbs; the selection
+ * has nine limbs per coordinate whatever the table entry had (.get(i).unwrap_or(&zero)).  [upstream-from-memory] one
+ * RandomAccessGate op per limb, whose generator also fills the 4 bit wires of the access index, least significant first */
+static pt aux_point(walker *w, const pt *p, unsigned idx) {
+    pt r = *p;
+    r.x.n = r.y.n = NL;
+    aux_emit(w, r.x.l, NL);
+    aux_emit(w, r.y.l, NL);
+    if (w->want_gate) {
+        u64 bits[4] = {idx & 1, (idx >> 1) & 1, (idx >> 2) & 1, (idx >> 3) & 1};
+        for (int i = 0; i < 2 * NL; i++) gate_emit(w, bits, 4);
+    }
+    return r;
 }
 /* gadgets/curve_fixed_base.rs:18-66; table = the windows of the base (fb_table_init), NULL = the curve's generator */
 static pt w_fixed_base(walker *w, const nn *scalar, u64 (*table)[16][2][NL]) {
@@ -846,13 +1052,13 @@ static pt w_fixed_base(walker *w, const nn *scalar, u64 (*table)[16][2][NL]) {
     for (int i = 0; i < FB_WINDOWS; i++) {
         unsigned d = digit_of(scalar->l, NL, 4, i);
         u64 should_add = w_not(w, w_is_zero(w, d));
-        pt r = pt_from(table[i][d]);
-        aux_point(w, &r);
+        pt entry = pt_from(table[i][d]);
+        pt r = aux_point(w, &entry, d);
         result = w_curve_cond_add(w, &result, nlx, nly, &r, should_add);
         nlx = nly = NL;
     }
     pt nr = pt_from(NEG_RANDO_L);
-    return w_curve_add(w, &result, &nr);
+    return w_curve_add_rc(w, &result, &nr, 1);
 }
 /* gadgets/curve_msm.rs:21-79 on the walker's curve; nl = limbs of the two scalars: 5 (the GLV halves: 145 bits padded to
  * 146, 73 digits) or 9 (curve_msm_circuit on its own: 261 bits padded to 262, 131 digits) */
@@ -890,12 +1096,12 @@ static pt w_msm(walker *w, const pt *p, const pt *q, const u64 *nlimbs, const u6
         result = w_curve_double(w, &result);
         u64 idx = 4 * digit_of(mlimbs, nl, 2, d) + digit_of(nlimbs, nl, 2, d); /* mul_add(four, limb_m, limb_n) */
         aux_emit(w, &idx, 1);
-        aux_point(w, &pre[idx]);
+        pt r = aux_point(w, &pre[idx], (unsigned)idx);
         u64 should_add = w_not(w, w_is_zero(w, idx));
-        result = w_curve_cond_add(w, &result, NL, NL, &pre[idx], should_add);
+        result = w_curve_cond_add(w, &result, NL, NL, &r, should_add);
     }
     pt to_add = pt_from((u64(*)[NL])cv->NEG_RANDO_POW_L[nl == NL]);
-    return w_curve_add(w, &result, &to_add);
+    return w_curve_add_rc(w, &result, &to_add, 1);
 }
 static int nn_eq(const nn *a, const nn *b) { return memcmp(a->l, b->l, sizeof a->l) == 0; }
 static pt w_glv_mul(walker *w, const pt *p, const nn *k, int *ok) { /* gadgets/glv.rs:53-104 */
@@ -903,25 +1109,27 @@ static pt w_glv_mul(walker *w, const pt *p, const nn *k, int *ok) { /* gadgets/g
     nn k1 = nn_zero(), k2 = nn_zero();
     u64 n1, n2;
     gen_glv(k->l, NL, k1.l, k2.l, &n1, &n2, &w->err);
+    k1.n = k2.n = 5;
+    if (w->want_ux) ux_block_end(w, w->ucol); /* the decomposition generator has no constraint block of its own */
     emit(w, k1.l, 5);
     emit(w, k2.l, 5);
     emit(w, &n1, 1);
     emit(w, &n2, 1);
-    nn k1r = w_cond_neg(w, &k1, 5, n1, S);
-    nn k2r = w_cond_neg(w, &k2, 5, n2, S);
+    nn k1r = w_cond_neg(w, &k1, 5, n1, S, 0);
+    nn k2r = w_cond_neg(w, &k2, 5, n2, S, 0);
     nn gs = nn_from(GLV_S_L);
     nn sb = w_mul(w, &gs, &k2r, S);
-    sb = w_add(w, &sb, &k1r, S);
+    sb = w_add_rc(w, &sb, &k1r, S, 1);
     *ok &= nn_eq(&sb, k);
     nn beta = nn_from(BETA_L);
     pt sp;
-    sp.x = w_mul(w, &beta, &p->x, P2E_O_FIELD_BASE);
+    sp.x = w_mul_rc(w, &beta, &p->x, P2E_O_FIELD_BASE, 1);
     sp.y = p->y;
     pt pn, spn;
     pn.x = p->x;
-    pn.y = w_cond_neg(w, &p->y, NL, n1, P2E_O_FIELD_BASE);
+    pn.y = w_cond_neg(w, &p->y, NL, n1, P2E_O_FIELD_BASE, 1);
     spn.x = sp.x;
-    spn.y = w_cond_neg(w, &sp.y, NL, n2, P2E_O_FIELD_BASE);
+    spn.y = w_cond_neg(w, &sp.y, NL, n2, P2E_O_FIELD_BASE, 1);
     return w_msm(w, &pn, &spn, k1.l, k2.l, 5);
 }
 static nn nn_from_bytes(const uint8_t *b) {
@@ -929,6 +1137,7 @@ static nn nn_from_bytes(const uint8_t *b) {
     nn r;
     bytes_to_words(b, wv);
     words_to_limbs(wv, 8, r.l, NL);
+    r.n = NL;
     return r;
 }
 static void walk_verify(walker *w, const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32,
@@ -941,19 +1150,19 @@ static void walk_verify(walker *w, const uint8_t *msg32, const uint8_t *r32, con
     int ok = 1;
     /* curve_assert_valid gadgets/curve.rs:123-135 */
     nn a0 = nn_zero(), b7 = nn_from(SECP.B_L);
-    nn y2 = w_mul(w, &pk.y, &pk.y, F);
+    nn y2 = w_mul_rc(w, &pk.y, &pk.y, F, 1);
     nn x2 = w_mul(w, &pk.x, &pk.x, F);
     nn x3 = w_mul(w, &x2, &pk.x, F);
     nn ax = w_mul(w, &a0, &pk.x, F);
     nn axb = w_add(w, &ax, &b7, F);
-    nn rhs = w_add(w, &x3, &axb, F);
+    nn rhs = w_add_rc(w, &x3, &axb, F, 1);
     ok &= nn_eq(&y2, &rhs);
     nn c = w_inv(w, &s, S);
-    nn u1 = w_mul(w, &msg, &c, S);
-    nn u2 = w_mul(w, &r, &c, S);
+    nn u1 = w_mul_rc(w, &msg, &c, S, 1);
+    nn u2 = w_mul_rc(w, &r, &c, S, 1);
     pt p1 = w_fixed_base(w, &u1, NULL);
     pt p2 = w_glv_mul(w, &pk, &u2, &ok);
-    pt sum = w_curve_add(w, &p1, &p2);
+    pt sum = w_curve_add_rc(w, &p1, &p2, 1);
     ok &= nn_eq(&sum.x, &r);
     *flag = (uint8_t)ok;
 }
@@ -992,19 +1201,19 @@ static pt w_windowed_mul(walker *w, const pt *p, const nn *n, const apt *g) {
     ecc_neg(cv, &neg_g, g);
     pt pre[16], neg = pt_from_apt(&neg_g);
     pre[0] = pt_from_apt(g);
-    for (int i = 1; i < 16; i++) pre[i] = w_curve_add(w, p, &pre[i - 1]);
-    for (int i = 1; i < 16; i++) pre[i] = w_curve_add(w, &neg, &pre[i]);
+    for (int i = 1; i < 16; i++) pre[i] = w_curve_add_rc(w, p, &pre[i - 1], 1);
+    for (int i = 1; i < 16; i++) pre[i] = w_curve_add_rc(w, &neg, &pre[i], 1);
     pt result = pt_from_apt(&cv->start25);
     for (int i = FB_WINDOWS - 1; i >= 0; i--) { /* :157-166, most significant window first */
         for (int k = 0; k < 4; k++) result = w_curve_double(w, &result);
         unsigned d = digit_of(n->l, NL, 4, i);
-        aux_point(w, &pre[d]); /* random_access_curve_points, then is_equal, then not */
+        pt sel = aux_point(w, &pre[d], d); /* random_access_curve_points, then is_equal, then not */
         u64 should_add = w_not(w, w_is_zero(w, d));
-        result = w_curve_cond_add(w, &result, NL, NL, &pre[d], should_add);
+        result = w_curve_cond_add(w, &result, NL, NL, &sel, should_add);
     }
     pt to_subtract = pt_from_apt(&cv->start25_264);
     pt to_add = w_curve_neg(w, &to_subtract);
-    return w_curve_add(w, &result, &to_add);
+    return w_curve_add_rc(w, &result, &to_add, 1);
 }
 /* gadgets/curve.rs:245-285; rando = the rand() blinding point of :253 */
 static pt w_scalar_mul(walker *w, const pt *p, const nn *n, const apt *rando) {
@@ -1012,6 +1221,7 @@ static pt w_scalar_mul(walker *w, const pt *p, const nn *n, const apt *rando) {
     aux_bits(w, n->l, NL); /* split_nonnative_to_bits gadgets/nonnative.rs:566-582 */
     pt randot = pt_from_apt(rando);
     pt result = randot; /* add_virtual_affine_point_target + connect: 9 limbs */
+    result.x.n = result.y.n = NL;
     pt two_i_times_p = *p;
     for (int i = 0; i < NL * BITS; i++) {
         u64 bit = (n->l[i / BITS] >> (i % BITS)) & 1;
@@ -1026,7 +1236,7 @@ static pt w_scalar_mul(walker *w, const pt *p, const nn *n, const apt *rando) {
         two_i_times_p = w_curve_double(w, &two_i_times_p);
     }
     pt neg_r = w_curve_neg(w, &randot);
-    return w_curve_add(w, &result, &neg_r);
+    return w_curve_add_rc(w, &result, &neg_r, 1);
 }
 /* gadgets/ecdsa.rs:55-78 */
 static void walk_verify_p256(walker *w, const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32,
@@ -1039,19 +1249,19 @@ static void walk_verify_p256(walker *w, const uint8_t *msg32, const uint8_t *r32
     pk.y = nn_from_bytes(pky32);
     int ok = 1;
     nn a = nn_from(cv->A_L), b = nn_from(cv->B_L); /* curve_assert_valid gadgets/curve.rs:123-135 */
-    nn y2 = w_mul(w, &pk.y, &pk.y, F);
+    nn y2 = w_mul_rc(w, &pk.y, &pk.y, F, 1);
     nn x2 = w_mul(w, &pk.x, &pk.x, F);
     nn x3 = w_mul(w, &x2, &pk.x, F);
     nn ax = w_mul(w, &a, &pk.x, F);
     nn axb = w_add(w, &ax, &b, F);
-    nn rhs = w_add(w, &x3, &axb, F);
+    nn rhs = w_add_rc(w, &x3, &axb, F, 1);
     ok &= nn_eq(&y2, &rhs);
     nn c = w_inv(w, &s, S);
-    nn u1 = w_mul(w, &msg, &c, S);
-    nn u2 = w_mul(w, &r, &c, S);
+    nn u1 = w_mul_rc(w, &msg, &c, S, 1);
+    nn u2 = w_mul_rc(w, &r, &c, S, 1);
     pt p1 = w_fixed_base(w, &u1, NULL);
     pt p2 = w_windowed_mul(w, &pk, &u2, g);
-    pt sum = w_curve_add(w, &p1, &p2);
+    pt sum = w_curve_add_rc(w, &p1, &p2, 1);
     ok &= nn_eq(&sum.x, &r);
     *flag = (uint8_t)ok;
 }
@@ -1063,6 +1273,22 @@ typedef struct {
     const uint8_t *qx, *qy, *m;             /* kind 4: the second point and its scalar (the first scalar is msg) */
     u64 (*fb_table)[16][2][NL];             /* kind 5: the windows of the caller's base */
 } cp_job;
+/* where a walk records the constraint-block and gate-internal matrices (NULL members: not recorded) */
+typedef struct {
+    u64 *ux;
+    size_t uld;
+    u64 *gate;
+    size_t gld;
+} xsink;
+static const xsink NO_XSINK = {NULL, 0, NULL, 0};
+static walker walker_for(u64 *cols, size_t ld, size_t i, u64 *aux, size_t ald, const xsink *xs) {
+    walker w;
+    memset(&w, 0, sizeof w);
+    w.out = cols, w.ld = ld, w.idx = i, w.aux = aux, w.ald = ald;
+    w.want_ux = xs->ux != NULL, w.want_gate = xs->gate != NULL;
+    w.ux = xs->ux, w.uld = xs->uld, w.gate = xs->gate, w.gld = xs->gld;
+    return w;
+}
 static void walk_curve_program(walker *w, const cp_job *J, size_t i, uint8_t *flag) {
     w->cv = J->cv;
     if (J->kind == P2E_O_CP_VERIFY) {
@@ -1110,6 +1336,7 @@ typedef struct lockstep {
     const cp_job *job; /* non-NULL: a curve program instead of verify_secp256k1_message_circuit */
     uint64_t *cols, *aux;
     size_t ld, ald, first;
+    xsink xs;
     uint8_t *err, *flags;
 } lockstep;
 
@@ -1126,7 +1353,7 @@ static void ls_entry(void) {
     lockstep *L = LS;
     const int k = L->cur;
     const size_t i = L->first + (size_t)k;
-    walker w = {L->cols, L->ld, i, 0, 0, L->aux, L->ald, 0, NULL};
+    walker w = walker_for(L->cols, L->ld, i, L->aux, L->ald, &L->xs);
     uint8_t f = 0;
     if (L->job)
         walk_curve_program(&w, L->job, i, &f);
@@ -1422,9 +1649,31 @@ long p2e_oracle_verify_witness(const uint8_t *msg, const uint8_t *r, const uint8
                                uint8_t *flags, int nthreads) {
     return p2e_oracle_verify_witness_aux(msg, r, s, pkx, pky, cols, n, ld, NULL, 0, err, flags, nthreads);
 }
+static long verify_walks(const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx, const uint8_t *pky,
+                         uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, const xsink *xs, uint8_t *err,
+                         uint8_t *flags, int nthreads);
+static long run_lockstep(const cp_job *job, const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx,
+                         const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, const xsink *xs,
+                         uint8_t *err, uint8_t *flags, int nthreads, int group);
 long p2e_oracle_verify_witness_aux(const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx,
                                    const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint64_t *aux,
                                    size_t ald, uint8_t *err, uint8_t *flags, int nthreads) {
+    return verify_walks(msg, r, s, pkx, pky, cols, n, ld, aux, ald, &NO_XSINK, err, flags, nthreads);
+}
+long p2e_oracle_verify_witness_full(const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx,
+                                    const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
+                                    uint64_t *ux, size_t uld, uint64_t *gate, size_t gld, uint8_t *err, uint8_t *flags,
+                                    int nthreads, int lockstep_group) {
+    const xsink xs = {ux, uld, gate, gld};
+    if (lockstep_group > 0) {
+        oracle_init();
+        return run_lockstep(NULL, msg, r, s, pkx, pky, cols, n, ld, aux, ald, &xs, err, flags, nthreads, lockstep_group);
+    }
+    return verify_walks(msg, r, s, pkx, pky, cols, n, ld, aux, ald, &xs, err, flags, nthreads);
+}
+static long verify_walks(const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx, const uint8_t *pky,
+                         uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, const xsink *xs, uint8_t *err,
+                         uint8_t *flags, int nthreads) {
     oracle_init();
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
@@ -1433,7 +1682,7 @@ long p2e_oracle_verify_witness_aux(const uint8_t *msg, const uint8_t *r, const u
 #endif
 #pragma omp parallel for schedule(dynamic, 1)
     for (size_t i = 0; i < n; i++) {
-        walker w = {cols, ld, i, 0, 0, aux, ald, 0, NULL};
+        walker w = walker_for(cols, ld, i, aux, ald, xs);
         uint8_t f = 0;
         walk_verify(&w, msg + 32 * i, r + 32 * i, s + 32 * i, pkx + 32 * i, pky + 32 * i, &f);
         err[i] = w.err;
@@ -1442,8 +1691,8 @@ long p2e_oracle_verify_witness_aux(const uint8_t *msg, const uint8_t *r, const u
     return count_err(err, n);
 }
 static long run_lockstep(const cp_job *job, const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx,
-                         const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
-                         uint8_t *flags, int nthreads, int group) {
+                         const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, const xsink *xs,
+                         uint8_t *err, uint8_t *flags, int nthreads, int group) {
     if (group < 1) group = 64;
     if (group > LS_MAX) group = LS_MAX;
 #ifdef _OPENMP
@@ -1464,7 +1713,7 @@ static long run_lockstep(const cp_job *job, const uint8_t *msg, const uint8_t *r
             L->stack = stack;
             L->msg = msg, L->r = r, L->s = s, L->pkx = pkx, L->pky = pky;
             L->job = job;
-            L->cols = cols, L->ld = ld, L->aux = aux, L->ald = ald, L->err = err, L->flags = flags;
+            L->cols = cols, L->ld = ld, L->aux = aux, L->ald = ald, L->xs = *xs, L->err = err, L->flags = flags;
 #pragma omp for schedule(dynamic, 1)
             for (size_t g = 0; g < ngroups; g++) {
                 L->first = g * (size_t)group;
@@ -1484,14 +1733,14 @@ long p2e_oracle_verify_witness_lockstep(const uint8_t *msg, const uint8_t *r, co
                                         const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint8_t *err,
                                         uint8_t *flags, int nthreads, int group) {
     oracle_init();
-    return run_lockstep(NULL, msg, r, s, pkx, pky, cols, n, ld, NULL, 0, err, flags, nthreads, group);
+    return run_lockstep(NULL, msg, r, s, pkx, pky, cols, n, ld, NULL, 0, &NO_XSINK, err, flags, nthreads, group);
 }
 /* the lock-step walk recording the built-in-generator values as well (aux[8959][n], as p2e_oracle_verify_witness_aux) */
 long p2e_oracle_verify_witness_aux_lockstep(const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx,
                                             const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
                                             uint8_t *err, uint8_t *flags, int nthreads, int group) {
     oracle_init();
-    return run_lockstep(NULL, msg, r, s, pkx, pky, cols, n, ld, aux, ald, err, flags, nthreads, group);
+    return run_lockstep(NULL, msg, r, s, pkx, pky, cols, n, ld, aux, ald, &NO_XSINK, err, flags, nthreads, group);
 }
 /* kinds 1-3: (bx, by) = the blinding point; kind 4: none (NULL); kind 5: the base, whose windows are built here */
 static int cp_job_init(cp_job *J, int kind, int curve, const uint8_t *bx, const uint8_t *by) {
@@ -1511,41 +1760,66 @@ static int cp_job_init(cp_job *J, int kind, int curve, const uint8_t *bx, const 
     }
     return 0;
 }
-static long cp_job_run(const cp_job *J, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
-                       uint8_t *flags, int nthreads, int lockstep_group);
+static long cp_job_run(const cp_job *J, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, const xsink *xs,
+                       uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group);
 long p2e_oracle_curve_program(int kind, int curve, const uint8_t *blind_x32, const uint8_t *blind_y32,
                               const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *px,
                               const uint8_t *py, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
                               uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group) {
+    return p2e_oracle_curve_program_full(kind, curve, blind_x32, blind_y32, msg, r, s, px, py, cols, n, ld, aux, ald, NULL, 0,
+                                         NULL, 0, err, flags, nthreads, lockstep_group);
+}
+long p2e_oracle_curve_program_full(int kind, int curve, const uint8_t *blind_x32, const uint8_t *blind_y32,
+                                   const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *px,
+                                   const uint8_t *py, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
+                                   uint64_t *ux, size_t uld, uint64_t *gate, size_t gld, uint8_t *err, uint8_t *flags,
+                                   int nthreads, int lockstep_group) {
     cp_job J;
+    const xsink xs = {ux, uld, gate, gld};
     if (kind > P2E_O_CP_VERIFY || cp_job_init(&J, kind, curve, blind_x32, blind_y32)) return -1;
     J.msg = msg, J.r = r, J.s = s, J.px = px, J.py = py;
-    return cp_job_run(&J, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+    return cp_job_run(&J, cols, n, ld, aux, ald, &xs, err, flags, nthreads, lockstep_group);
 }
 long p2e_oracle_curve_msm(int curve, const uint8_t *px, const uint8_t *py, const uint8_t *qx, const uint8_t *qy,
                           const uint8_t *n_scalar, const uint8_t *m_scalar, uint64_t *cols, size_t n, size_t ld,
                           uint64_t *aux, size_t ald, uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group) {
+    return p2e_oracle_curve_msm_full(curve, px, py, qx, qy, n_scalar, m_scalar, cols, n, ld, aux, ald, NULL, 0, NULL, 0, err,
+                                     flags, nthreads, lockstep_group);
+}
+long p2e_oracle_curve_msm_full(int curve, const uint8_t *px, const uint8_t *py, const uint8_t *qx, const uint8_t *qy,
+                               const uint8_t *n_scalar, const uint8_t *m_scalar, uint64_t *cols, size_t n, size_t ld,
+                               uint64_t *aux, size_t ald, uint64_t *ux, size_t uld, uint64_t *gate, size_t gld, uint8_t *err,
+                               uint8_t *flags, int nthreads, int lockstep_group) {
     cp_job J;
+    const xsink xs = {ux, uld, gate, gld};
     if (cp_job_init(&J, P2E_O_CP_MSM, curve, NULL, NULL)) return -1;
     J.msg = n_scalar, J.m = m_scalar, J.px = px, J.py = py, J.qx = qx, J.qy = qy;
-    return cp_job_run(&J, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+    return cp_job_run(&J, cols, n, ld, aux, ald, &xs, err, flags, nthreads, lockstep_group);
 }
 long p2e_oracle_curve_fixed_base(int curve, const uint8_t *base_x32, const uint8_t *base_y32, const uint8_t *k,
                                  uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
                                  uint8_t *flags, int nthreads, int lockstep_group) {
+    return p2e_oracle_curve_fixed_base_full(curve, base_x32, base_y32, k, cols, n, ld, aux, ald, NULL, 0, NULL, 0, err, flags,
+                                            nthreads, lockstep_group);
+}
+long p2e_oracle_curve_fixed_base_full(int curve, const uint8_t *base_x32, const uint8_t *base_y32, const uint8_t *k,
+                                      uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint64_t *ux, size_t uld,
+                                      uint64_t *gate, size_t gld, uint8_t *err, uint8_t *flags, int nthreads,
+                                      int lockstep_group) {
     cp_job J;
+    const xsink xs = {ux, uld, gate, gld};
     int rc0 = cp_job_init(&J, P2E_O_CP_FIXED_BASE_MUL, curve, base_x32, base_y32);
     if (rc0) return rc0;
     J.msg = k;
-    long rc = cp_job_run(&J, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+    long rc = cp_job_run(&J, cols, n, ld, aux, ald, &xs, err, flags, nthreads, lockstep_group);
     free(J.fb_table);
     return rc;
 }
-static long cp_job_run(const cp_job *Jp, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err,
-                       uint8_t *flags, int nthreads, int lockstep_group) {
+static long cp_job_run(const cp_job *Jp, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, const xsink *xs,
+                       uint8_t *err, uint8_t *flags, int nthreads, int lockstep_group) {
     const cp_job J = *Jp;
     if (lockstep_group > 0) {
-        long rc = run_lockstep(&J, NULL, NULL, NULL, NULL, NULL, cols, n, ld, aux, ald, err, flags, nthreads, lockstep_group);
+        long rc = run_lockstep(&J, NULL, NULL, NULL, NULL, NULL, cols, n, ld, aux, ald, xs, err, flags, nthreads, lockstep_group);
         return rc == -1 ? -2 : rc;
     }
 #ifdef _OPENMP
@@ -1555,7 +1829,7 @@ static long cp_job_run(const cp_job *Jp, uint64_t *cols, size_t n, size_t ld, ui
 #endif
 #pragma omp parallel for schedule(dynamic, 1)
     for (size_t i = 0; i < n; i++) {
-        walker w = {cols, ld, i, 0, 0, aux, ald, 0, NULL};
+        walker w = walker_for(cols, ld, i, aux, ald, xs);
         uint8_t f = 0;
         walk_curve_program(&w, &J, i, &f);
         err[i] = w.err;
@@ -1564,8 +1838,37 @@ static long cp_job_run(const cp_job *Jp, uint64_t *cols, size_t n, size_t ld, ui
     return count_err(err, n);
 }
 long p2e_oracle_curve_program_num_cols(int kind, int curve, long *num_aux) {
+    return p2e_oracle_program_layout(kind, curve, num_aux, NULL, NULL, NULL, 0, NULL);
+}
+long p2e_oracle_program_layout(int kind, int curve, long *num_aux, long *num_ux, long *num_gate, uint32_t *blocks, size_t cap,
+                               long *num_generators) {
     cp_job J;
     uint8_t zero[32] = {0}, gx[32], gy[32];
+    if (kind == P2E_O_PROG_VERIFY || kind == P2E_O_PROG_GLV_MUL) { /* the two built-in walks, secp256k1 only */
+        if (curve != 0) return -1;
+        oracle_init();
+        uint8_t ones[32];
+        memset(ones, 0x11, sizeof ones);
+        words_to_bytes(SECP.g.x, gx);
+        words_to_bytes(SECP.g.y, gy);
+        walker w = walker_for(NULL, 0, 0, NULL, 0, &NO_XSINK);
+        w.want_ux = w.want_gate = 1, w.blocks = blocks, w.bcap = cap;
+        uint8_t f = 0;
+        if (kind == P2E_O_PROG_VERIFY)
+            walk_verify(&w, ones, ones, ones, gx, gy, &f);
+        else {
+            pt p;
+            p.x = nn_from_bytes(gx), p.y = nn_from_bytes(gy);
+            nn k = nn_from_bytes(ones);
+            int ok = 1;
+            (void)w_glv_mul(&w, &p, &k, &ok);
+        }
+        if (num_aux) *num_aux = (long)w.acol;
+        if (num_ux) *num_ux = (long)w.ucol;
+        if (num_gate) *num_gate = (long)w.gcol;
+        if (num_generators) *num_generators = (long)w.nblocks;
+        return (long)w.col;
+    }
     if (kind < 1 || kind > 5) return -1;
     /* (kind 5 is set up as kind 1 here: no windows of a base are built, the walk below uses the generator's) */
     if (cp_job_init(&J, kind == P2E_O_CP_FIXED_BASE_MUL ? P2E_O_CP_WINDOWED_MUL : kind, curve, zero, zero)) return -1;
@@ -1580,10 +1883,14 @@ long p2e_oracle_curve_program_num_cols(int kind, int curve, long *num_aux) {
     memset(ones, 0x11, sizeof ones);
     J.msg = J.r = J.s = J.m = ones, J.px = gx, J.py = gy;
     J.qx = J.px, J.qy = J.py; /* (p = q meets an inverse of zero; the column count does not depend on it) */
-    walker w = {NULL, 0, 0, 0, 0, NULL, 0, 0, NULL};
+    walker w = walker_for(NULL, 0, 0, NULL, 0, &NO_XSINK);
+    w.want_ux = w.want_gate = 1, w.blocks = blocks, w.bcap = cap;
     uint8_t f = 0;
     walk_curve_program(&w, &J, 0, &f);
     if (num_aux) *num_aux = (long)w.acol;
+    if (num_ux) *num_ux = (long)w.ucol;
+    if (num_gate) *num_gate = (long)w.gcol;
+    if (num_generators) *num_generators = (long)w.nblocks;
     return (long)w.col;
 }
 long p2e_oracle_glv_mul_witness(const uint8_t *px, const uint8_t *py, const uint8_t *k, uint64_t *cols,
@@ -1593,6 +1900,12 @@ long p2e_oracle_glv_mul_witness(const uint8_t *px, const uint8_t *py, const uint
 long p2e_oracle_glv_mul_witness_aux(const uint8_t *px, const uint8_t *py, const uint8_t *k, uint64_t *cols,
                                     size_t n, size_t ld, uint64_t *aux, size_t ald, uint8_t *err, uint8_t *flags,
                                     int nthreads) {
+    return p2e_oracle_glv_mul_witness_full(px, py, k, cols, n, ld, aux, ald, NULL, 0, NULL, 0, err, flags, nthreads);
+}
+long p2e_oracle_glv_mul_witness_full(const uint8_t *px, const uint8_t *py, const uint8_t *k, uint64_t *cols, size_t n,
+                                     size_t ld, uint64_t *aux, size_t ald, uint64_t *ux, size_t uld, uint64_t *gate,
+                                     size_t gld, uint8_t *err, uint8_t *flags, int nthreads) {
+    const xsink xs = {ux, uld, gate, gld};
     oracle_init();
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
@@ -1601,7 +1914,7 @@ long p2e_oracle_glv_mul_witness_aux(const uint8_t *px, const uint8_t *py, const 
 #endif
 #pragma omp parallel for schedule(dynamic, 1)
     for (size_t i = 0; i < n; i++) {
-        walker w = {cols, ld, i, 0, 0, aux, ald, 0, NULL};
+        walker w = walker_for(cols, ld, i, aux, ald, &xs);
         pt p;
         p.x = nn_from_bytes(px + 32 * i);
         p.y = nn_from_bytes(py + 32 * i);

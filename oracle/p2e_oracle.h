@@ -7,6 +7,8 @@
  * vectors for these generators and cannot be built offline: SURVEY.md 8c).  Pinned instead by
  * (i) agreement with the independent Python big-int restatement oracle/p2e_ref.py on the committed
  * fixtures tests/golden/ (ii) the reference's constraint equations, re-evaluated in tests/.
+ * The constraint-block (ux) and gate-internal matrices of the *_full walks are pinned by agreement with the Python
+ * constraint replay oracle/check_circuit.py; their U29 gate model stays "upstream-from-memory" (see below).
  *
  * Data layout (same as include/p2e.h): Goldilocks-canonical u64 columns, column-major over the
  * batch: element (col, i) lives at base[col * ld + i], ld >= n.  256-bit inputs are packed 32-byte
@@ -141,6 +143,55 @@ long p2e_oracle_curve_fixed_base(int curve, const uint8_t *base_x32, const uint8
                                  uint8_t *flags, int nthreads, int lockstep_group);
 /* column counts of a curve program (kinds 1-5) by a dry walk: returns num_cols, *num_aux = built-in-generator values */
 long p2e_oracle_curve_program_num_cols(int kind, int curve, long *num_aux);
+
+/* ---- constraint-block (ux) and gate-internal (gate) matrices: SURVEY.md 8(f) rank 2 and the rest of rank 1 -----------
+ * The *_full walks are the walks above, additionally recording
+ *   ux[num_ux][n]     every value a plonky2_ux U29 gate returns inside the constraint block of a non-native gadget
+ *                     (gadgets/nonnative.rs:262-273 add, :330-351 add_many, :373-386 sub, :462-463 mul's range check,
+ *                     :518-530 inv; gadgets/biguint.rs:240-323 add / sub / mul_biguint, :360-374 modulus * overflow),
+ *                     generator by generator in builder-call order.  The gates are modelled by what they constrain --
+ *                     add_many_ux / add_uxs_with_carry -> (sum mod 2^29, sum >> 29), mul_ux -> (a b mod 2^29, a b >> 29),
+ *                     sub_ux -> (x - y - borrow + 2^29 borrow_out, borrow_out), list_le -> [a <= b] -- the model stated at
+ *                     the top of oracle/check_circuit.py [upstream-from-memory: plonky2_ux is not in the container]
+ *   gate[num_gate][n] per window, in call order: is_equal(index, zero)'s five internal targets (not(equal), the
+ *                     EqualityGenerator's inverse of the index in Goldilocks or 0, diff, diff * inv, diff * (diff * inv))
+ *                     and, per selected limb of a random_access_curve_points (9 x, 9 y), the 4 bit wires of the access
+ *                     index, least significant first [upstream-from-memory]
+ * both u64, column-major with their own strides (uld, gld >= n); NULL = not recorded.  Operands are the limb vectors the
+ * walk holds, with the limb count the target has in the reference (constants drop zero limbs on top); nothing is read
+ * back through a wiring table.  Values of an element with err != 0 are unspecified.
+ * PARITY STATUS of these two matrices: pinned by agreement with the Python constraint replay oracle/check_circuit.py
+ * (Circuit.ux / .gate / .ux_ops) on random, named adversarial and golden elements of every program (tests/); the U29
+ * gate model itself stays "upstream-from-memory". */
+long p2e_oracle_verify_witness_full(const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *pkx,
+                                    const uint8_t *pky, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
+                                    uint64_t *ux, size_t uld, uint64_t *gate, size_t gld, uint8_t *err, uint8_t *flags,
+                                    int nthreads, int lockstep_group);
+long p2e_oracle_glv_mul_witness_full(const uint8_t *px, const uint8_t *py, const uint8_t *k, uint64_t *cols, size_t n,
+                                     size_t ld, uint64_t *aux, size_t ald, uint64_t *ux, size_t uld, uint64_t *gate,
+                                     size_t gld, uint8_t *err, uint8_t *flags, int nthreads);
+long p2e_oracle_curve_program_full(int kind, int curve, const uint8_t *blind_x32, const uint8_t *blind_y32,
+                                   const uint8_t *msg, const uint8_t *r, const uint8_t *s, const uint8_t *px,
+                                   const uint8_t *py, uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald,
+                                   uint64_t *ux, size_t uld, uint64_t *gate, size_t gld, uint8_t *err, uint8_t *flags,
+                                   int nthreads, int lockstep_group);
+long p2e_oracle_curve_msm_full(int curve, const uint8_t *px, const uint8_t *py, const uint8_t *qx, const uint8_t *qy,
+                               const uint8_t *n_scalar, const uint8_t *m_scalar, uint64_t *cols, size_t n, size_t ld,
+                               uint64_t *aux, size_t ald, uint64_t *ux, size_t uld, uint64_t *gate, size_t gld, uint8_t *err,
+                               uint8_t *flags, int nthreads, int lockstep_group);
+long p2e_oracle_curve_fixed_base_full(int curve, const uint8_t *base_x32, const uint8_t *base_y32, const uint8_t *k,
+                                      uint64_t *cols, size_t n, size_t ld, uint64_t *aux, size_t ald, uint64_t *ux, size_t uld,
+                                      uint64_t *gate, size_t gld, uint8_t *err, uint8_t *flags, int nthreads,
+                                      int lockstep_group);
+/* Layout of a program by a dry walk: kind 1-5 a curve program on `curve`, P2E_O_PROG_VERIFY / P2E_O_PROG_GLV_MUL the two
+ * built-in walks (curve 0).  Returns num_cols; *num_aux, *num_ux, *num_gate the other three column counts;
+ * *num_generators the generator count.  blocks (cap pairs, may be NULL): (first ux column, number of ux columns) of every
+ * generator in registration order -- 0 columns for a generator without a block (the GLV decomposition, a multiplication
+ * that is not range-checked). */
+#define P2E_O_PROG_VERIFY 0
+#define P2E_O_PROG_GLV_MUL 6
+long p2e_oracle_program_layout(int kind, int curve, long *num_aux, long *num_ux, long *num_gate, uint32_t *blocks, size_t cap,
+                               long *num_generators);
 
 /* constants computed at init (for tests): rando = keccak256(0u64 LE) as LE scalar * G */
 void p2e_oracle_rando(uint8_t x32[32], uint8_t y32[32]);

@@ -208,6 +208,17 @@ long emuc_curve_ux(int kind, int curve, const uint8_t* bx, const uint8_t* by, co
     in[INPUT_QY] = qy;
     return run_ux<true>(sb, cv.data(), in, narrow, ldn, cols, ld, aux, ald, ux, ux_u32, uld, n, err);
 }
+// what p2e_curve_program_ux_describe reports (a program object needs a device): (first, count) per generator, the generator count
+long emuc_curve_ux_describe(int kind, int curve, const uint8_t* bx, const uint8_t* by, uint32_t* first, uint32_t* count, size_t cap) {
+    host::CurveProgramHost H;
+    if (!curve_program(H, kind, curve, bx, by)) return -1;
+    const host::ScheduleBuilder& sb = H.sb;
+    for (size_t k = 0; first && count && k < sb.ux_first.size() && k < cap; k++) {
+        first[k] = sb.ux_first[k];
+        count[k] = sb.ux_count[k];
+    }
+    return (long)sb.ux_first.size();
+}
 // ---- layout: the generator table with its wiring, the compact layout, and the library's own consecutive-rows check ------------
 long emuc_gens(int program, int32_t* kinds, uint32_t* first, uint32_t* ncols, int32_t* nops, uint32_t* src, uint8_t* nl, size_t cap) {
     host::ScheduleBuilder sb;

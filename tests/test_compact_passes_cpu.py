@@ -84,6 +84,22 @@ class CompactEmu:
     def layout(self, program):
         return self._layout(lambda *a: self.L.emuc_layout(program, *a))
 
+    def curve_ux_describe(self, kind, curve, blind):
+        """[(first ux column, number of columns)] per generator: what p2e_curve_program_ux_describe reports"""
+        self.L.emuc_curve_ux_describe.restype = C.c_long
+        b = [_p(blind[0]), _p(blind[1])]
+        ng = self.L.emuc_curve_ux_describe(kind, curve, *b, None, None, _sz(0))
+        first, count = np.zeros(ng, np.uint32), np.zeros(ng, np.uint32)
+        assert self.L.emuc_curve_ux_describe(kind, curve, *b, _p(first), _p(count), _sz(ng)) == ng
+        return [(int(a), int(c)) for a, c in zip(first, count)]
+
+    def curve_ux_count(self, kind, curve, blind):
+        return self.L.emuc_curve_ux(kind, curve, _p(blind[0]), _p(blind[1]), *([None] * 7), None, _sz(0), None, _sz(0), None, _sz(0),
+                                    None, 0, _sz(0), _sz(0), None)
+
+    def curve_gate_count(self, kind, curve, blind):
+        return self.L.emuc_curve_gate(kind, curve, _p(blind[0]), _p(blind[1]), None, _sz(0), None, _sz(0), _sz(0))
+
     # -- bodies ------------------------------------------------------------------------------------------
     def ux(self, program, inputs, narrow, aux32, u32):
         if program == 0:

@@ -13,6 +13,7 @@ import pytest
 
 import adversarial_inputs as A
 import oracle_c
+import ux_oracle as UX
 from test_adversarial_cpu import KIND, oracle
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,28 @@ def reference(program, curve_id):
         to_dev = lambda m: torch.from_numpy(np.ascontiguousarray(m[:, err == 0]).view(np.int64)).cuda()
         _cache[key] = dict(rows=rows, marks=marks, arrs=arrs, dev=[torch.from_numpy(a).cuda() for a in arrs], cols=to_dev(cols),
                            aux=to_dev(aux), err=err, verifier=program == "verify", verdict=verdict, clean=clean, bad=int((err != 0).sum()))
+    return _cache[key]
+
+
+def pass_reference(program, curve_id):
+    """the oracle's constraint-block and gate-internal matrices of one whole batch, uploaded (ux as int32: 1.2 GB for the
+    built-in verifier), with the clean-row mask and the per-generator block list; one program's at a time"""
+    import torch
+    key = ("passes", program, curve_id)
+    if key not in _cache:
+        for k in [k for k in _cache if isinstance(k, tuple) and k[0] == "passes"]:
+            del _cache[k]
+        ref = reference(program, curve_id)
+        if curve_id == 0 and program in ("verify", "glv_mul"):
+            exp, lay = UX.builtin(0 if program == "verify" else 1, ref["arrs"]), UX.layout("builtin", 0 if program == "verify" else 1)
+        else:
+            exp = UX.curve_program(KIND[program], curve_id, A.blind(curve_id), ref["arrs"])
+            lay = UX.layout("curve", KIND[program], curve_id)
+        assert np.array_equal(exp["err"], ref["err"])
+        del exp["cols"], exp["aux"]
+        dexp = UX.to_device(torch, exp)
+        dexp["blocks"] = lay["blocks"]
+        _cache[key] = dexp
     return _cache[key]
 
 
@@ -143,15 +166,42 @@ def test_curve_programs_on_adversarial_rows(program, curve_id, plan, monkeypatch
         verr, vvalid, vbad = prog.verify_batch(*dev)
         torch.cuda.synchronize()
         same_flags("verdict-only call", ref, verr, vvalid, vbad)
+    if plan == "default":
+        # the constraint-block and gate-internal passes on the whole batch, both containers, against the oracle's walk
+        n, ok = len(ref["rows"]), ref["err"] == 0
+        dexp = pass_reference(program, curve_id)
+        blocks = dexp["blocks"]
+        assert [tuple(b) for b in prog.ux_describe()] == blocks
+        aux32, _e, _b = prog.aux_witness_compact_batch(dev, nar, n=n)
+        for u32 in (True, False):
+            ux, uerr, _ub = prog.ux_witness_compact_batch(dev, nar, aux32, n=n, u32=u32)
+            torch.cuda.synchronize()
+            assert not uerr.cpu().numpy()[ok].any()
+            UX.assert_same_device(torch, f"compact container, ux as {'u32' if u32 else 'u64'}", ux, dexp["ux32"], dexp, blocks)
+            del ux
+        if prog.num_gate_cols:
+            UX.assert_same_device(torch, "u32 aux, gate", prog.gate_internal_compact_batch(aux32, n=n), dexp["gate"], dexp)
+        del nar, wid
+        cols, _e, _v, _b = fill(*dev)
+        aux, _ae, _ab = prog.aux_witness_batch(dev, cols)
+        for u32 in (True, False):
+            ux, uerr, _ub = prog.ux_witness_batch(dev, cols, aux, n=n, ld=p2e._ld(cols), u32=u32)
+            torch.cuda.synchronize()
+            assert not uerr.cpu().numpy()[ok].any()
+            UX.assert_same_device(torch, f"u64 matrices, ux as {'u32' if u32 else 'u64'}", ux, dexp["ux32"], dexp, blocks)
+            del ux
+        if prog.num_gate_cols:
+            UX.assert_same_device(torch, "u64 aux, gate", prog.gate_internal_batch(aux, n=n), dexp["gate"], dexp)
     prog.close()
     ctx.close()
 
 
 @pytest.mark.parametrize("program", ["verify", "glv_mul"])
 def test_gate_internal_and_constraint_block_passes_on_named_rows(program):
-    """the gate-internal and constraint-block passes on the GPU's own matrices of the adversarial batch, against the replay
-    model on four named clean rows: k1 = 0, both GLV signs set, a u1 with a zero window in every group of sixteen (a sparse k
-    for glv_mul), pk.x = p - small"""
+    """the gate-internal and constraint-block passes on the GPU's own matrices of the adversarial batch: against the replay
+    model on four named clean rows (k1 = 0, both GLV signs set, a u1 with a zero window in every group of sixteen or a sparse k
+    for glv_mul, pk.x = p - small), and against the C oracle's walk on every column of every row the fill does not flag --
+    u32 and u64 outputs, from the u64 matrices and from the compact container, padded strides with guard values"""
     import torch
     import check_circuit as CC
     import plonky2_ecdsa_amd as p2e
@@ -173,4 +223,35 @@ def test_gate_internal_and_constraint_block_passes_on_named_rows(program):
         check = CC.check_verify if pid == 0 else CC.check_glv_mul
         c = check(col(cols, np.uint64), *ref["rows"][i].args, aux=col(aux, np.uint64), ux=col(ux, np.uint32))
         assert np.array_equal(col(gate, np.uint64), np.array(c.gate, dtype=np.uint64)), ref["rows"][i].kind
+    # every element and column against the oracle
+    n, ok = len(ref["rows"]), ref["err"] == 0
+    dexp = pass_reference(program, 0)
+    blocks = dexp["blocks"]
+    UX.assert_same_device(torch, "u64 matrices, ux as u32", ux, dexp["ux32"], dexp, blocks)
+    UX.assert_same_device(torch, "u64 aux, gate", gate, dexp["gate"], dexp)
+    del ux, gate
+    k, kg = p2e.ux_num_cols(pid), dexp["gate"].shape[0]
+    big64 = torch.full((k, n + 5), -1, dtype=torch.int64, device="cuda")          # odd stride: one element per store
+    ux64, e64, _b = ctx.ux_witness_batch(pid, dev, cols, aux, ux=big64[:, :n])
+    torch.cuda.synchronize()
+    assert not e64.cpu().numpy()[ok].any() and bool((big64[:, n:] == -1).all())
+    UX.assert_same_device(torch, "u64 matrices, ux as u64", ux64, dexp["ux32"], dexp, blocks)
+    del ux64, big64, cols, aux
+    nar, _wid, _e, _v, _b = (ctx.ecdsa_verify_witness_compact_batch if pid == 0 else ctx.glv_mul_witness_compact_batch)(*dev)
+    aux32, _e, _b = ctx.aux_witness_compact_batch(pid, dev[4] if pid == 0 else dev[1], nar, n=n, ld_narrow=nar.stride(0))
+    bigg = torch.full((kg, n + 10), -1, dtype=torch.int64, device="cuda")
+    cgate = ctx.gate_internal_compact_batch(pid, aux32, gate=bigg[:, :n])
+    torch.cuda.synchronize()
+    assert bool((bigg[:, n:] == -1).all())
+    UX.assert_same_device(torch, "u32 aux, gate", cgate, dexp["gate"], dexp)
+    big32 = torch.full((k, n + 6), -1, dtype=torch.int32, device="cuda")           # even stride: paired stores + tail
+    c32, ce32, _b = ctx.ux_witness_compact_batch(pid, dev, nar, aux32, ux=big32[:, :n])
+    torch.cuda.synchronize()
+    assert not ce32.cpu().numpy()[ok].any() and bool((big32[:, n:] == -1).all())
+    UX.assert_same_device(torch, "compact container, ux as u32", c32, dexp["ux32"], dexp, blocks)
+    del c32, big32
+    c64, ce64, _b = ctx.ux_witness_compact_batch(pid, dev, nar, aux32, u32=False)
+    torch.cuda.synchronize()
+    assert not ce64.cpu().numpy()[ok].any()
+    UX.assert_same_device(torch, "compact container, ux as u64", c64, dexp["ux32"], dexp, blocks)
     ctx.close()

@@ -8,6 +8,7 @@ import pytest
 import check_circuit as CC
 import oracle_c
 import p2e_ref as R
+import ux_oracle as UX
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +75,13 @@ def test_builtin_compact_chain_equals_the_u64_chain(program, gpu):
     ux64, e64, b64 = ctx.ux_witness_batch(program, inputs, cols, aux, u32=False)
     assert abad == b32 == b64 == 0
     k = p2e.ux_num_cols(program)
+    # the oracle's own walk of the same inputs: every element and column of both passes, from both containers
+    exp = UX.builtin(program, list(sigs) if program == 0 else [sigs[3], sigs[4], oracle_c.pack256(ks)])
+    dexp, blocks = UX.to_device(torch, exp), UX.layout("builtin", program)["blocks"]
+    assert not exp["err"].any() and [tuple(b) for b in p2e.ux_describe(program)] == blocks
+    UX.assert_same_device(torch, "u64 matrices, ux as u32", ux32, dexp["ux32"], dexp, blocks)
+    UX.assert_same_device(torch, "u64 matrices, ux as u64", ux64, dexp["ux32"], dexp, blocks)
+    UX.assert_same_device(torch, "u64 aux, gate", gate, dexp["gate"], dexp)
     for pad in (3, 6):                              # the narrow source on an odd and on an even padded stride
         nar, _big = _padded(torch, narrow, pad)
         assert p2e._ld(nar) == n + pad
@@ -90,6 +98,9 @@ def test_builtin_compact_chain_equals_the_u64_chain(program, gpu):
         assert torch.equal(c32, ux32) and torch.equal(c64, ux64)
         assert torch.equal(ce32, e32) and torch.equal(ce64, e64)
         assert bool((big32[:, n:] == -1).all()) and bool((big64[:, n:] == -1).all())      # padding untouched
+        UX.assert_same_device(torch, f"compact container (pad {pad}), ux as u32", c32, dexp["ux32"], dexp, blocks)
+        UX.assert_same_device(torch, f"compact container (pad {pad}), ux as u64", c64, dexp["ux32"], dexp, blocks)
+        UX.assert_same_device(torch, f"u32 aux (pad {pad}), gate", cgate, dexp["gate"], dexp)
     # independent check: columns rebuilt from the compact container alone, through the constraint replay
     h_cols = p2e.compact_expand(program, _u32(narrow), _u64(wide))
     h_aux, h_ux, h_gate = _u32(aux32), _u32(c32), _u64(cgate)
@@ -114,6 +125,9 @@ def test_builtin_compact_chain_equals_the_u64_chain(program, gpu):
     assert hb == hab == hub == 0 and not np.asarray(he).any()
     assert np.array_equal(np.asarray(ha), h_aux[:, :3]) and np.array_equal(np.asarray(hg), h_gate[:, :3])
     assert np.array_equal(np.asarray(hu), h_ux[:, :3]) and np.array_equal(np.asarray(hu64), h_ux[:, :3].astype(np.uint64))
+    UX.assert_same_numpy("host-pointer context, ux as u32", np.asarray(hu).astype(np.uint64), exp["ux"][:, :3], blocks=blocks)
+    UX.assert_same_numpy("host-pointer context, ux as u64", np.asarray(hu64).view(np.uint64), exp["ux"][:, :3], blocks=blocks)
+    UX.assert_same_numpy("host-pointer context, gate", np.asarray(hg).view(np.uint64), exp["gate"][:, :3])
     hctx.close()
 
 
@@ -302,14 +316,27 @@ def test_curve_program_compact_chain_equals_the_u64_chain(kind, curve, gpu):
     assert abad == cabad == b32 == cb32 == 0
     assert torch.equal(aux32.to(torch.int64), aux)
     assert torch.equal(c32, ux32) and torch.equal(ce32, e32)
+    # the oracle's own walk of the same inputs: every element and column, u32 and u64 outputs, both containers
+    exp = UX.curve_program(kind, curve, point, host)
+    dexp, blocks = UX.to_device(torch, exp), UX.layout("curve", kind, curve)["blocks"]
+    assert not exp["err"].any() and [tuple(b) for b in prog.ux_describe()] == blocks
+    assert (prog.num_ux_cols, prog.num_gate_cols) == (exp["ux"].shape[0], exp["gate"].shape[0])
+    UX.assert_same_device(torch, "u64 matrices, ux as u32", ux32, dexp["ux32"], dexp, blocks)
+    UX.assert_same_device(torch, "compact container, ux as u32", c32, dexp["ux32"], dexp, blocks)
     gate = None
     if prog.num_gate_cols:
         gate = prog.gate_internal_compact_batch(aux32, n=n)
-        assert torch.equal(gate, prog.gate_internal_batch(aux, n=n))
-    if (kind, curve) == (p2e.CP_WINDOWED_MUL, p2e.CURVE_P256):     # the u64 output, for one program only
-        ux64, _e, _b = ux_u64(inputs, cols, aux, n=n, ld=ld, u32=False)
-        c64, _e, _b = prog.ux_witness_compact_batch(inputs, nar, aux32, n=n, u32=False)
-        assert torch.equal(c64, ux64) and torch.equal(c64, c32.to(torch.int64))
+        wgate = prog.gate_internal_batch(aux, n=n)
+        assert torch.equal(gate, wgate)
+        UX.assert_same_device(torch, "u32 aux, gate", gate, dexp["gate"], dexp)
+        UX.assert_same_device(torch, "u64 aux, gate", wgate, dexp["gate"], dexp)
+        del wgate
+    ux64, _e, _b = ux_u64(inputs, cols, aux, n=n, ld=ld, u32=False)
+    UX.assert_same_device(torch, "u64 matrices, ux as u64", ux64, dexp["ux32"], dexp, blocks)
+    c64, _e, _b = prog.ux_witness_compact_batch(inputs, nar, aux32, n=n, u32=False)
+    UX.assert_same_device(torch, "compact container, ux as u64", c64, dexp["ux32"], dexp, blocks)
+    assert torch.equal(c64, ux64) and torch.equal(c64, c32.to(torch.int64))
+    del ux64, c64
     torch.cuda.synchronize()
     h_cols = prog.compact_expand(_u32(narrow), _u64(wide))
     h_aux, h_ux = _u32(aux32), _u32(c32)
@@ -341,6 +368,12 @@ def test_msm_constraint_block_pass_in_both_forms(curve, gpu):
     assert bool((big[:, n:] == -1).all())
     assert torch.equal(c32, ux32) and torch.equal(ux64, ux32.to(torch.int64))
     assert sum(nc for _first, nc in prog.ux_describe()) == k
+    exp = UX.curve_program(p2e.CP_MSM, curve, None, host)
+    dexp, blocks = UX.to_device(torch, exp), UX.layout("curve", p2e.CP_MSM, curve)["blocks"]
+    assert not exp["err"].any() and [tuple(b) for b in prog.ux_describe()] == blocks
+    UX.assert_same_device(torch, "p2e_curve_msm_ux_witness_batch, u32", ux32, dexp["ux32"], dexp, blocks)
+    UX.assert_same_device(torch, "p2e_curve_msm_ux_witness_batch, u64", ux64, dexp["ux32"], dexp, blocks)
+    UX.assert_same_device(torch, "compact container, u32", c32, dexp["ux32"], dexp, blocks)
     h_cols, h_aux, h_ux = _u64(cols), _u64(aux), _u32(ux32)
     for i in REPLAYED:
         c = _curve_replay(p2e, p2e.CP_MSM, curve, point, host, i, h_cols[:, i], h_aux[:, i])

@@ -8,6 +8,7 @@ import pytest
 import oracle_c
 import p2e_ref as R
 import parity_checks as pc
+import ux_oracle as UX
 
 pytestmark = pytest.mark.gpu
 
@@ -644,9 +645,10 @@ def test_failed_calls_clean_up_and_the_context_survives():
 @pytest.mark.parametrize("program", [0, 1])
 def test_constraint_block_columns_match_the_replay_model(program):
     """SURVEY 8(f) rank 2 (p2e_ux_witness_batch): the U29-gate values of every constraint block, derived on the GPU from
-    its own witness + aux matrices through the wiring table, against the constraint replay's model (which recomputes
-    them from the reference's gadgets while checking every constraint on the same GPU witness).  n = 300: a full
-    workgroup of paired stores + a ragged tail; u32 and u64 outputs, padded strides."""
+    its own witness + aux matrices through the wiring table, against the C oracle's walk on every element and column,
+    and on four elements against the constraint replay's model (which recomputes them from the reference's gadgets while
+    checking every constraint on the same GPU witness).  n = 300: a full workgroup of paired stores + a ragged tail; u32
+    and u64 outputs, padded strides."""
     import torch
     import check_circuit as CC
     import plonky2_ecdsa_amd as p2e
@@ -673,6 +675,12 @@ def test_constraint_block_columns_match_the_replay_model(program):
     assert bool((big32[:, n:] == -1).all())                                 # padding untouched
     h32 = ux32.cpu().numpy().view(np.uint32)
     assert np.array_equal(h32.astype(np.uint64), ux64.cpu().numpy().view(np.uint64)) and int(h32.max()) < 1 << 29
+    # every element and column against the oracle's own walk of the same inputs
+    exp = UX.builtin(program, list(sigs) if program == 0 else [sigs[3], sigs[4], oracle_c.pack256(ks)])
+    dexp, blocks = UX.to_device(torch, exp), UX.layout("builtin", program)["blocks"]
+    assert not exp["err"].any() and [tuple(b) for b in p2e.ux_describe(program)] == blocks
+    UX.assert_same_device(torch, "ux as u32", ux32, dexp["ux32"], dexp, blocks)
+    UX.assert_same_device(torch, "ux as u64", ux64, dexp["ux32"], dexp, blocks)
     host, haux = cols.cpu().numpy().view(np.uint64), aux.cpu().numpy().view(np.uint64)
     for i in (0, 255, 256, 299):
         if program == 0:
@@ -694,12 +702,14 @@ def test_constraint_block_columns_match_the_replay_model(program):
     ha, _, _ = hctx.aux_witness_batch(program, sl[4], hc)
     hu, he, hb = hctx.ux_witness_batch(program, hin, hc, ha)
     assert hb == 0 and np.array_equal(np.asarray(hu), h32[:, :3])
+    UX.assert_same_numpy("host-pointer context, ux", np.asarray(hu).astype(np.uint64), exp["ux"][:, :3], blocks=blocks)
 
 
 @pytest.mark.parametrize("program", [0, 1])
 def test_gate_internal_values_on_the_gpu(program):
     """p2e_gate_internal_batch (equality-gadget internals, RandomAccessGate index bits per window) from the GPU's own aux
-    matrix against the constraint replay's model; n = 300, padded stride, staged host-pointer path."""
+    matrix against the C oracle's walk on every element and column and, on four elements, the constraint replay's model;
+    n = 300, padded stride, staged host-pointer path."""
     import torch
     import check_circuit as CC
     import plonky2_ecdsa_amd as p2e
@@ -721,6 +731,10 @@ def test_gate_internal_values_on_the_gpu(program):
     torch.cuda.synchronize()
     assert bad == 0 and abad == 0 and bool((big[:, n:] == -1).all())
     host, hg = cols.cpu().numpy().view(np.uint64), gate.cpu().numpy().view(np.uint64)
+    exp = UX.builtin(program, list(sigs) if program == 0 else [sigs[3], sigs[4], oracle_c.pack256(ks)])
+    dexp = UX.to_device(torch, exp)
+    assert not exp["err"].any() and exp["gate"].shape[0] == k
+    UX.assert_same_device(torch, "gate-internal values", gate, dexp["gate"], dexp)
     for i in (0, 255, 256, 299):
         if program == 0:
             c = CC.check_verify(host[:, i], *CC.unpack_inputs(sigs, i))
@@ -729,7 +743,9 @@ def test_gate_internal_values_on_the_gpu(program):
             c = CC.check_glv_mul(host[:, i], px, py, ks[i])
         assert np.array_equal(hg[:, i], np.array(c.gate, dtype=np.uint64))
     hctx = p2e.Context(device=0, host_pointers=True)
-    assert np.array_equal(np.asarray(hctx.gate_internal_batch(program, aux.cpu().numpy().view(np.uint64)[:, :7].copy())), hg[:, :7])
+    hgate = np.asarray(hctx.gate_internal_batch(program, aux.cpu().numpy().view(np.uint64)[:, :7].copy()))
+    assert np.array_equal(hgate, hg[:, :7])
+    UX.assert_same_numpy("host-pointer context, gate", hgate.view(np.uint64), exp["gate"][:, :7])
 
 
 def test_assemble_wires_against_numpy():
