@@ -878,6 +878,54 @@ long p2e_schnorr_verify_aggregate(p2e_ctx *ctx, const uint8_t *msg32, const uint
                                   const uint8_t *seed32, unsigned window_bits, uint8_t *verdict,
                                   uint8_t *err /* nullable */);
 
+/* ---- BIP-32 key derivation and Bitcoin key hashes on secp256k1: where a wallet's keys come from (one extended key, its
+ * children) and where they go (HASH160, the payload of P2PKH / P2WPKH and the source of the BIP-32 fingerprint).  Defined by
+ * BIP-32, FIPS 180-4 (SHA-512, SHA-256), RFC 2104 (HMAC) and the RIPEMD-160 paper.  The curve is secp256k1 alone (no curve
+ * argument, as p2e_eth_address_batch).  An extended key on the device becomes n child keys, then n key hashes, and with the
+ * signing, encoding and verifying calls signatures and witnesses, without visiting the host.
+ *   bytes    keys and coordinates (sk32, pkx32, pky32 and the par_* ones) are this library's 32-byte LITTLE-endian values, so
+ *            they chain into every other call.  Chain codes (cc32) are 32 bytes in the standard's order.  index is a uint32_t
+ *            array; index >= 2^31 is a hardened child.  Hashes are in the order their standard defines.  Every array is 4-byte
+ *            aligned but seed (any alignment, stride seed_len) and the data of p2e_hash160_batch (any alignment); both are read
+ *            as p2e_hash_batch reads its data: aligned 4-byte words, and only words that hold a byte of the lane's element.
+ *   parents  n_parents is 1 or n, anything else is P2E_E_INVALID.  With 1 every element derives from parent 0: the scan of
+ *            one extended key (for n == 1 the two meanings coincide).
+ *   err[i]   a P2E_WIRE_* CODE: the first failing check in the order given below.  A flagged element writes zeros to ALL its
+ *            outputs, the chain code included.  BIP-32's "proceed with the next index" is NOT done: the code tells the caller.
+ *   p2e_bip32_master_batch   I = HMAC-SHA512(key = "Bitcoin seed", seed_i), seed_i = seed[seed_len i, seed_len (i + 1)), one
+ *            seed_len of 16 .. 64 per call (anything else: P2E_E_INVALID).  I_L = 0 or I_L >= n: P2E_WIRE_SCALAR_RANGE.
+ *            sk = I_L, cc = I_R.
+ *   p2e_bip32_ckd_priv_batch   CKDpriv.  In order: parent k = 0 or k >= n: P2E_WIRE_SCALAR_RANGE (not reduced: BIP-32 keys
+ *            lie in [1, n - 1]).  data = 00 || ser256(k) || ser32(index) for a hardened index, serP(k G) || ser32(index)
+ *            otherwise (the lane walks the generator's table: the cost of p2e_ecdsa_public_key_batch).
+ *            I = HMAC-SHA512(key = cc, data); I_L >= n: P2E_WIRE_SCALAR_RANGE; k_child = I_L + k mod n, 0:
+ *            P2E_WIRE_INFINITY.  I_L = 0 is valid and computed.  cc_child = I_R.
+ *   p2e_bip32_ckd_pub_batch   CKDpub.  In order: index >= 2^31: P2E_WIRE_BAD_INDEX (a public parent has no hardened child);
+ *            parent (0, 0): P2E_WIRE_INFINITY; a parent coordinate >= p: P2E_WIRE_COORD_RANGE; parent off the curve:
+ *            P2E_WIRE_NOT_ON_CURVE; I = HMAC-SHA512(key = cc, serP(K) || ser32(index)), I_L >= n: P2E_WIRE_SCALAR_RANGE;
+ *            K_child = I_L G + K, the neutral element: P2E_WIRE_INFINITY.  I_L = 0 (child = parent) and I_L G = K (a
+ *            doubling) are computed, not flagged.  The point and chain code are those CKDpriv's child has.
+ *   p2e_key_hash160_batch   out20[20 i ..] = RIPEMD-160(SHA-256(the SEC1 string of (pkx, pky))), form P2E_SEC1_COMPRESSED
+ *            (33 bytes) or P2E_SEC1_UNCOMPRESSED (65 bytes); an unknown form is P2E_E_INVALID.  Mirrors p2e_eth_address_batch:
+ *            nothing is checked, and where err_in[i] != 0 (nullable) twenty zero bytes are written.  Returns 0.  Bytes 0 .. 3
+ *            of the compressed form's output are the BIP-32 fingerprint of the key.
+ *   p2e_hash160_batch   out20[20 i ..] = RIPEMD-160(SHA-256(message i)); messages, offsets, alignment, empty and reversed
+ *            elements, the return value and host staging are exactly p2e_hash_batch's.
+ * Each call is one kernel on the context's caller stream, one lane per element: no internal streams, no LDS, no scratch;
+ * the secrets (parent key, I_L, child key) live in registers only.  Return value: the number of flagged elements
+ * (p2e_hash160_batch: of reversed elements); P2E_E_INVALID on a null pointer (other than err_in) or a bad argument; n == 0
+ * returns 0.  Host pointers, async mode, the current device and failed calls behave as for the signing calls. */
+long p2e_bip32_master_batch(p2e_ctx *ctx, const uint8_t *seed, size_t seed_len, uint8_t *sk32, uint8_t *cc32, size_t n,
+                            uint8_t *err);
+long p2e_bip32_ckd_priv_batch(p2e_ctx *ctx, const uint8_t *par_sk32, const uint8_t *par_cc32, size_t n_parents,
+                              const uint32_t *index, uint8_t *sk32, uint8_t *cc32, size_t n, uint8_t *err);
+long p2e_bip32_ckd_pub_batch(p2e_ctx *ctx, const uint8_t *par_pkx32, const uint8_t *par_pky32, const uint8_t *par_cc32,
+                             size_t n_parents, const uint32_t *index, uint8_t *pkx32, uint8_t *pky32, uint8_t *cc32,
+                             size_t n, uint8_t *err);
+long p2e_key_hash160_batch(p2e_ctx *ctx, unsigned form, const uint8_t *pkx32, const uint8_t *pky32,
+                           const uint8_t *err_in /* nullable */, uint8_t *out20, size_t n);
+long p2e_hash160_batch(p2e_ctx *ctx, const uint8_t *data, const uint64_t *offsets, uint8_t *out20, size_t n);
+
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */
 int p2e_synth_signatures(uint64_t seed, size_t first, size_t n, uint8_t *msg32, uint8_t *r32, uint8_t *s32,

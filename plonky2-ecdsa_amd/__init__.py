@@ -101,6 +101,7 @@ EXPORTS = (
     "p2e_point_table_read_window", "p2e_point_table_mul_batch", "p2e_point_table_lincomb_batch", "p2e_ecdsa_verify_table_batch",
     "p2e_schnorr_public_key_batch", "p2e_schnorr_sign_batch", "p2e_schnorr_verify_batch", "p2e_xonly_decode_batch",
     "p2e_schnorr_verify_aggregate",
+    "p2e_bip32_master_batch", "p2e_bip32_ckd_priv_batch", "p2e_bip32_ckd_pub_batch", "p2e_key_hash160_batch", "p2e_hash160_batch",
 )
 
 
@@ -1289,6 +1290,71 @@ class Context:
         bad = self._check(self._L.p2e_schnorr_verify_aggregate(self._h, _ptr(msg), _ptr(pk), _ptr(sig), C.c_size_t(n), _ptr(seed),
                                                                 C.c_uint(window_bits), _ptr(verdict), _ptr(err)))
         return verdict, err, bad
+
+    # ---- BIP-32 key derivation and HASH160 on secp256k1 (include/p2e.h p2e_bip32_master_batch and the four calls after it) ------
+    @staticmethod
+    def _parents(par, n):
+        """n_parents of a parent array: its rows, which must be 1 (one parent for the whole batch) or n"""
+        m = par.shape[0]
+        if m != 1 and m != n:
+            raise P2EError("parents must have 1 row or one row per index")
+        return m
+
+    def bip32_master_batch(self, seed, sk=None, cc=None, err=None):
+        """BIP-32 master keys of (n, seed_len) seeds, 16 <= seed_len <= 64: (sk (n, 32) little-endian, cc (n, 32) chain codes in
+        the standard's byte order, err, flagged count).  I_L = 0 or I_L >= n: zeros and WIRE_SCALAR_RANGE."""
+        n, seed_len = self._shape(seed)
+        sk = sk if sk is not None else self._packed(n)
+        cc = cc if cc is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_bip32_master_batch(self._h, _ptr(seed), C.c_size_t(seed_len), _ptr(sk), _ptr(cc), C.c_size_t(n),
+                                                         _ptr(err)))
+        return sk, cc, err, bad
+
+    def bip32_ckd_priv_batch(self, par_sk, par_cc, index, sk=None, cc=None, err=None):
+        """CKDpriv: child index[i] (uint32; >= 2^31 hardened) of parent i, or of parent 0 where par_sk and par_cc have one row:
+        (sk, cc, err, flagged count).  WIRE_SCALAR_RANGE for a parent key or an I_L out of range, WIRE_INFINITY for a zero
+        child; a flagged element is all zeros, the chain code included."""
+        n = self._shape(index)[0]
+        m = self._parents(par_sk, n)
+        sk = sk if sk is not None else self._packed(n)
+        cc = cc if cc is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_bip32_ckd_priv_batch(self._h, _ptr(par_sk), _ptr(par_cc), C.c_size_t(m), _ptr(index), _ptr(sk),
+                                                           _ptr(cc), C.c_size_t(n), _ptr(err)))
+        return sk, cc, err, bad
+
+    def bip32_ckd_pub_batch(self, par_pkx, par_pky, par_cc, index, pkx=None, pky=None, cc=None, err=None):
+        """CKDpub: the public key and chain code of the non-hardened child index[i] of parent i, or of parent 0 where the parent
+        arrays have one row (the scan of one extended public key): (pkx, pky, cc, err, flagged count).  err, in order:
+        WIRE_BAD_INDEX for a hardened index, WIRE_INFINITY / WIRE_COORD_RANGE / WIRE_NOT_ON_CURVE for the parent,
+        WIRE_SCALAR_RANGE for I_L >= n, WIRE_INFINITY for a neutral child."""
+        n = self._shape(index)[0]
+        m = self._parents(par_pkx, n)
+        pkx = pkx if pkx is not None else self._packed(n)
+        pky = pky if pky is not None else self._packed(n)
+        cc = cc if cc is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_bip32_ckd_pub_batch(self._h, _ptr(par_pkx), _ptr(par_pky), _ptr(par_cc), C.c_size_t(m), _ptr(index),
+                                                          _ptr(pkx), _ptr(pky), _ptr(cc), C.c_size_t(n), _ptr(err)))
+        return pkx, pky, cc, err, bad
+
+    def key_hash160_batch(self, pkx, pky, form=SEC1_COMPRESSED, err=None, out=None):
+        """HASH160 = RIPEMD-160(SHA-256(.)) of the SEC1 form (SEC1_COMPRESSED or SEC1_UNCOMPRESSED) of (n, 32) little-endian
+        secp256k1 coordinates: (out (n, 20), 0).  err (n,) uint8, optional: where err[i] != 0 the hash is twenty zero bytes.
+        The first four bytes of the compressed form's hash are the key's BIP-32 fingerprint."""
+        n = self._shape(pkx)[0]
+        out = out if out is not None else self._bytes(n, 20)
+        rc = self._check(self._L.p2e_key_hash160_batch(self._h, C.c_uint(form), _ptr(pkx), _ptr(pky), _ptr(err), _ptr(out), C.c_size_t(n)))
+        return out, rc
+
+    def hash160_batch(self, data, offsets, out=None):
+        """HASH160 of message i = data[offsets[i]:offsets[i + 1]], laid out as for hash_batch: (out (n, 20), count of elements
+        with offsets[i + 1] < offsets[i], which are hashed as the empty message)."""
+        n = self._shape(offsets)[0] - 1
+        out = out if out is not None else self._bytes(n, 20)
+        bad = self._check(self._L.p2e_hash160_batch(self._h, _ptr(data), _ptr(offsets), _ptr(out), C.c_size_t(n)))
+        return out, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

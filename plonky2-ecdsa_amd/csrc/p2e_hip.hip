@@ -29,6 +29,7 @@
 #include "point_arith.hpp"
 #include "point_table.hpp"
 #include "schnorr.hpp"
+#include "hd.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
 
@@ -39,7 +40,7 @@ using host::COMPACT_WIDE;
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
 // streaming passes, descriptions;  1 = the fused pipeline of the two built-in programs (run_program);  2 / 3 = the
 // curve-program pipeline instantiated for secp256k1 / P-256 (run_curve_program<CV>).  Undefined = everything in one
-// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 kernels (schnorr.hpp) ride in part 3.  Small static helpers (error text, staging, scratch) are compiled into every part.
+// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 kernels (schnorr.hpp) ride in part 3; the BIP-32 and HASH160 kernels (hd.hpp) ride in part 1 with the other hashes.  Small static helpers (error text, staging, scratch) are compiled into every part.
 #ifndef P2E_PART
 #define P2E_PART (-1)
 #endif
@@ -3399,6 +3400,183 @@ extern "C" long p2e_schnorr_verify_aggregate(p2e_ctx* c, const uint8_t* msg32, c
     launch_schnorr_agg_prepare(c, table, L, block, msg32, pk32, sig64, seed32, n, err);
     launch_msm<Secp256k1>(c, a);
     launch_schnorr_agg_verdict(c, L, block, verdict);
+    return S.done(finish_call(c));
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// BIP-32 key derivation and HASH160 on secp256k1 (hd.hpp): master keys, CKDpriv, CKDpub, key hashes, message hashes
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 1 beside the other hashing kernels, called from part 0
+void launch_bip32_master(p2e_ctx* c, const uint8_t* seed, size_t seed_len, uint8_t* sk, uint8_t* cc, size_t n, uint8_t* err);
+void launch_bip32_ckd_priv(p2e_ctx* c, const Aff* table, const uint8_t* par_sk, const uint8_t* par_cc, bool broadcast, const uint32_t* index,
+                           uint8_t* sk, uint8_t* cc, size_t n, uint8_t* err);
+void launch_bip32_ckd_pub(p2e_ctx* c, const Aff* table, const uint8_t* par_pkx, const uint8_t* par_pky, const uint8_t* par_cc, bool broadcast,
+                          const uint32_t* index, uint8_t* pkx, uint8_t* pky, uint8_t* cc, size_t n, uint8_t* err);
+void launch_key_hash160(p2e_ctx* c, unsigned form, const uint8_t* pkx, const uint8_t* pky, const uint8_t* err, uint8_t* out20, size_t n);
+void launch_hash160(p2e_ctx* c, const uint8_t* data, const uint64_t* offsets, uint8_t* out20, size_t n);
+#if P2E_HAS(1)
+void launch_bip32_master(p2e_ctx* c, const uint8_t* seed, size_t seed_len, uint8_t* sk, uint8_t* cc, size_t n, uint8_t* err) {
+    hipLaunchKernelGGL((k_bip32_master<0>), grid1(n), dim3(BS), 0, c->stream, seed, (u32)seed_len, sk, cc, n, err, c->d_counter);
+}
+void launch_bip32_ckd_priv(p2e_ctx* c, const Aff* table, const uint8_t* par_sk, const uint8_t* par_cc, bool broadcast, const uint32_t* index,
+                           uint8_t* sk, uint8_t* cc, size_t n, uint8_t* err) {
+    hipLaunchKernelGGL((k_bip32_ckd_priv<0>), grid1(n), dim3(BS), 0, c->stream, table, par_sk, par_cc, broadcast ? 1 : 0, index, sk, cc, n, err,
+                       c->d_counter);
+}
+void launch_bip32_ckd_pub(p2e_ctx* c, const Aff* table, const uint8_t* par_pkx, const uint8_t* par_pky, const uint8_t* par_cc, bool broadcast,
+                          const uint32_t* index, uint8_t* pkx, uint8_t* pky, uint8_t* cc, size_t n, uint8_t* err) {
+    hipLaunchKernelGGL((k_bip32_ckd_pub<0>), grid1(n), dim3(BS), 0, c->stream, table, par_pkx, par_pky, par_cc, broadcast ? 1 : 0, index, pkx,
+                       pky, cc, n, err, c->d_counter);
+}
+void launch_key_hash160(p2e_ctx* c, unsigned form, const uint8_t* pkx, const uint8_t* pky, const uint8_t* err, uint8_t* out20, size_t n) {
+    if (form == P2E_SEC1_COMPRESSED) {
+        if (err)
+            hipLaunchKernelGGL((k_key_hash160<SEC1_COMPRESSED, true>), grid1(n), dim3(BS), 0, c->stream, pkx, pky, err, out20, n);
+        else
+            hipLaunchKernelGGL((k_key_hash160<SEC1_COMPRESSED, false>), grid1(n), dim3(BS), 0, c->stream, pkx, pky, err, out20, n);
+    } else {
+        if (err)
+            hipLaunchKernelGGL((k_key_hash160<SEC1_UNCOMPRESSED, true>), grid1(n), dim3(BS), 0, c->stream, pkx, pky, err, out20, n);
+        else
+            hipLaunchKernelGGL((k_key_hash160<SEC1_UNCOMPRESSED, false>), grid1(n), dim3(BS), 0, c->stream, pkx, pky, err, out20, n);
+    }
+}
+void launch_hash160(p2e_ctx* c, const uint8_t* data, const uint64_t* offsets, uint8_t* out20, size_t n) {
+    hipLaunchKernelGGL((k_hash160<0>), grid1(n), dim3(BS), 0, c->stream, data, offsets, out20, n, c->d_counter);
+}
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static_assert(P2E_WIRE_BAD_INDEX == WIRE_BAD_INDEX, "include/p2e.h and point_table.hpp must agree");
+// n_parents is 1 (one parent serves the whole batch) or n
+static bool bip32_bad_parents(size_t n_parents, size_t n) {
+    if (n_parents == 1 || n_parents == n) return false;
+    set_error("n_parents must be 1 or n");
+    return true;
+}
+extern "C" long p2e_bip32_master_batch(p2e_ctx* c, const uint8_t* seed, size_t seed_len, uint8_t* sk32, uint8_t* cc32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!seed || !sk32 || !cc32 || !err) {
+        set_error("null pointer (seed, sk32, cc32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    if (seed_len < 16 || seed_len > 64) {
+        set_error("seed_len must be 16 .. 64 bytes");
+        return P2E_E_INVALID;
+    }
+    if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    Staged S(c);
+    seed = S.in(seed, n * seed_len);
+    sk32 = S.out(sk32, n * 32);
+    cc32 = S.out(cc32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_bip32_master(c, seed, seed_len, sk32, cc32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_bip32_ckd_priv_batch(p2e_ctx* c, const uint8_t* par_sk32, const uint8_t* par_cc32, size_t n_parents, const uint32_t* index,
+                                         uint8_t* sk32, uint8_t* cc32, size_t n, uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!par_sk32 || !par_cc32 || !index || !sk32 || !cc32 || !err) {
+        set_error("null pointer (par_sk32, par_cc32, index, sk32, cc32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    if (bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, n, &table)) return rc;   // (the generator's table of secp256k1, lane plan)
+    if (n == 0) return 0;
+    Staged S(c);
+    par_sk32 = S.in(par_sk32, n_parents * 32);
+    par_cc32 = S.in(par_cc32, n_parents * 32);
+    index = S.in(index, n * sizeof(uint32_t));
+    sk32 = S.out(sk32, n * 32);
+    cc32 = S.out(cc32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_bip32_ckd_priv(c, table, par_sk32, par_cc32, n_parents != n, index, sk32, cc32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_bip32_ckd_pub_batch(p2e_ctx* c, const uint8_t* par_pkx32, const uint8_t* par_pky32, const uint8_t* par_cc32,
+                                        size_t n_parents, const uint32_t* index, uint8_t* pkx32, uint8_t* pky32, uint8_t* cc32, size_t n,
+                                        uint8_t* err) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!par_pkx32 || !par_pky32 || !par_cc32 || !index || !pkx32 || !pky32 || !cc32 || !err) {
+        set_error("null pointer (par_pkx32, par_pky32, par_cc32, index, pkx32, pky32, cc32 and err are all required)");
+        return P2E_E_INVALID;
+    }
+    if (bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (n == 0) return 0;
+    Staged S(c);
+    par_pkx32 = S.in(par_pkx32, n_parents * 32);
+    par_pky32 = S.in(par_pky32, n_parents * 32);
+    par_cc32 = S.in(par_cc32, n_parents * 32);
+    index = S.in(index, n * sizeof(uint32_t));
+    pkx32 = S.out(pkx32, n * 32);
+    pky32 = S.out(pky32, n * 32);
+    cc32 = S.out(cc32, n * 32);
+    err = S.out(err, n);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_bip32_ckd_pub(c, table, par_pkx32, par_pky32, par_cc32, n_parents != n, index, pkx32, pky32, cc32, n, err);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_key_hash160_batch(p2e_ctx* c, unsigned form, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err_in,
+                                      uint8_t* out20, size_t n) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!pkx32 || !pky32 || !out20) {
+        set_error("null pointer (pkx32, pky32 and out20 are all required; err_in may be null)");
+        return P2E_E_INVALID;
+    }
+    if (form != P2E_SEC1_COMPRESSED && form != P2E_SEC1_UNCOMPRESSED) {
+        set_error("unknown form (P2E_SEC1_COMPRESSED or P2E_SEC1_UNCOMPRESSED)");
+        return P2E_E_INVALID;
+    }
+    if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    Staged S(c);
+    pkx32 = S.in(pkx32, n * 32);
+    pky32 = S.in(pky32, n * 32);
+    err_in = S.in(err_in, n);
+    out20 = S.out(out20, n * 20);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_key_hash160(c, form, pkx32, pky32, err_in, out20, n);
+    return S.done(finish_call(c));
+}
+extern "C" long p2e_hash160_batch(p2e_ctx* c, const uint8_t* data, const uint64_t* offsets, uint8_t* out20, size_t n) {
+    if (bad_common(c, n, n)) return P2E_E_INVALID;
+    if (!data || !offsets || !out20) {
+        set_error("null pointer (data, offsets and out20 are all required)");
+        return P2E_E_INVALID;
+    }
+    if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (n == 0) return 0;
+    Staged S(c);
+    if (S.host) {   // as p2e_hash_batch: the staging copy holds data[offsets[0], offsets[n]), moved back by offsets[0]
+        const uint64_t first = offsets[0], last = offsets[n];
+        if (last < first) {
+            set_error("offsets[n] < offsets[0]");
+            return S.done(P2E_E_INVALID);
+        }
+        const uint8_t* d = S.in(data + first, (size_t)(last - first));
+        data = d ? d - first : nullptr;
+    }
+    offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
+    out20 = S.out(out20, n * 20);
+    if (S.rc) return S.done(S.rc);
+    c->have_phases = false;
+    ZERO_COUNTER(c);
+    launch_hash160(c, data, offsets, out20, n);
     return S.done(finish_call(c));
 }
 #endif   // P2E_HAS(0)

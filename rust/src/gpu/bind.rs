@@ -311,6 +311,43 @@ pub fn schnorr_verify_aggregate(ctx: *mut P2eCtx, msgs: &[[u8; 32]], pks: &[[u8;
     Ok(verdict == 1)
 }
 
+/// The scan of one extended public key (`p2e_bip32_ckd_pub_batch` with `n_parents = 1`, then `p2e_key_hash160_batch`,
+/// host-pointer context): for every non-hardened `index` the child's point, its chain code (the standard's byte order) and
+/// the HASH160 of its compressed key.  `Err(code)` carries the `P2E_WIRE_*` code of the first failed check
+/// (`P2E_WIRE_BAD_INDEX` for a hardened index); BIP-32's "proceed with the next index" is the caller's.
+#[allow(clippy::type_complexity)]
+pub fn xpub_scan(ctx: *mut P2eCtx, key: &(BigUint, BigUint), chain_code: &[u8; 32], indices: &[u32])
+                 -> Result<Vec<std::result::Result<((BigUint, BigUint), [u8; 32], [u8; 20]), u8>>> {
+    let n = indices.len();
+    let (px, py) = (pack32(std::iter::once(key.0.clone()), 1), pack32(std::iter::once(key.1.clone()), 1));
+    let (mut x, mut y, mut cc, mut err, mut h) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![[0u8; 32]; n], vec![0u8; n], vec![[0u8; 20]; n]);
+    let rc = unsafe {
+        p2e_bip32_ckd_pub_batch(ctx, px.as_ptr(), py.as_ptr(), chain_code.as_ptr(), 1, indices.as_ptr(), x.as_mut_ptr(), y.as_mut_ptr(),
+                                cc.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    let rc = unsafe { p2e_key_hash160_batch(ctx, P2E_SEC1_COMPRESSED as u32, x.as_ptr(), y.as_ptr(), err.as_ptr(), h.as_mut_ptr().cast(), n) };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    let le = |b: &[u8], i: usize| BigUint::from_bytes_le(&b[32 * i..32 * i + 32]);
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(((le(&x, i), le(&y, i)), cc[i], h[i])) }).collect())
+}
+
+/// Hardened or ordinary private children (`p2e_bip32_ckd_priv_batch`, host-pointer context), one parent per index:
+/// `(child key, child chain code)` or the `P2E_WIRE_*` code.  The keys are secrets: they are the caller's to wipe.
+pub fn ckd_priv(ctx: *mut P2eCtx, parents: &[(BigUint, [u8; 32])], indices: &[u32]) -> Result<Vec<std::result::Result<(BigUint, [u8; 32]), u8>>> {
+    let n = indices.len();
+    ensure!(parents.len() == n || parents.len() == 1);
+    let sk = pack32(parents.iter().map(|p| p.0.clone()), parents.len());
+    let pcc: Vec<[u8; 32]> = parents.iter().map(|p| p.1).collect();
+    let (mut out, mut cc, mut err) = (vec![0u8; 32 * n], vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_bip32_ckd_priv_batch(ctx, sk.as_ptr(), pcc.as_ptr().cast(), parents.len(), indices.as_ptr(), out.as_mut_ptr(),
+                                 cc.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok((BigUint::from_bytes_le(&out[32 * i..32 * i + 32]), cc[i])) }).collect())
+}
+
 /// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
 /// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
 /// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).

@@ -300,6 +300,18 @@ extern "C" {
     pub fn p2e_schnorr_verify_aggregate(ctx: *mut P2eCtx, msg32: *const u8, pk32: *const u8, sig64: *const u8, n: usize,
         seed32: *const u8, window_bits: u32, verdict: *mut u8, err: *mut u8) -> i64;
 
+    // ---- BIP-32 key derivation and HASH160 on secp256k1: keys and coordinates little-endian, chain codes and hashes in their
+    // standard's byte order; n_parents is 1 (one parent for the batch) or n; err[i] is a P2E_WIRE_* code
+    pub fn p2e_bip32_master_batch(ctx: *mut P2eCtx, seed: *const u8, seed_len: usize, sk32: *mut u8, cc32: *mut u8, n: usize,
+        err: *mut u8) -> i64;
+    pub fn p2e_bip32_ckd_priv_batch(ctx: *mut P2eCtx, par_sk32: *const u8, par_cc32: *const u8, n_parents: usize, index: *const u32,
+        sk32: *mut u8, cc32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_bip32_ckd_pub_batch(ctx: *mut P2eCtx, par_pkx32: *const u8, par_pky32: *const u8, par_cc32: *const u8, n_parents: usize,
+        index: *const u32, pkx32: *mut u8, pky32: *mut u8, cc32: *mut u8, n: usize, err: *mut u8) -> i64;
+    pub fn p2e_key_hash160_batch(ctx: *mut P2eCtx, form: u32, pkx32: *const u8, pky32: *const u8, err_in: *const u8, out20: *mut u8,
+        n: usize) -> i64;
+    pub fn p2e_hash160_batch(ctx: *mut P2eCtx, data: *const u8, offsets: *const u64, out20: *mut u8, n: usize) -> i64;
+
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
         pky32: *mut u8) -> i32;
