@@ -19,6 +19,46 @@
  *   through its own device buffers (PCIe-inclusive; never the benchmarked configuration).
  *   The caller owns every buffer; the library owns only the p2e_ctx (stream, scratch, constant tables).
  *
+ * BUFFER OVERLAP
+ *   What a call may be handed when an output buffer shares bytes with another argument.  The rule below holds for the
+ *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_hash160_batch (keys, signing, recovery,
+ *   hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32) and the two verdict-only
+ *   verifiers p2e_ecdsa_verify_batch and p2e_p256_verify_batch.  It is checked on the host, behind the call's other argument
+ *   checks and before the context is looked at, and it is the same with P2E_CTX_HOST_POINTERS (staging would hide the race;
+ *   the contract does not depend on the mode).
+ *   1. The outputs of one call are pairwise disjoint.
+ *   2. An output may coincide with an input only EXACTLY IN PLACE: same base pointer, same bytes per element, one element per
+ *      index (a 32-byte array on a 32-byte array, v / err bytes on bytes).  Lane i then only overwrites what lane i has
+ *      already read: the kernels of these calls read every input of element i before their first store to element i.
+ *      The forms that are tested on every plan, byte for byte:
+ *        p2e_ecdsa_public_key_batch            pkx32 = sk32
+ *        p2e_ecdsa_sign_batch, _sign_recoverable_batch          r32 = msg32, s32 = k32
+ *        p2e_ecdsa_sign_deterministic_batch    r32 = msg32
+ *        p2e_ecdsa_nonce_rfc6979_batch         k32 = msg32
+ *        p2e_ecdsa_recover_batch               pkx32 = r32, pky32 = s32
+ *        p2e_point_mul_batch, p2e_point_lincomb_batch, p2e_point_add_batch   (outx32, outy32) = (px32, py32); mul also outx32 = k32
+ *        p2e_point_table_mul_batch             outx32 = k32;   p2e_point_table_lincomb_batch   outx32 = a32 or b32
+ *        p2e_schnorr_public_key_batch          pk32 = sk32;    p2e_xonly_decode_batch          px32 = pk32
+ *        p2e_bip32_ckd_priv_batch, p2e_bip32_ckd_pub_batch with n_parents == n: the children over the parents (sk32 = par_sk32,
+ *            pkx32 = par_pkx32, pky32 = par_pky32, cc32 = par_cc32) -- how a path is deepened level by level
+ *   3. Any other intersection of an output with an input is P2E_E_INVALID, with "overlap" and the two argument names in
+ *      p2e_last_error(): a shifted overlap (out == in + 32), different bytes per element (r32 on the 64-byte data of
+ *      P2E_SIG_COMPACT64, addr20 on pkx32), and every input that lanes other than "its own" read -- the single parent of a
+ *      BIP-32 call with n_parents == 1 < n (lane 0 would store child 0 over the parent the other lanes have yet to read),
+ *      the terms of p2e_point_msm and p2e_schnorr_verify_aggregate against their one-element outputs (for n == 1 too), the
+ *      points of p2e_point_table_create, the inputs of the two verdict-only verifiers.  Nothing is launched, nothing is
+ *      staged, no byte is written, and the context stays usable.
+ *   4. Adjacent ranges (the end of one is the start of the other) do not overlap.  n == 0 checks nothing and returns 0 as
+ *      before.  A null nullable argument, and an argument the chosen form does not use, is skipped.  A range whose end
+ *      wraps round the address space is refused.  Inputs may overlap each other freely.
+ *   5. Variable-length `data` (p2e_hash_batch, p2e_hash160_batch, p2e_point_decode_batch, P2E_SIG_DER in p2e_sig_decode_batch)
+ *      has an extent only the device knows.  It must not overlap any output: the CALLER's duty.  It is checked only where the
+ *      call reads offsets[0] and offsets[n] on the host anyway (P2E_CTX_HOST_POINTERS), with the same error.
+ *   6. The column-matrix calls (single generators, fused fills, aux / gate-internal / constraint-block passes, wire assembly,
+ *      the layout helpers, the curve programs' fills and passes) are different: their inputs and outputs must not overlap at
+ *      all, and this is NOT checked.
+ *   In the calls the rule covers, a null context is reported behind the argument and overlap checks.
+ *
  * ERRORS
  *   Return value: < 0 API misuse / HIP failure (p2e_last_error() has the text); >= 0 number of batch
  *   elements whose err byte is non-zero.  err[i] is a bit mask of P2E_ERR_* -- the conditions under
@@ -512,6 +552,7 @@ int p2e_synth_signatures_curve(int curve, uint64_t seed, size_t first, size_t n,
  * P2E_SIGN_PLAN_AUTO = the library's choice by batch size.  Same results, bit for bit.
  * The calls run one kernel on the context's caller stream (no internal streams, no scratch).  Return value: number of
  * flagged elements; P2E_E_INVALID on a null pointer, an unknown curve or an unknown plan; n == 0 returns 0.
+ * Outputs that share bytes with other arguments: BUFFER OVERLAP at the top (pkx32 = sk32, r32 = msg32 and s32 = k32 are fine).
  *
  * p2e_ecdsa_public_key_batch   ECDSASecretKey::to_public (curve/ecdsa.rs:16-20): (pkx, pky) = affine sk G.
  *     sk = 0 (mod n): the reference returns AffinePoint::ZERO (curve/curve_types.rs:163-171); zeros are written and
@@ -547,7 +588,8 @@ long p2e_ecdsa_sign_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t 
  *     r, s and err are bit for bit those of p2e_ecdsa_sign_batch for the same inputs and plan.
  * One kernel per call on the context's caller stream, one lane per signature in the recovery (no internal streams, no
  * scratch, no LDS).  Return value: number of flagged elements; P2E_E_INVALID on a null pointer, an unknown curve (or
- * plan); n == 0 returns 0.  Host pointers, async mode and the current device behave as for the signing calls.
+ * plan); n == 0 returns 0.  Host pointers, async mode and the current device behave as for the signing calls; so does
+ * BUFFER OVERLAP (pkx32 = r32 and pky32 = s32 are fine).
  * A zero Z at the end of the walk (impossible, see csrc/recover.hpp) would set P2E_ERR_INVERSE_OF_ZERO. */
 long p2e_ecdsa_recover_batch(p2e_ctx *ctx, int curve, const uint8_t *msg32, const uint8_t *r32, const uint8_t *s32,
                              const uint8_t *v, uint8_t *pkx32, uint8_t *pky32, size_t n, uint8_t *err);
@@ -591,7 +633,9 @@ long p2e_ecdsa_sign_recoverable_batch(p2e_ctx *ctx, int curve, unsigned plan, co
  *     plausible address.  addr20 is 4-byte aligned.  Returns 0.  secp256k1 by meaning: there is no curve argument.
  * Each call is one kernel (the deterministic signer: two and a memset) on the context's caller stream: no internal
  * streams, no LDS.  P2E_E_INVALID on a null pointer (other than the nullable ones), an unknown curve or plan; n == 0
- * returns 0.  Host pointers, async mode, the current device and failed calls behave as for the signing calls. */
+ * returns 0.  Host pointers, async mode, the current device and failed calls behave as for the signing calls.  BUFFER OVERLAP
+ * (top of this file): k32 = msg32 and r32 = msg32 are fine; addr20 and out32 have a stride of their own and lie on no input;
+ * the variable-length data of p2e_hash_batch must not touch out32 (the caller's duty, checked with host pointers only). */
 #define P2E_HASH_SHA256 0
 #define P2E_HASH_SHA256D 1     /* SHA-256 of the SHA-256 digest (Bitcoin) */
 #define P2E_HASH_KECCAK256 2   /* legacy 0x01 padding (Ethereum), not SHA3-256 */
@@ -662,7 +706,9 @@ long p2e_eth_address_batch(p2e_ctx *ctx, const uint8_t *pkx32, const uint8_t *pk
  * Each call is one kernel on the context's caller stream, one lane per element: no internal streams, no LDS, no scratch.
  * P2E_E_INVALID on a null pointer (other than the nullable ones), an unknown curve, form or flag combination; n == 0
  * returns 0.  Host pointers (the staging copy of data[offsets[0], offsets[n]) included), async mode, the current device
- * and failed calls behave as for p2e_hash_batch. */
+ * and failed calls behave as for p2e_hash_batch.  BUFFER OVERLAP (top of this file): wire forms and 32-byte arrays never
+ * have the same stride, so no output of these four calls may lie on an input (r32 == data is refused for the compact forms;
+ * for DER and for keys the extent of data is the caller's duty, checked with host pointers only). */
 #define P2E_WIRE_OK 0
 #define P2E_WIRE_BAD_LENGTH 1
 #define P2E_WIRE_BAD_PREFIX 2
@@ -716,7 +762,8 @@ long p2e_sig_encode_batch(p2e_ctx *ctx, int curve, int form, unsigned flags, con
  * words indexed by P2E_MSM_PLAN_*: the window width and the number of windows, buckets per window, the segment length
  * (a bucket is cut into segments of at most so many entries, one lane each), scratch bytes, and MAX_LANE_ADDITIONS: an
  * upper bound on the point operations (additions and doublings) any single lane performs in any launch of the call.
- * It depends on n and the plan only, never on the scalars.  Returns 0, or P2E_E_INVALID as above. */
+ * It depends on n and the plan only, never on the scalars.  Returns 0, or P2E_E_INVALID as above.
+ * BUFFER OVERLAP: no output of p2e_point_msm may lie inside k32, px32 or py32 (every lane reads them; P2E_E_INVALID). */
 #define P2E_MSM_WINDOW_AUTO 0
 #define P2E_MSM_WINDOW_MIN 4
 #define P2E_MSM_WINDOW_MAX 12
@@ -760,7 +807,8 @@ int p2e_point_msm_plan(int curve, size_t n, unsigned window_bits, uint64_t *plan
  * stream, one lane per element (csrc/point_arith.hpp): no internal streams, no scratch block, no table in LDS, nothing in the
  * private segment.  Host pointers, async mode (the return value then comes from p2e_sync), the current device and failed calls
  * behave as for the signing calls.  A zero Z at the end of a walk (impossible, see csrc/point_arith.hpp) would set
- * P2E_WIRE_INFINITY and write zeros. */
+ * P2E_WIRE_INFINITY and write zeros.  BUFFER OVERLAP (top of this file): P += Q, P = k P and P = a G + b P in place are fine
+ * (outx32 = px32, outy32 = py32), and so is outx32 = k32. */
 #define P2E_MUL_PLAN_AUTO 0
 #define P2E_MUL_PLAN_PLAIN 1   /* 128 two-bit windows over the 256-bit scalar (recover.hpp's walk), both curves */
 #define P2E_MUL_PLAN_GLV 2     /* secp256k1 only: k = +-k1 +- k2 lambda, two 128-bit halves walked together */
@@ -797,7 +845,8 @@ long p2e_point_add_batch(p2e_ctx *ctx, int curve, const uint8_t *px32, const uin
  *            conditional subtraction; outputs are canonical affine coordinates.  One kernel per call on the caller's
  *            stream, one lane per element: no internal streams, no LDS table, nothing in the private segment.  Host
  *            pointers, async mode, n == 0, null pointers (only idx may be null) and failed calls behave as for the
- *            point-arithmetic calls above.  The return value counts the non-zero err bytes.
+ *            point-arithmetic calls above.  The return value counts the non-zero err bytes.  BUFFER OVERLAP: outx32 on a
+ *            scalar array is fine; point_err of create may not lie on the points.
  *     p2e_point_table_mul_batch      out_i = k_i T[idx_i]; k = 0 (mod n): zeros and P2E_WIRE_INFINITY.  Byte for byte
  *            what p2e_point_mul_batch writes for (k_i, P_idx_i) under every plan.
  *     p2e_point_table_lincomb_batch  out_i = a_i G + b_i T[idx_i]: two window sums and one complete addition (a G = b P
@@ -834,7 +883,9 @@ long p2e_ecdsa_verify_table_batch(p2e_ctx *ctx, const void *table, const uint32_
  *            that p2e_xonly_decode_batch writes.
  *   err[i]   a P2E_WIRE_* CODE: the first failing check in the order given below; a flagged element writes zeros to all
  *            its outputs.  The return value counts the non-zero err bytes.  Null pointers, n == 0 (returns 0), host
- *            pointers, async mode, the current device and failed calls behave as for the point-arithmetic calls.
+ *            pointers, async mode, the current device, failed calls and BUFFER OVERLAP behave as for the point-arithmetic
+ *            calls (pk32 = sk32 and px32 = pk32 are fine; sig64 has another stride than every input; verdict may not lie
+ *            inside an input of the aggregate check).
  *   p2e_schnorr_public_key_batch   d = int(sk); d = 0 or d >= n: P2E_WIRE_SCALAR_RANGE (the standard fails here, nothing is
  *            reduced).  Otherwise pk = bytes(x(d G)).
  *   p2e_schnorr_sign_batch   the standard's "Default Signing"; all pointers required.  The range check of d as above; P = d G,
@@ -889,7 +940,9 @@ long p2e_schnorr_verify_aggregate(p2e_ctx *ctx, const uint8_t *msg32, const uint
  *            aligned but seed (any alignment, stride seed_len) and the data of p2e_hash160_batch (any alignment); both are read
  *            as p2e_hash_batch reads its data: aligned 4-byte words, and only words that hold a byte of the lane's element.
  *   parents  n_parents is 1 or n, anything else is P2E_E_INVALID.  With 1 every element derives from parent 0: the scan of
- *            one extended key (for n == 1 the two meanings coincide).
+ *            one extended key (for n == 1 the two meanings coincide).  With n the children may be written over the
+ *            parents, chain codes included; with 1 (and n > 1) an output on a parent array is P2E_E_INVALID: lane 0 would
+ *            store child 0 where the other lanes have yet to read the parent (BUFFER OVERLAP at the top of this file).
  *   err[i]   a P2E_WIRE_* CODE: the first failing check in the order given below.  A flagged element writes zeros to ALL its
  *            outputs, the chain code included.  BIP-32's "proceed with the next index" is NOT done: the code tells the caller.
  *   p2e_bip32_master_batch   I = HMAC-SHA512(key = "Bitcoin seed", seed_i), seed_i = seed[seed_len i, seed_len (i + 1)), one

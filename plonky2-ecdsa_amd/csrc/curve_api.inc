@@ -419,7 +419,11 @@ static bool curve_msm_ux_inputs_ok(const uint8_t* px, const uint8_t* py, const u
 // verify_message on P-256, with exactly the circuit's verdict
 extern "C" long p2e_p256_verify_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
                                       const uint8_t* pkx32, const uint8_t* pky32, size_t n, uint8_t* err, uint8_t* valid) {
-    if (bad_common(c, n, n) || !P || !msg32 || !r32 || !s32 || !pkx32 || !pky32 || !err || !valid) return P2E_E_INVALID;
+    if (!P || !msg32 || !r32 || !s32 || !pkx32 || !pky32 || !err || !valid) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_SHARED(msg32, 32, n), OV_SHARED(r32, 32, n), OV_SHARED(s32, 32, n), OV_SHARED(pkx32, 32, n),
+                        OV_SHARED(pky32, 32, n), OV_OUT(err, 1, n), OV_OUT(valid, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
     if (P->H.kind != CP_VERIFY) {
         set_error("not a verifier program");
         return P2E_E_INVALID;

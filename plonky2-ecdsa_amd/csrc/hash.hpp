@@ -494,6 +494,7 @@ P2E_HD bool body_hash(const uint8_t* data, const uint64_t* offsets, uint8_t* out
 }
 // msg32 and sk32 taken modulo the order FN::m exactly as the signer takes them (sign.hpp sign_scalar); the order itself
 // travels to the generator as a value
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class FN>
 P2E_HD void body_nonce(const uint8_t* msg32, const uint8_t* sk32, uint8_t* k32, size_t i) {
     const U256 x = fe_canon<FN>(hash_load_packed(sk32, i));

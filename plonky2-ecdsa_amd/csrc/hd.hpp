@@ -447,6 +447,7 @@ P2E_HD uint8_t body_bip32_master(const uint8_t* seed, u32 seed_len, uint8_t* sk3
 }
 
 // ---- call 2: CKDpriv.  Element i derives from parent `p` (i, or 0 where one parent serves the batch) ----------------------------
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 P2E_HD uint8_t body_bip32_ckd_priv(const Aff* T, const uint8_t* par_sk32, const uint8_t* par_cc32, size_t p, const uint32_t* index,
                                    uint8_t* sk32, uint8_t* cc32, size_t i) {
     const U256 k = load_packed(par_sk32, p);
@@ -480,6 +481,7 @@ P2E_HD uint8_t body_bip32_ckd_priv(const Aff* T, const uint8_t* par_sk32, const 
 }
 
 // ---- call 3: CKDpub -------------------------------------------------------------------------------------------------------------
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 P2E_HD uint8_t body_bip32_ckd_pub(const Aff* T, const uint8_t* par_pkx32, const uint8_t* par_pky32, const uint8_t* par_cc32, size_t p,
                                   const uint32_t* index, uint8_t* pkx32, uint8_t* pky32, uint8_t* cc32, size_t i) {
     Aff K, C;

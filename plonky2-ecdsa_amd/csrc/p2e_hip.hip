@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -17,6 +18,7 @@
 #include "consts.hpp"
 #include "device_array.hpp"
 #include "knobs.hpp"
+#include "overlap.hpp"
 #include "launch_plan.hpp"
 #include "pipeline.hpp"
 #include "prims.hpp"
@@ -1091,6 +1093,30 @@ static bool bad_common(p2e_ctx* c, size_t n, size_t ld) {
     }
     return false;
 }
+// BUFFER OVERLAP (include/p2e.h): what every fixed-stride per-element entry point does between its argument checks and its
+// first read of the context.  The call lists its arguments as spans (overlap.hpp); n == 0 checks nothing.  The context's
+// null test comes behind it, so that a call that passed the overlap check says so with "null context".
+#define OV_IN(p, bytes, count) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), false, false}
+#define OV_OUT(p, bytes, count) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), true, false}
+#define OV_SHARED(p, bytes, count) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), false, true}   // read by lanes that own no element of it
+#define OV_BCAST(p, bytes, count, lanes) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), false, (count) == 1 && (lanes) > 1}
+static bool bad_overlap(size_t n, std::initializer_list<overlap::Span> spans) {
+    if (n == 0) return false;
+    const overlap::Clash k = overlap::check(spans.begin(), spans.size());
+    if (!k.bad) return false;
+    if (k.a == k.b)
+        set_error(std::string("overlap: the end of ") + k.a + " wraps round the address space");
+    else
+        set_error(std::string("overlap: ") + k.a + " and " + k.b +
+                  " share bytes (outputs are disjoint; an output may lie on an input only exactly in place, never on a broadcast one)");
+    return true;
+}
+// bad_common for the calls that check overlap: the arguments first, the context's null test last (bad_ctx)
+static bool bad_ctx(p2e_ctx* c) {
+    if (c) return false;
+    set_error("null context");
+    return true;
+}
 static inline dim3 grid1(size_t n) { return dim3((unsigned)((n + BS - 1) / BS)); }
 #define ZERO_COUNTER(c) HIP_TRY(hipMemsetAsync((c)->d_counter, 0, sizeof(unsigned long long), (c)->stream))
 
@@ -1545,7 +1571,11 @@ extern "C" long p2e_ecdsa_verify_witness_batch(p2e_ctx* c, const uint8_t* msg32,
 }
 extern "C" long p2e_ecdsa_verify_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
                                        const uint8_t* pkx32, const uint8_t* pky32, size_t n, uint8_t* err, uint8_t* valid) {
-    if (bad_common(c, n, n) || !msg32 || !r32 || !s32 || !pkx32 || !pky32 || !err || !valid) return P2E_E_INVALID;
+    if (!msg32 || !r32 || !s32 || !pkx32 || !pky32 || !err || !valid) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_SHARED(msg32, 32, n), OV_SHARED(r32, 32, n), OV_SHARED(s32, 32, n), OV_SHARED(pkx32, 32, n),
+                        OV_SHARED(pky32, 32, n), OV_OUT(err, 1, n), OV_OUT(valid, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     return run_program(c, 0, msg32, r32, s32, pkx32, pky32, nullptr, n, n, err, valid, nullptr, 0, nullptr, 0, true);
 }
@@ -2224,7 +2254,9 @@ template void launch_sign<P256>(p2e_ctx*, int, const Aff*, const uint8_t*, const
 
 #if P2E_HAS(0)
 // curve / plan checks shared by the two calls, and the curve's generator table (P-256: made on first use, kept)
-static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Aff** table, int* chosen) {
+// `spans`: the call's arguments for the overlap check, which runs behind the argument checks and before the context is read
+static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Aff** table, int* chosen,
+                        std::initializer_list<overlap::Span> spans = {}) {
     if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
         set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
         return P2E_E_INVALID;
@@ -2237,6 +2269,7 @@ static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Af
         set_error("batch too large for one launch");
         return P2E_E_INVALID;
     }
+    if (bad_overlap(n, spans) || bad_ctx(c)) return P2E_E_INVALID;
     *chosen = plan == P2E_SIGN_PLAN_AUTO ? (n <= c->tune.sign_quad_max_n ? SIGN_PLAN_QUAD : SIGN_PLAN_LANE) : (int)plan;
     if (curve == P2E_CURVE_SECP256K1) {
         *table = c->d_fbtab.get();
@@ -2256,14 +2289,15 @@ static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Af
 }
 extern "C" long p2e_ecdsa_public_key_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* sk32, uint8_t* pkx32, uint8_t* pky32,
                                            size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!sk32 || !pkx32 || !pky32 || !err) {
         set_error("null pointer (sk32, pkx32, pky32 and err are all required)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
+                              {OV_IN(sk32, 32, n), OV_OUT(pkx32, 32, n), OV_OUT(pky32, 32, n), OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     sk32 = S.in(sk32, n * 32);
@@ -2281,14 +2315,16 @@ extern "C" long p2e_ecdsa_public_key_batch(p2e_ctx* c, int curve, unsigned plan,
 }
 extern "C" long p2e_ecdsa_sign_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* k32,
                                      uint8_t* r32, uint8_t* s32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !sk32 || !k32 || !r32 || !s32 || !err) {
         set_error("null pointer (msg32, sk32, k32, r32, s32 and err are all required)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
+                              {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_IN(k32, 32, n), OV_OUT(r32, 32, n), OV_OUT(s32, 32, n),
+                               OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     msg32 = S.in(msg32, n * 32);
@@ -2309,14 +2345,16 @@ extern "C" long p2e_ecdsa_sign_batch(p2e_ctx* c, int curve, unsigned plan, const
 // sign_message with the recovery byte, and the recovery of the public key from (msg, r, s, v) (recover.hpp)
 extern "C" long p2e_ecdsa_sign_recoverable_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32,
                                                  const uint8_t* k32, uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !sk32 || !k32 || !r32 || !s32 || !v || !err) {
         set_error("null pointer (msg32, sk32, k32, r32, s32, v and err are all required)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
+                              {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_IN(k32, 32, n), OV_OUT(r32, 32, n), OV_OUT(s32, 32, n),
+                               OV_OUT(v, 1, n), OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     msg32 = S.in(msg32, n * 32);
@@ -2337,14 +2375,16 @@ extern "C" long p2e_ecdsa_sign_recoverable_batch(p2e_ctx* c, int curve, unsigned
 }
 extern "C" long p2e_ecdsa_recover_batch(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32, const uint8_t* v,
                                         uint8_t* pkx32, uint8_t* pky32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !r32 || !s32 || !v || !pkx32 || !pky32 || !err) {
         set_error("null pointer (msg32, r32, s32, v, pkx32, pky32 and err are all required)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &chosen)) return rc;
+    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &chosen,
+                              {OV_IN(msg32, 32, n), OV_IN(r32, 32, n), OV_IN(s32, 32, n), OV_IN(v, 1, n), OV_OUT(pkx32, 32, n),
+                               OV_OUT(pky32, 32, n), OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     msg32 = S.in(msg32, n * 32);
@@ -2396,6 +2436,27 @@ void launch_eth_address(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, 
 #endif   // P2E_HAS(1)
 
 #if P2E_HAS(0)
+// the variable-length input of a staged call: the copy holds data[offsets[0], offsets[n]) and `data` becomes that copy moved
+// back by offsets[0], as in p2e_hash_batch.  false: offsets[n] < offsets[0] (the error text is set)
+// `outs`: the call's outputs; the extent of data, known here alone, must not touch them (BUFFER OVERLAP, include/p2e.h)
+static bool wire_stage_elements(Staged& S, const uint8_t*& data, const uint64_t* offsets, size_t n,
+                                std::initializer_list<overlap::Span> outs) {
+    if (!S.host) return true;
+    const uint64_t first = offsets[0], last = offsets[n];
+    if (last < first) {
+        set_error("offsets[n] < offsets[0]");
+        return false;
+    }
+    std::vector<overlap::Span> spans(outs);
+    spans.push_back(overlap::Span{"data", data + first, 1, (size_t)(last - first), false, true});   // (no lane owns a byte of it)
+    if (const overlap::Clash k = overlap::check(spans.data(), spans.size()); k.bad) {
+        set_error(std::string("overlap: ") + k.a + " and " + k.b + " share bytes (variable-length data may not touch an output)");
+        return false;
+    }
+    const uint8_t* d = S.in(data + first, (size_t)(last - first));
+    data = d ? d - first : nullptr;
+    return true;
+}
 static bool hash_batch_too_large(size_t n) {
     if (n <= ((size_t)1 << 31)) return false;
     set_error("batch too large for one launch");
@@ -2403,7 +2464,6 @@ static bool hash_batch_too_large(size_t n) {
 }
 extern "C" long p2e_hash_batch(p2e_ctx* c, int alg, unsigned out_form, const uint8_t* data, const uint64_t* offsets, uint8_t* out32,
                                size_t n) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!data || !offsets || !out32) {
         set_error("null pointer (data, offsets and out32 are all required)");
         return P2E_E_INVALID;
@@ -2417,17 +2477,10 @@ extern "C" long p2e_hash_batch(p2e_ctx* c, int alg, unsigned out_form, const uin
         return P2E_E_INVALID;
     }
     if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_IN(offsets, 8, n + 1), OV_OUT(out32, 32, n)}) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    if (S.host) {   // the staging copy holds data[offsets[0], offsets[n]): the kernel's `data` is that copy moved back by offsets[0]
-        const uint64_t first = offsets[0], last = offsets[n];
-        if (last < first) {
-            set_error("offsets[n] < offsets[0]");
-            return S.done(P2E_E_INVALID);
-        }
-        const uint8_t* d = S.in(data + first, (size_t)(last - first));
-        data = d ? d - first : nullptr;
-    }
+    if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(out32, 32, n)})) return S.done(P2E_E_INVALID);
     offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
     out32 = S.out(out32, n * 32);
     if (S.rc) return S.done(S.rc);
@@ -2437,7 +2490,6 @@ extern "C" long p2e_hash_batch(p2e_ctx* c, int alg, unsigned out_form, const uin
     return S.done(finish_call(c));
 }
 extern "C" long p2e_ecdsa_nonce_rfc6979_batch(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* sk32, uint8_t* k32, size_t n) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !sk32 || !k32) {
         set_error("null pointer (msg32, sk32 and k32 are all required)");
         return P2E_E_INVALID;
@@ -2447,6 +2499,7 @@ extern "C" long p2e_ecdsa_nonce_rfc6979_batch(p2e_ctx* c, int curve, const uint8
         return P2E_E_INVALID;
     }
     if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_OUT(k32, 32, n)}) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     msg32 = S.in(msg32, n * 32);
@@ -2461,14 +2514,16 @@ extern "C" long p2e_ecdsa_nonce_rfc6979_batch(p2e_ctx* c, int curve, const uint8
 // the nonce kernel into the context's scratch, the unchanged signer behind it, then the wipe: all on the caller's stream
 extern "C" long p2e_ecdsa_sign_deterministic_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32,
                                                    uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !sk32 || !r32 || !s32 || !err) {
         set_error("null pointer (msg32, sk32, r32, s32 and err are all required; v may be null)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen)) return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
+                              {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_OUT(r32, 32, n), OV_OUT(s32, 32, n), OV_OUT(v, 1, n),
+                               OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     msg32 = S.in(msg32, n * 32);
@@ -2499,12 +2554,13 @@ extern "C" long p2e_ecdsa_sign_deterministic_batch(p2e_ctx* c, int curve, unsign
 }
 extern "C" long p2e_eth_address_batch(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err, uint8_t* addr20,
                                       size_t n) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!pkx32 || !pky32 || !addr20) {
         set_error("null pointer (pkx32, pky32 and addr20 are all required; err may be null)");
         return P2E_E_INVALID;
     }
     if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_IN(pkx32, 32, n), OV_IN(pky32, 32, n), OV_IN(err, 1, n), OV_OUT(addr20, 20, n)}) || bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     pkx32 = S.in(pkx32, n * 32);
@@ -2615,30 +2671,19 @@ static bool wire_bad_sig_form(int form) {
     set_error("unknown form (P2E_SIG_DER, P2E_SIG_COMPACT64 or P2E_SIG_COMPACT65)");
     return true;
 }
-// the variable-length input of a staged call: the copy holds data[offsets[0], offsets[n]) and `data` becomes that copy moved
-// back by offsets[0], as in p2e_hash_batch.  false: offsets[n] < offsets[0] (the error text is set)
-static bool wire_stage_elements(Staged& S, const uint8_t*& data, const uint64_t* offsets, size_t n) {
-    if (!S.host) return true;
-    const uint64_t first = offsets[0], last = offsets[n];
-    if (last < first) {
-        set_error("offsets[n] < offsets[0]");
-        return false;
-    }
-    const uint8_t* d = S.in(data + first, (size_t)(last - first));
-    data = d ? d - first : nullptr;
-    return true;
-}
 extern "C" long p2e_point_decode_batch(p2e_ctx* c, int curve, const uint8_t* data, const uint64_t* offsets, uint8_t* px32, uint8_t* py32,
                                        size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!data || !offsets || !px32 || !py32 || !err) {
         set_error("null pointer (data, offsets, px32, py32 and err are all required)");
         return P2E_E_INVALID;
     }
     if (wire_bad_curve(curve, n)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_IN(offsets, 8, n + 1), OV_OUT(px32, 32, n), OV_OUT(py32, 32, n), OV_OUT(err, 1, n)}) || bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    if (!wire_stage_elements(S, data, offsets, n)) return S.done(P2E_E_INVALID);
+    if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(px32, 32, n), OV_OUT(py32, 32, n), OV_OUT(err, 1, n)}))
+        return S.done(P2E_E_INVALID);
     offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
     px32 = S.out(px32, n * 32);
     py32 = S.out(py32, n * 32);
@@ -2651,7 +2696,6 @@ extern "C" long p2e_point_decode_batch(p2e_ctx* c, int curve, const uint8_t* dat
 }
 extern "C" long p2e_point_encode_batch(p2e_ctx* c, int curve, int form, const uint8_t* px32, const uint8_t* py32, uint8_t* out, size_t n,
                                        uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!px32 || !py32 || !out || !err) {
         set_error("null pointer (px32, py32, out and err are all required)");
         return P2E_E_INVALID;
@@ -2661,6 +2705,9 @@ extern "C" long p2e_point_encode_batch(p2e_ctx* c, int curve, int form, const ui
         set_error("unknown form (P2E_SEC1_COMPRESSED or P2E_SEC1_UNCOMPRESSED)");
         return P2E_E_INVALID;
     }
+    if (bad_overlap(n, {OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_OUT(out, form == P2E_SEC1_COMPRESSED ? 33 : 65, n), OV_OUT(err, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     px32 = S.in(px32, n * 32);
@@ -2675,7 +2722,6 @@ extern "C" long p2e_point_encode_batch(p2e_ctx* c, int curve, int form, const ui
 }
 extern "C" long p2e_sig_decode_batch(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* data, const uint64_t* offsets,
                                      uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (wire_bad_curve(curve, n) || wire_bad_sig_form(form)) return P2E_E_INVALID;
     if (!data || !r32 || !s32 || !err || (form == P2E_SIG_DER && !offsets)) {
         set_error("null pointer (data, r32, s32 and err are all required, offsets with P2E_SIG_DER; v may be null)");
@@ -2685,16 +2731,22 @@ extern "C" long p2e_sig_decode_batch(p2e_ctx* c, int curve, int form, unsigned f
         set_error("unknown flags (0, P2E_SIG_REQUIRE_LOW_S or P2E_SIG_NORMALIZE_S)");
         return P2E_E_INVALID;
     }
+    if (form != P2E_SIG_COMPACT65) v = nullptr;
+    if (form != P2E_SIG_DER) offsets = nullptr;
+    // (DER: the extent of data is known on the device alone; the compact forms have a stride)
+    if (bad_overlap(n, {OV_IN(data, form == P2E_SIG_COMPACT64 ? 64 : 65, form == P2E_SIG_DER ? 0 : n), OV_IN(offsets, 8, n + 1),
+                        OV_OUT(r32, 32, n), OV_OUT(s32, 32, n), OV_OUT(v, 1, n), OV_OUT(err, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     if (form == P2E_SIG_DER) {
-        if (!wire_stage_elements(S, data, offsets, n)) return S.done(P2E_E_INVALID);
+        if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(r32, 32, n), OV_OUT(s32, 32, n), OV_OUT(err, 1, n)}))
+            return S.done(P2E_E_INVALID);
         offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
     } else {
         data = S.in(data, n * (form == P2E_SIG_COMPACT64 ? 64 : 65));
-        offsets = nullptr;
     }
-    if (form != P2E_SIG_COMPACT65) v = nullptr;
     r32 = S.out(r32, n * 32);
     s32 = S.out(s32, n * 32);
     v = S.out(v, n);
@@ -2707,7 +2759,6 @@ extern "C" long p2e_sig_decode_batch(p2e_ctx* c, int curve, int form, unsigned f
 }
 extern "C" long p2e_sig_encode_batch(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* r32, const uint8_t* s32,
                                      const uint8_t* v, uint8_t* out, uint8_t* out_len, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (wire_bad_curve(curve, n) || wire_bad_sig_form(form)) return P2E_E_INVALID;
     if (!r32 || !s32 || !out || !err || (form == P2E_SIG_DER && !out_len) || (form == P2E_SIG_COMPACT65 && !v)) {
         set_error("null pointer (r32, s32, out and err are all required, out_len with P2E_SIG_DER, v with P2E_SIG_COMPACT65)");
@@ -2717,9 +2768,14 @@ extern "C" long p2e_sig_encode_batch(p2e_ctx* c, int curve, int form, unsigned f
         set_error("unknown flags (0 or P2E_SIG_NORMALIZE_S)");
         return P2E_E_INVALID;
     }
-    if (n == 0) return 0;
     if (form != P2E_SIG_COMPACT65) v = nullptr;
     if (form != P2E_SIG_DER) out_len = nullptr;
+    if (bad_overlap(n, {OV_IN(r32, 32, n), OV_IN(s32, 32, n), OV_IN(v, 1, n),
+                        OV_OUT(out, form == P2E_SIG_DER ? P2E_SIG_DER_STRIDE : form == P2E_SIG_COMPACT64 ? 64 : 65, n), OV_OUT(out_len, 1, n),
+                        OV_OUT(err, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
+    if (n == 0) return 0;
     Staged S(c);
     r32 = S.in(r32, n * 32);
     s32 = S.in(s32, n * 32);
@@ -2794,12 +2850,15 @@ extern "C" int p2e_point_msm_plan(int curve, size_t n, unsigned window_bits, uin
 }
 extern "C" long p2e_point_msm(p2e_ctx* c, int curve, unsigned window_bits, const uint8_t* k32, const uint8_t* px32, const uint8_t* py32,
                               size_t n, uint8_t* outx32, uint8_t* outy32, uint8_t* status, uint8_t* point_err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!k32 || !px32 || !py32 || !outx32 || !outy32 || !status) {
         set_error("null pointer (k32, px32, py32, outx32, outy32 and status are all required; point_err may be null)");
         return P2E_E_INVALID;
     }
     if (msm_bad_args(curve, n, window_bits)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_SHARED(k32, 32, n), OV_SHARED(px32, 32, n), OV_SHARED(py32, 32, n), OV_OUT(outx32, 32, 1), OV_OUT(outy32, 32, 1),
+                        OV_OUT(status, 1, 1), OV_OUT(point_err, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
     const MsmPlan P = msm_plan(n, window_bits == P2E_MSM_WINDOW_AUTO ? msm_auto_window(n) : window_bits);
     Staged S(c);
     k32 = S.in(k32, n * 32);
@@ -2907,13 +2966,16 @@ static int point_mul_prepare(int curve, unsigned plan, size_t n, int* chosen) {
 }
 extern "C" long p2e_point_mul_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* k32, const uint8_t* px32, const uint8_t* py32,
                                     uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!k32 || !px32 || !py32 || !outx32 || !outy32 || !err) {
         set_error("null pointer (k32, px32, py32, outx32, outy32 and err are all required)");
         return P2E_E_INVALID;
     }
     int chosen = 0;
     if (int rc = point_mul_prepare(curve, plan, n, &chosen)) return rc;
+    if (bad_overlap(n, {OV_IN(k32, 32, n), OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_OUT(outx32, 32, n), OV_OUT(outy32, 32, n),
+                        OV_OUT(err, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     k32 = S.in(k32, n * 32);
@@ -2933,7 +2995,6 @@ extern "C" long p2e_point_mul_batch(p2e_ctx* c, int curve, unsigned plan, const 
 }
 extern "C" long p2e_point_lincomb_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* a32, const uint8_t* b32, const uint8_t* px32,
                                         const uint8_t* py32, uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!a32 || !b32 || !px32 || !py32 || !outx32 || !outy32 || !err) {
         set_error("null pointer (a32, b32, px32, py32, outx32, outy32 and err are all required)");
         return P2E_E_INVALID;
@@ -2941,7 +3002,10 @@ extern "C" long p2e_point_lincomb_batch(p2e_ctx* c, int curve, unsigned plan, co
     int chosen = 0, lane = 0;
     if (int rc = point_mul_prepare(curve, plan, n, &chosen)) return rc;
     const Aff* table = nullptr;
-    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &lane)) return rc;
+    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &lane,
+                              {OV_IN(a32, 32, n), OV_IN(b32, 32, n), OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_OUT(outx32, 32, n),
+                               OV_OUT(outy32, 32, n), OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     a32 = S.in(a32, n * 32);
@@ -2962,13 +3026,16 @@ extern "C" long p2e_point_lincomb_batch(p2e_ctx* c, int curve, unsigned plan, co
 }
 extern "C" long p2e_point_add_batch(p2e_ctx* c, int curve, const uint8_t* px32, const uint8_t* py32, const uint8_t* qx32, const uint8_t* qy32,
                                     uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!px32 || !py32 || !qx32 || !qy32 || !outx32 || !outy32 || !err) {
         set_error("null pointer (px32, py32, qx32, qy32, outx32, outy32 and err are all required)");
         return P2E_E_INVALID;
     }
     int chosen = 0;
     if (int rc = point_mul_prepare(curve, P2E_MUL_PLAN_PLAIN, n, &chosen)) return rc;
+    if (bad_overlap(n, {OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_IN(qx32, 32, n), OV_IN(qy32, 32, n), OV_OUT(outx32, 32, n),
+                        OV_OUT(outy32, 32, n), OV_OUT(err, 1, n)}) ||
+        bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     px32 = S.in(px32, n * 32);
@@ -3057,7 +3124,6 @@ static long table_wait_count(p2e_ctx* c) {
 extern "C" long p2e_point_table_create(p2e_ctx* c, int curve, const uint8_t* px32, const uint8_t* py32, size_t m, uint8_t* point_err,
                                        void** out) {
     if (out) *out = nullptr;
-    if (bad_common(c, m, m)) return P2E_E_INVALID;
     if (!px32 || !py32 || !out) {
         set_error("null pointer (px32, py32 and out are all required; point_err may be null)");
         return P2E_E_INVALID;
@@ -3070,6 +3136,8 @@ extern "C" long p2e_point_table_create(p2e_ctx* c, int curve, const uint8_t* px3
         set_error("a table holds 1 .. P2E_POINT_TABLE_MAX_POINTS points");
         return P2E_E_INVALID;
     }
+    // (each point's powers and rows are built by many lanes over two launches: nothing here is in place)
+    if (bad_overlap(m, {OV_SHARED(px32, 32, m), OV_SHARED(py32, 32, m), OV_OUT(point_err, 1, m)}) || bad_ctx(c)) return P2E_E_INVALID;
     Staged S(c);   // (its guard puts the context's device in place and restores the caller's)
     px32 = S.in(px32, m * 32);
     py32 = S.in(py32, m * 32);
@@ -3137,10 +3205,20 @@ extern "C" int p2e_point_table_read_window(p2e_ctx* c, const void* table, size_t
 // out1 = outx32 / valid, out2 = outy32 (null for what == 2)
 static long table_call(p2e_ctx* c, const PointTable* t, int what, const uint32_t* idx, const uint8_t* a, const uint8_t* b,
                        const uint8_t* s, uint8_t* out1, uint8_t* out2, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!t || !b || !out1 || !err || (what != 0 && !a) || (what == 2 ? !s : !out2)) {
         set_error("null pointer (only idx may be null)");
         return P2E_E_INVALID;
+    }
+    {   // the header's names of what a, b, s, out1 and out2 are in this call
+        static const char* const names[3][5] = {{"", "k32", "", "outx32", "outy32"},
+                                                {"a32", "b32", "", "outx32", "outy32"},
+                                                {"msg32", "r32", "s32", "valid", ""}};
+        const char* const* nm = names[what];
+        if (bad_overlap(n, {OV_IN(idx, 4, n), overlap::Span{nm[0], a, 32, n, false, false}, overlap::Span{nm[1], b, 32, n, false, false},
+                            overlap::Span{nm[2], s, 32, n, false, false}, overlap::Span{nm[3], out1, what == 2 ? (size_t)1 : (size_t)32, n, true, false},
+                            overlap::Span{nm[4], out2, 32, n, true, false}, OV_OUT(err, 1, n)}) ||
+            bad_ctx(c))
+            return P2E_E_INVALID;
     }
     if (t->device != c->device) {
         set_error("the table belongs to another device than the context");
@@ -3253,18 +3331,17 @@ void launch_schnorr_agg_verdict(p2e_ctx* c, const SchnorrAggLayout& L, const uns
 
 #if P2E_HAS(0)
 // the generator's table; n beyond one launch is refused (sign_prepare's rule)
-static int schnorr_prepare(p2e_ctx* c, size_t n, const Aff** table) {
+static int schnorr_prepare(p2e_ctx* c, size_t n, const Aff** table, std::initializer_list<overlap::Span> spans) {
     int lane = 0;
-    return sign_prepare(c, P2E_CURVE_SECP256K1, P2E_SIGN_PLAN_LANE, n, table, &lane);
+    return sign_prepare(c, P2E_CURVE_SECP256K1, P2E_SIGN_PLAN_LANE, n, table, &lane, spans);
 }
 extern "C" long p2e_schnorr_public_key_batch(p2e_ctx* c, const uint8_t* sk32, uint8_t* pk32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!sk32 || !pk32 || !err) {
         set_error("null pointer (sk32, pk32 and err are all required)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (int rc = schnorr_prepare(c, n, &table, {OV_IN(sk32, 32, n), OV_OUT(pk32, 32, n), OV_OUT(err, 1, n)})) return rc;
     if (n == 0) return 0;
     Staged S(c);
     sk32 = S.in(sk32, n * 32);
@@ -3278,13 +3355,14 @@ extern "C" long p2e_schnorr_public_key_batch(p2e_ctx* c, const uint8_t* sk32, ui
 }
 extern "C" long p2e_schnorr_sign_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* aux32, uint8_t* sig64, size_t n,
                                        uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !sk32 || !aux32 || !sig64 || !err) {
         set_error("null pointer (msg32, sk32, aux32, sig64 and err are all required)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (int rc = schnorr_prepare(c, n, &table,
+                                 {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_IN(aux32, 32, n), OV_OUT(sig64, 64, n), OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     msg32 = S.in(msg32, n * 32);
@@ -3300,13 +3378,14 @@ extern "C" long p2e_schnorr_sign_batch(p2e_ctx* c, const uint8_t* msg32, const u
 }
 extern "C" long p2e_schnorr_verify_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* pk32, const uint8_t* sig64, size_t n, uint8_t* err,
                                          uint8_t* valid) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !pk32 || !sig64 || !err || !valid) {
         set_error("null pointer (msg32, pk32, sig64, err and valid are all required)");
         return P2E_E_INVALID;
     }
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (int rc = schnorr_prepare(c, n, &table,
+                                 {OV_IN(msg32, 32, n), OV_IN(pk32, 32, n), OV_IN(sig64, 64, n), OV_OUT(err, 1, n), OV_OUT(valid, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     msg32 = S.in(msg32, n * 32);
@@ -3321,7 +3400,6 @@ extern "C" long p2e_schnorr_verify_batch(p2e_ctx* c, const uint8_t* msg32, const
     return S.done(finish_call(c));
 }
 extern "C" long p2e_xonly_decode_batch(p2e_ctx* c, const uint8_t* pk32, uint8_t* px32, uint8_t* py32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!pk32 || !px32 || !py32 || !err) {
         set_error("null pointer (pk32, px32, py32 and err are all required)");
         return P2E_E_INVALID;
@@ -3330,6 +3408,7 @@ extern "C" long p2e_xonly_decode_batch(p2e_ctx* c, const uint8_t* pk32, uint8_t*
         set_error("batch too large for one launch");
         return P2E_E_INVALID;
     }
+    if (bad_overlap(n, {OV_IN(pk32, 32, n), OV_OUT(px32, 32, n), OV_OUT(py32, 32, n), OV_OUT(err, 1, n)}) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     pk32 = S.in(pk32, n * 32);
@@ -3357,7 +3436,6 @@ static long schnorr_grow(p2e_ctx* c, DeviceArray<unsigned char>& block, size_t& 
 }
 extern "C" long p2e_schnorr_verify_aggregate(p2e_ctx* c, const uint8_t* msg32, const uint8_t* pk32, const uint8_t* sig64, size_t n,
                                              const uint8_t* seed32, unsigned window_bits, uint8_t* verdict, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!msg32 || !pk32 || !sig64 || !seed32 || !verdict) {
         set_error("null pointer (msg32, pk32, sig64, seed32 and verdict are all required; err may be null)");
         return P2E_E_INVALID;
@@ -3369,7 +3447,10 @@ extern "C" long p2e_schnorr_verify_aggregate(p2e_ctx* c, const uint8_t* msg32, c
     const size_t terms = 2 * n + 1;
     if (msm_bad_args(P2E_CURVE_SECP256K1, terms, window_bits)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (int rc = schnorr_prepare(c, n, &table,
+                                 {OV_SHARED(msg32, 32, n), OV_SHARED(pk32, 32, n), OV_SHARED(sig64, 64, n), OV_SHARED(seed32, 32, 1),
+                                  OV_OUT(verdict, 1, 1), OV_OUT(err, 1, n)}))
+        return rc;
     Staged S(c);
     verdict = S.out(verdict, 1);
     if (n == 0) {   // the empty batch holds: nothing to sum
@@ -3456,7 +3537,6 @@ static bool bip32_bad_parents(size_t n_parents, size_t n) {
     return true;
 }
 extern "C" long p2e_bip32_master_batch(p2e_ctx* c, const uint8_t* seed, size_t seed_len, uint8_t* sk32, uint8_t* cc32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!seed || !sk32 || !cc32 || !err) {
         set_error("null pointer (seed, sk32, cc32 and err are all required)");
         return P2E_E_INVALID;
@@ -3466,6 +3546,8 @@ extern "C" long p2e_bip32_master_batch(p2e_ctx* c, const uint8_t* seed, size_t s
         return P2E_E_INVALID;
     }
     if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_IN(seed, seed_len, n), OV_OUT(sk32, 32, n), OV_OUT(cc32, 32, n), OV_OUT(err, 1, n)}) || bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     seed = S.in(seed, n * seed_len);
@@ -3480,14 +3562,16 @@ extern "C" long p2e_bip32_master_batch(p2e_ctx* c, const uint8_t* seed, size_t s
 }
 extern "C" long p2e_bip32_ckd_priv_batch(p2e_ctx* c, const uint8_t* par_sk32, const uint8_t* par_cc32, size_t n_parents, const uint32_t* index,
                                          uint8_t* sk32, uint8_t* cc32, size_t n, uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!par_sk32 || !par_cc32 || !index || !sk32 || !cc32 || !err) {
         set_error("null pointer (par_sk32, par_cc32, index, sk32, cc32 and err are all required)");
         return P2E_E_INVALID;
     }
     if (bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table)) return rc;   // (the generator's table of secp256k1, lane plan)
+    if (int rc = schnorr_prepare(c, n, &table,   // (the generator's table of secp256k1, lane plan)
+                                 {OV_BCAST(par_sk32, 32, n_parents, n), OV_BCAST(par_cc32, 32, n_parents, n), OV_IN(index, 4, n),
+                                  OV_OUT(sk32, 32, n), OV_OUT(cc32, 32, n), OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     par_sk32 = S.in(par_sk32, n_parents * 32);
@@ -3505,14 +3589,17 @@ extern "C" long p2e_bip32_ckd_priv_batch(p2e_ctx* c, const uint8_t* par_sk32, co
 extern "C" long p2e_bip32_ckd_pub_batch(p2e_ctx* c, const uint8_t* par_pkx32, const uint8_t* par_pky32, const uint8_t* par_cc32,
                                         size_t n_parents, const uint32_t* index, uint8_t* pkx32, uint8_t* pky32, uint8_t* cc32, size_t n,
                                         uint8_t* err) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!par_pkx32 || !par_pky32 || !par_cc32 || !index || !pkx32 || !pky32 || !cc32 || !err) {
         set_error("null pointer (par_pkx32, par_pky32, par_cc32, index, pkx32, pky32, cc32 and err are all required)");
         return P2E_E_INVALID;
     }
     if (bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table)) return rc;
+    if (int rc = schnorr_prepare(c, n, &table,
+                                 {OV_BCAST(par_pkx32, 32, n_parents, n), OV_BCAST(par_pky32, 32, n_parents, n),
+                                  OV_BCAST(par_cc32, 32, n_parents, n), OV_IN(index, 4, n), OV_OUT(pkx32, 32, n), OV_OUT(pky32, 32, n),
+                                  OV_OUT(cc32, 32, n), OV_OUT(err, 1, n)}))
+        return rc;
     if (n == 0) return 0;
     Staged S(c);
     par_pkx32 = S.in(par_pkx32, n_parents * 32);
@@ -3531,7 +3618,6 @@ extern "C" long p2e_bip32_ckd_pub_batch(p2e_ctx* c, const uint8_t* par_pkx32, co
 }
 extern "C" long p2e_key_hash160_batch(p2e_ctx* c, unsigned form, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err_in,
                                       uint8_t* out20, size_t n) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!pkx32 || !pky32 || !out20) {
         set_error("null pointer (pkx32, pky32 and out20 are all required; err_in may be null)");
         return P2E_E_INVALID;
@@ -3541,6 +3627,8 @@ extern "C" long p2e_key_hash160_batch(p2e_ctx* c, unsigned form, const uint8_t* 
         return P2E_E_INVALID;
     }
     if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_IN(pkx32, 32, n), OV_IN(pky32, 32, n), OV_IN(err_in, 1, n), OV_OUT(out20, 20, n)}) || bad_ctx(c))
+        return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
     pkx32 = S.in(pkx32, n * 32);
@@ -3554,23 +3642,15 @@ extern "C" long p2e_key_hash160_batch(p2e_ctx* c, unsigned form, const uint8_t* 
     return S.done(finish_call(c));
 }
 extern "C" long p2e_hash160_batch(p2e_ctx* c, const uint8_t* data, const uint64_t* offsets, uint8_t* out20, size_t n) {
-    if (bad_common(c, n, n)) return P2E_E_INVALID;
     if (!data || !offsets || !out20) {
         set_error("null pointer (data, offsets and out20 are all required)");
         return P2E_E_INVALID;
     }
     if (hash_batch_too_large(n)) return P2E_E_INVALID;
+    if (bad_overlap(n, {OV_IN(offsets, 8, n + 1), OV_OUT(out20, 20, n)}) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    if (S.host) {   // as p2e_hash_batch: the staging copy holds data[offsets[0], offsets[n]), moved back by offsets[0]
-        const uint64_t first = offsets[0], last = offsets[n];
-        if (last < first) {
-            set_error("offsets[n] < offsets[0]");
-            return S.done(P2E_E_INVALID);
-        }
-        const uint8_t* d = S.in(data + first, (size_t)(last - first));
-        data = d ? d - first : nullptr;
-    }
+    if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(out20, 20, n)})) return S.done(P2E_E_INVALID);
     offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
     out20 = S.out(out20, n * 20);
     if (S.rc) return S.done(S.rc);

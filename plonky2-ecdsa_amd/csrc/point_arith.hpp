@@ -161,6 +161,7 @@ P2E_HD uint8_t point_finish(uint8_t e, const SignSum<CV>& s, uint8_t* outx32, ui
 }
 
 // out_i = k_i P_i; returns the code of element i
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV, int PLAN>
 P2E_HD uint8_t body_point_mul(const uint8_t* k32, const uint8_t* px32, const uint8_t* py32, uint8_t* outx32, uint8_t* outy32, size_t i) {
     Aff P;
@@ -173,6 +174,7 @@ P2E_HD uint8_t body_point_mul(const uint8_t* k32, const uint8_t* px32, const uin
 }
 
 // out_i = a_i G + b_i P_i (T: the generator's fixed-base table of sign.hpp)
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV, int PLAN>
 P2E_HD uint8_t body_point_lincomb(const Aff* T, const uint8_t* a32, const uint8_t* b32, const uint8_t* px32, const uint8_t* py32,
                                   uint8_t* outx32, uint8_t* outy32, size_t i) {
@@ -190,6 +192,7 @@ P2E_HD uint8_t body_point_lincomb(const Aff* T, const uint8_t* a32, const uint8_
 }
 
 // out_i = P_i + Q_i
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV>
 P2E_HD uint8_t body_point_add(const uint8_t* px32, const uint8_t* py32, const uint8_t* qx32, const uint8_t* qy32, uint8_t* outx32,
                               uint8_t* outy32, size_t i) {

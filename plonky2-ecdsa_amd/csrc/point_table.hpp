@@ -109,6 +109,7 @@ P2E_HD uint8_t table_pick(const Aff* tab, const u32* idx, u32 m, size_t i, const
 }
 
 // out_i = k_i T[idx_i]; returns the code of element i
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV>
 P2E_HD uint8_t body_table_mul(const Aff* tab, const u32* idx, u32 m, const uint8_t* k32, uint8_t* outx32, uint8_t* outy32, size_t i) {
     const Aff* T = nullptr;
@@ -119,6 +120,7 @@ P2E_HD uint8_t body_table_mul(const Aff* tab, const u32* idx, u32 m, const uint8
 }
 
 // out_i = a_i G + b_i T[idx_i] (G: the generator's table)
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV>
 P2E_HD uint8_t body_table_lincomb(const Aff* G, const Aff* tab, const u32* idx, u32 m, const uint8_t* a32, const uint8_t* b32,
                                   uint8_t* outx32, uint8_t* outy32, size_t i) {

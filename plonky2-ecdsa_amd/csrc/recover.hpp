@@ -178,6 +178,7 @@ P2E_HD bool recover_abscissa(const U256& r, bool hi, U256& x) {
 }
 
 // recovery of element i; returns its err byte (zeros are written where it is not 0)
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV>
 P2E_HD uint8_t body_recover(const Aff* T, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32, const uint8_t* v8,
                             uint8_t* pkx32, uint8_t* pky32, size_t i) {

@@ -117,6 +117,7 @@ P2E_HD bool schnorr_base_mul(const Aff* T, const U256& k, U256& x, U256& y) {
 }
 
 // ---- call 1: pk = bytes(x(d G)) ------------------------------------------------------------------------------------------------
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 P2E_HD uint8_t body_schnorr_public_key(const Aff* T, const uint8_t* sk32, uint8_t* pk32, size_t i) {
     const U256 d = schnorr_load_be(sk32 + 32 * i);
     uint8_t e = WIRE_OK;
@@ -196,6 +197,7 @@ P2E_HD uint8_t body_schnorr_verify(const Aff* T, const uint8_t* msg32, const uin
 }
 
 // ---- call 4: x-only key -> the library's little-endian affine point with even y ------------------------------------------------------
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 P2E_HD uint8_t body_xonly_decode(const uint8_t* pk32, uint8_t* px32, uint8_t* py32, size_t i) {
     Aff P;
     const uint8_t e = schnorr_lift_x(schnorr_load_be(pk32 + 32 * i), false, P);

@@ -273,6 +273,7 @@ P2E_HD bool sign_to_affine(const SignSum<CV>& s, U256& x, U256& y) {
 }
 
 // to_public of element i; the returned err byte is meaningful (and the outputs are written) in role 0 only
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV, int PLAN>
 P2E_HD uint8_t body_public_key(const Aff* T, const uint8_t* sk32, uint8_t* pkx32, uint8_t* pky32, size_t i, int role) {
     const U256 sk = sign_scalar<CV>(sk32, i);
@@ -293,6 +294,7 @@ P2E_HD uint8_t body_public_key(const Aff* T, const uint8_t* sk32, uint8_t* pkx32
 
 // sign_message of element i with nonce k32[i].  RECOVERABLE: also v8[i] = (R.y & 1) | (R.x >= n ? 2 : 0), what
 // recover.hpp needs to find R again (0 where flagged); r, s and the err byte are those of the plain form.
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
 template <class CV, int PLAN, bool RECOVERABLE = false>
 P2E_HD uint8_t body_sign(const Aff* T, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* k32, uint8_t* r32, uint8_t* s32,
                          size_t i, int role, uint8_t* v8 = nullptr) {

@@ -126,7 +126,8 @@ def test_refused_arguments(hctx):
     # seed_len outside 16 .. 64, null pointers
     for seed_len in (0, 15, 65, 1 << 20):
         assert L.p2e_bip32_master_batch(h, p, C.c_size_t(seed_len), p, p, one, p) == INV
-    assert L.p2e_bip32_master_batch(h, p, C.c_size_t(16), p, p, one, p) == 0
+    sk1, cc1, err1 = np.zeros(32, np.uint8), np.zeros(32, np.uint8), np.zeros(1, np.uint8)     # (outputs are pairwise disjoint)
+    assert L.p2e_bip32_master_batch(h, p, C.c_size_t(16), _p(sk1), _p(cc1), one, _p(err1)) == 0
     for k in range(4):
         a = [p, p, p, p]
         a[k] = None
