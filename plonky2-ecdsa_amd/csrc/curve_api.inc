@@ -417,19 +417,19 @@ static bool curve_msm_ux_inputs_ok(const uint8_t* px, const uint8_t* py, const u
 // the verifier circuit's verdict alone: valid[i] = curve_assert_valid's connect and r == x both hold (and no error
 // flag), no witness written -- a pre-filter for invalid signatures; native counterpart curve/ecdsa.rs:42-62
 // verify_message on P-256, with exactly the circuit's verdict
-extern "C" long p2e_p256_verify_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
-                                      const uint8_t* pkx32, const uint8_t* pky32, size_t n, uint8_t* err, uint8_t* valid) {
-    if (!P || !msg32 || !r32 || !s32 || !pkx32 || !pky32 || !err || !valid) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_SHARED(msg32, 32, n), OV_SHARED(r32, 32, n), OV_SHARED(s32, 32, n), OV_SHARED(pkx32, 32, n),
-                        OV_SHARED(pky32, 32, n), OV_OUT(err, 1, n), OV_OUT(valid, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
-    if (P->H.kind != CP_VERIFY) {
+extern "C" long p2e_p256_verify_batch(p2e_ctx* c, const p2e_curve_program* prog, const uint8_t* msg32, const uint8_t* r32,
+                                      const uint8_t* s32, const uint8_t* pkx32, const uint8_t* pky32, size_t n, uint8_t* err,
+                                      uint8_t* valid) {
+    // (staging is curve_dispatch's own, as for every curve program)
+    const Args args = {ARG_OPAQUE(prog),         ARG_SHARED(msg32, 32, n), ARG_SHARED(r32, 32, n), ARG_SHARED(s32, 32, n),
+                       ARG_SHARED(pkx32, 32, n), ARG_SHARED(pky32, 32, n), ARG_OUT(err, 1, n),     ARG_OUT(valid, 1, n)};
+    if (missing(args) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (prog->H.kind != CP_VERIFY) {
         set_error("not a verifier program");
         return P2E_E_INVALID;
     }
     if (n == 0) return 0;
-    return curve_dispatch(c, P, msg32, r32, s32, pkx32, pky32, nullptr, n, n, err, valid, true);
+    return curve_dispatch(c, prog, msg32, r32, s32, pkx32, pky32, nullptr, n, n, err, valid, true);
 }
 // curve_scalar_mul_windowed(p, k) / curve_scalar_mul(p, k) witnesses of a batch of (point, scalar) pairs
 extern "C" long p2e_curve_mul_witness_batch(p2e_ctx* c, const p2e_curve_program* P, const uint8_t* px32, const uint8_t* py32,

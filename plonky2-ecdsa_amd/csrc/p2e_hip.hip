@@ -19,6 +19,7 @@
 #include "device_array.hpp"
 #include "knobs.hpp"
 #include "overlap.hpp"
+#include "call_args.hpp"
 #include "launch_plan.hpp"
 #include "pipeline.hpp"
 #include "prims.hpp"
@@ -984,18 +985,25 @@ static int ensure_scratch(p2e_ctx* c, size_t bytes) {
     return 0;
 }
 
-// finish a call: fetch the flagged count (synchronously unless the context is async)
-static long finish_call(p2e_ctx* c) {
+// the launches' status, and the flagged count on its way to the host
+static long fetch_count(p2e_ctx* c) {
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) {
         set_error(std::string("kernel launch: ") + hipGetErrorString(le));
         return P2E_E_HIP;
     }
     HIP_TRY(hipMemcpyAsync(c->h_counter, c->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+// finish a call: fetch the flagged count (synchronously unless the context is async)
+static long finish_call(p2e_ctx* c) {
+    if (long r = fetch_count(c)) return r;
     if (c->flags & P2E_CTX_ASYNC) return 0;
     int r = p2e_sync(c);
     return r;
 }
+
+#define ZERO_COUNTER(c) HIP_TRY(hipMemsetAsync((c)->d_counter, 0, sizeof(unsigned long long), (c)->stream))
 
 // ---- host-pointer staging (slow path, used by ctypes-only callers) ----------------------------------
 struct Staged {
@@ -1080,6 +1088,16 @@ struct Staged {
     ~Staged() {
         if (!finished) release(true);
     }
+    // what every per-element call does around its launches.  begin: the list's buffers staged, the phase times of an earlier
+    // fused call dropped, the flagged count zeroed; nonzero = the call's return value.  end: the count fetched, the outputs home.
+    long begin(call_args::List args) {
+        call_args::stage(args, *this);
+        if (rc) return done(rc);
+        c->have_phases = false;
+        ZERO_COUNTER(c);
+        return 0;
+    }
+    long end() { return done(finish_call(c)); }
 };
 
 static bool bad_common(p2e_ctx* c, size_t n, size_t ld) {
@@ -1094,15 +1112,20 @@ static bool bad_common(p2e_ctx* c, size_t n, size_t ld) {
     return false;
 }
 // BUFFER OVERLAP (include/p2e.h): what every fixed-stride per-element entry point does between its argument checks and its
-// first read of the context.  The call lists its arguments as spans (overlap.hpp); n == 0 checks nothing.  The context's
+// first read of the context.  The call lists its arguments once (call_args.hpp); n == 0 checks nothing.  The context's
 // null test comes behind it, so that a call that passed the overlap check says so with "null context".
-#define OV_IN(p, bytes, count) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), false, false}
-#define OV_OUT(p, bytes, count) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), true, false}
-#define OV_SHARED(p, bytes, count) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), false, true}   // read by lanes that own no element of it
-#define OV_BCAST(p, bytes, count, lanes) overlap::Span{#p, p, (size_t)(bytes), (size_t)(count), false, (count) == 1 && (lanes) > 1}
-static bool bad_overlap(size_t n, std::initializer_list<overlap::Span> spans) {
+using Args = call_args::List;
+// the null test of a call's list, in front of every other check (the wire-signature calls: behind curve and form)
+static bool missing(Args args, const char* form = nullptr) {
+    std::string text;
+    if (!call_args::missing(args, text, form)) return false;
+    set_error(text);
+    return true;
+}
+static bool bad_overlap(size_t n, Args args) {
     if (n == 0) return false;
-    const overlap::Clash k = overlap::check(spans.begin(), spans.size());
+    overlap::Span spans[call_args::kMaxBufs];
+    const overlap::Clash k = overlap::check(spans, call_args::spans(args, n, spans));
     if (!k.bad) return false;
     if (k.a == k.b)
         set_error(std::string("overlap: the end of ") + k.a + " wraps round the address space");
@@ -1117,8 +1140,18 @@ static bool bad_ctx(p2e_ctx* c) {
     set_error("null context");
     return true;
 }
+static bool bad_curve(int curve) {
+    if (curve == P2E_CURVE_SECP256K1 || curve == P2E_CURVE_P256) return false;
+    set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
+    return true;
+}
+// one launch covers at most 2^31 elements
+static bool batch_too_large(size_t n) {
+    if (n <= ((size_t)1 << 31)) return false;
+    set_error("batch too large for one launch");
+    return true;
+}
 static inline dim3 grid1(size_t n) { return dim3((unsigned)((n + BS - 1) / BS)); }
-#define ZERO_COUNTER(c) HIP_TRY(hipMemsetAsync((c)->d_counter, 0, sizeof(unsigned long long), (c)->stream))
 
 // ====================================================================================================
 // single generators
@@ -1571,11 +1604,10 @@ extern "C" long p2e_ecdsa_verify_witness_batch(p2e_ctx* c, const uint8_t* msg32,
 }
 extern "C" long p2e_ecdsa_verify_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32,
                                        const uint8_t* pkx32, const uint8_t* pky32, size_t n, uint8_t* err, uint8_t* valid) {
-    if (!msg32 || !r32 || !s32 || !pkx32 || !pky32 || !err || !valid) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_SHARED(msg32, 32, n), OV_SHARED(r32, 32, n), OV_SHARED(s32, 32, n), OV_SHARED(pkx32, 32, n),
-                        OV_SHARED(pky32, 32, n), OV_OUT(err, 1, n), OV_OUT(valid, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
+    // (staging is run_program's own, as for the witness calls)
+    const Args args = {ARG_SHARED(msg32, 32, n), ARG_SHARED(r32, 32, n), ARG_SHARED(s32, 32, n), ARG_SHARED(pkx32, 32, n),
+                       ARG_SHARED(pky32, 32, n), ARG_OUT(err, 1, n), ARG_OUT(valid, 1, n)};
+    if (missing(args) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     return run_program(c, 0, msg32, r32, s32, pkx32, pky32, nullptr, n, n, err, valid, nullptr, 0, nullptr, 0, true);
 }
@@ -2254,22 +2286,14 @@ template void launch_sign<P256>(p2e_ctx*, int, const Aff*, const uint8_t*, const
 
 #if P2E_HAS(0)
 // curve / plan checks shared by the two calls, and the curve's generator table (P-256: made on first use, kept)
-// `spans`: the call's arguments for the overlap check, which runs behind the argument checks and before the context is read
-static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Aff** table, int* chosen,
-                        std::initializer_list<overlap::Span> spans = {}) {
-    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
-        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
-        return P2E_E_INVALID;
-    }
+// `args`: the call's buffers for the overlap check, which runs behind the argument checks and before the context is read
+static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Aff** table, int* chosen, Args args = {}) {
+    if (bad_curve(curve)) return P2E_E_INVALID;
     if (plan != P2E_SIGN_PLAN_AUTO && plan != P2E_SIGN_PLAN_LANE && plan != P2E_SIGN_PLAN_QUAD) {
         set_error("unknown plan (P2E_SIGN_PLAN_AUTO, P2E_SIGN_PLAN_LANE or P2E_SIGN_PLAN_QUAD)");
         return P2E_E_INVALID;
     }
-    if (n > ((size_t)1 << 31)) {
-        set_error("batch too large for one launch");
-        return P2E_E_INVALID;
-    }
-    if (bad_overlap(n, spans) || bad_ctx(c)) return P2E_E_INVALID;
+    if (batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     *chosen = plan == P2E_SIGN_PLAN_AUTO ? (n <= c->tune.sign_quad_max_n ? SIGN_PLAN_QUAD : SIGN_PLAN_LANE) : (int)plan;
     if (curve == P2E_CURVE_SECP256K1) {
         *table = c->d_fbtab.get();
@@ -2289,119 +2313,71 @@ static int sign_prepare(p2e_ctx* c, int curve, unsigned plan, size_t n, const Af
 }
 extern "C" long p2e_ecdsa_public_key_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* sk32, uint8_t* pkx32, uint8_t* pky32,
                                            size_t n, uint8_t* err) {
-    if (!sk32 || !pkx32 || !pky32 || !err) {
-        set_error("null pointer (sk32, pkx32, pky32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(sk32, 32, n), ARG_OUT(pkx32, 32, n), ARG_OUT(pky32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
-                              {OV_IN(sk32, 32, n), OV_OUT(pkx32, 32, n), OV_OUT(pky32, 32, n), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    sk32 = S.in(sk32, n * 32);
-    pkx32 = S.out(pkx32, n * 32);
-    pky32 = S.out(pky32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     if (curve == P2E_CURVE_P256)
         launch_sign<P256>(c, chosen, table, nullptr, sk32, nullptr, pkx32, pky32, n, err);
     else
         launch_sign<Secp256k1>(c, chosen, table, nullptr, sk32, nullptr, pkx32, pky32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_ecdsa_sign_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* k32,
                                      uint8_t* r32, uint8_t* s32, size_t n, uint8_t* err) {
-    if (!msg32 || !sk32 || !k32 || !r32 || !s32 || !err) {
-        set_error("null pointer (msg32, sk32, k32, r32, s32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(msg32, 32, n), ARG_IN(sk32, 32, n), ARG_IN(k32, 32, n),
+                       ARG_OUT(r32, 32, n), ARG_OUT(s32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
-                              {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_IN(k32, 32, n), OV_OUT(r32, 32, n), OV_OUT(s32, 32, n),
-                               OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    msg32 = S.in(msg32, n * 32);
-    sk32 = S.in(sk32, n * 32);
-    k32 = S.in(k32, n * 32);
-    r32 = S.out(r32, n * 32);
-    s32 = S.out(s32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     if (curve == P2E_CURVE_P256)
         launch_sign<P256>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
     else
         launch_sign<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 // sign_message with the recovery byte, and the recovery of the public key from (msg, r, s, v) (recover.hpp)
 extern "C" long p2e_ecdsa_sign_recoverable_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32,
                                                  const uint8_t* k32, uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
-    if (!msg32 || !sk32 || !k32 || !r32 || !s32 || !v || !err) {
-        set_error("null pointer (msg32, sk32, k32, r32, s32, v and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(msg32, 32, n), ARG_IN(sk32, 32, n), ARG_IN(k32, 32, n), ARG_OUT(r32, 32, n),
+                       ARG_OUT(s32, 32, n),  ARG_OUT(v, 1, n),    ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
-                              {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_IN(k32, 32, n), OV_OUT(r32, 32, n), OV_OUT(s32, 32, n),
-                               OV_OUT(v, 1, n), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    msg32 = S.in(msg32, n * 32);
-    sk32 = S.in(sk32, n * 32);
-    k32 = S.in(k32, n * 32);
-    r32 = S.out(r32, n * 32);
-    s32 = S.out(s32, n * 32);
-    v = S.out(v, n);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     if (curve == P2E_CURVE_P256)
         launch_sign_recoverable<P256>(c, chosen, table, msg32, sk32, k32, r32, s32, v, n, err);
     else
         launch_sign_recoverable<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, v, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_ecdsa_recover_batch(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* r32, const uint8_t* s32, const uint8_t* v,
                                         uint8_t* pkx32, uint8_t* pky32, size_t n, uint8_t* err) {
-    if (!msg32 || !r32 || !s32 || !v || !pkx32 || !pky32 || !err) {
-        set_error("null pointer (msg32, r32, s32, v, pkx32, pky32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(msg32, 32, n),  ARG_IN(r32, 32, n),    ARG_IN(s32, 32, n), ARG_IN(v, 1, n),
+                       ARG_OUT(pkx32, 32, n), ARG_OUT(pky32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &chosen,
-                              {OV_IN(msg32, 32, n), OV_IN(r32, 32, n), OV_IN(s32, 32, n), OV_IN(v, 1, n), OV_OUT(pkx32, 32, n),
-                               OV_OUT(pky32, 32, n), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &chosen, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    msg32 = S.in(msg32, n * 32);
-    r32 = S.in(r32, n * 32);
-    s32 = S.in(s32, n * 32);
-    v = S.in(v, n);
-    pkx32 = S.out(pkx32, n * 32);
-    pky32 = S.out(pky32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     if (curve == P2E_CURVE_P256)
         launch_recover<P256>(c, table, msg32, r32, s32, v, pkx32, pky32, n, err);
     else
         launch_recover<Secp256k1>(c, table, msg32, r32, s32, v, pkx32, pky32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 #endif   // P2E_HAS(0)
 
@@ -2438,18 +2414,21 @@ void launch_eth_address(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, 
 #if P2E_HAS(0)
 // the variable-length input of a staged call: the copy holds data[offsets[0], offsets[n]) and `data` becomes that copy moved
 // back by offsets[0], as in p2e_hash_batch.  false: offsets[n] < offsets[0] (the error text is set)
-// `outs`: the call's outputs; the extent of data, known here alone, must not touch them (BUFFER OVERLAP, include/p2e.h)
-static bool wire_stage_elements(Staged& S, const uint8_t*& data, const uint64_t* offsets, size_t n,
-                                std::initializer_list<overlap::Span> outs) {
+// `args`: the call's list, not yet staged (offsets is read here on the host); the extent of data, known here alone, must
+// not touch the list's outputs (BUFFER OVERLAP, include/p2e.h)
+static bool wire_stage_elements(Staged& S, Args args, const uint8_t*& data, const uint64_t* offsets, size_t n) {
     if (!S.host) return true;
     const uint64_t first = offsets[0], last = offsets[n];
     if (last < first) {
         set_error("offsets[n] < offsets[0]");
         return false;
     }
-    std::vector<overlap::Span> spans(outs);
-    spans.push_back(overlap::Span{"data", data + first, 1, (size_t)(last - first), false, true});   // (no lane owns a byte of it)
-    if (const overlap::Clash k = overlap::check(spans.data(), spans.size()); k.bad) {
+    overlap::Span spans[call_args::kMaxBufs + 1];
+    size_t num = 0;
+    for (size_t i = 0, all = call_args::spans(args, n, spans); i < all; i++)
+        if (spans[i].is_output) spans[num++] = spans[i];
+    spans[num++] = overlap::Span{"data", data + first, 1, (size_t)(last - first), false, true};   // (no lane owns a byte of it)
+    if (const overlap::Clash k = overlap::check(spans, num); k.bad) {
         set_error(std::string("overlap: ") + k.a + " and " + k.b + " share bytes (variable-length data may not touch an output)");
         return false;
     }
@@ -2457,17 +2436,10 @@ static bool wire_stage_elements(Staged& S, const uint8_t*& data, const uint64_t*
     data = d ? d - first : nullptr;
     return true;
 }
-static bool hash_batch_too_large(size_t n) {
-    if (n <= ((size_t)1 << 31)) return false;
-    set_error("batch too large for one launch");
-    return true;
-}
 extern "C" long p2e_hash_batch(p2e_ctx* c, int alg, unsigned out_form, const uint8_t* data, const uint64_t* offsets, uint8_t* out32,
                                size_t n) {
-    if (!data || !offsets || !out32) {
-        set_error("null pointer (data, offsets and out32 are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_OPAQUE(data), ARG_IN(offsets, 8, n + 1), ARG_OUT(out32, 32, n)};
+    if (missing(args)) return P2E_E_INVALID;
     if (alg != P2E_HASH_SHA256 && alg != P2E_HASH_SHA256D && alg != P2E_HASH_KECCAK256) {
         set_error("unknown alg (P2E_HASH_SHA256, P2E_HASH_SHA256D or P2E_HASH_KECCAK256)");
         return P2E_E_INVALID;
@@ -2476,67 +2448,37 @@ extern "C" long p2e_hash_batch(p2e_ctx* c, int alg, unsigned out_form, const uin
         set_error("unknown out_form (P2E_DIGEST_BYTES or P2E_DIGEST_SCALAR)");
         return P2E_E_INVALID;
     }
-    if (hash_batch_too_large(n)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_IN(offsets, 8, n + 1), OV_OUT(out32, 32, n)}) || bad_ctx(c)) return P2E_E_INVALID;
+    if (batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(out32, 32, n)})) return S.done(P2E_E_INVALID);
-    offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
-    out32 = S.out(out32, n * 32);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (!wire_stage_elements(S, args, data, offsets, n)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
     launch_hash(c, alg, out_form, data, offsets, out32, n);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_ecdsa_nonce_rfc6979_batch(p2e_ctx* c, int curve, const uint8_t* msg32, const uint8_t* sk32, uint8_t* k32, size_t n) {
-    if (!msg32 || !sk32 || !k32) {
-        set_error("null pointer (msg32, sk32 and k32 are all required)");
-        return P2E_E_INVALID;
-    }
-    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
-        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
-        return P2E_E_INVALID;
-    }
-    if (hash_batch_too_large(n)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_OUT(k32, 32, n)}) || bad_ctx(c)) return P2E_E_INVALID;
+    const Args args = {ARG_IN(msg32, 32, n), ARG_IN(sk32, 32, n), ARG_OUT(k32, 32, n)};
+    if (missing(args) || bad_curve(curve) || batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    msg32 = S.in(msg32, n * 32);
-    sk32 = S.in(sk32, n * 32);
-    k32 = S.out(k32, n * 32);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_nonce_rfc6979(c, curve, msg32, sk32, k32, n);
-    return S.done(finish_call(c));
+    return S.end();
 }
 // the nonce kernel into the context's scratch, the unchanged signer behind it, then the wipe: all on the caller's stream
 extern "C" long p2e_ecdsa_sign_deterministic_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* msg32, const uint8_t* sk32,
                                                    uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
-    if (!msg32 || !sk32 || !r32 || !s32 || !err) {
-        set_error("null pointer (msg32, sk32, r32, s32 and err are all required; v may be null)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(msg32, 32, n), ARG_IN(sk32, 32, n),  ARG_OUT(r32, 32, n),
+                       ARG_OUT(s32, 32, n),  ARG_OUT_OPT(v, 1, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
     int chosen = 0;
-    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen,
-                              {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_OUT(r32, 32, n), OV_OUT(s32, 32, n), OV_OUT(v, 1, n),
-                               OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = sign_prepare(c, curve, plan, n, &table, &chosen, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    msg32 = S.in(msg32, n * 32);
-    sk32 = S.in(sk32, n * 32);
-    r32 = S.out(r32, n * 32);
-    s32 = S.out(s32, n * 32);
-    v = S.out(v, n);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
     if (int rc = ensure_scratch(c, n * 32)) return S.done(rc);
     uint8_t* const k32 = static_cast<uint8_t*>(c->scratch);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_nonce_rfc6979(c, curve, msg32, sk32, k32, n);
     if (curve == P2E_CURVE_P256) {
         if (v)
@@ -2550,28 +2492,17 @@ extern "C" long p2e_ecdsa_sign_deterministic_batch(p2e_ctx* c, int curve, unsign
             launch_sign<Secp256k1>(c, chosen, table, msg32, sk32, k32, r32, s32, n, err);
     }
     HIP_TRY(hipMemsetAsync(k32, 0, n * 32, c->stream));   // the nonces are secret: gone once the signer has read them
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_eth_address_batch(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err, uint8_t* addr20,
                                       size_t n) {
-    if (!pkx32 || !pky32 || !addr20) {
-        set_error("null pointer (pkx32, pky32 and addr20 are all required; err may be null)");
-        return P2E_E_INVALID;
-    }
-    if (hash_batch_too_large(n)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_IN(pkx32, 32, n), OV_IN(pky32, 32, n), OV_IN(err, 1, n), OV_OUT(addr20, 20, n)}) || bad_ctx(c))
-        return P2E_E_INVALID;
+    const Args args = {ARG_IN(pkx32, 32, n), ARG_IN(pky32, 32, n), ARG_IN_OPT(err, 1, n), ARG_OUT(addr20, 20, n)};
+    if (missing(args) || batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    pkx32 = S.in(pkx32, n * 32);
-    pky32 = S.in(pky32, n * 32);
-    err = S.in(err, n);
-    addr20 = S.out(addr20, n * 20);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_eth_address(c, pkx32, pky32, err, addr20, n);
-    return S.done(finish_call(c));
+    return S.end();
 }
 #endif   // P2E_HAS(0)
 
@@ -2659,135 +2590,92 @@ static_assert(P2E_SEC1_COMPRESSED == SEC1_COMPRESSED && P2E_SEC1_UNCOMPRESSED ==
                   P2E_SIG_COMPACT64 == SIG_COMPACT64 && P2E_SIG_COMPACT65 == SIG_COMPACT65 && P2E_SIG_REQUIRE_LOW_S == SIG_REQUIRE_LOW_S &&
                   P2E_SIG_NORMALIZE_S == SIG_NORMALIZE_S && P2E_SIG_DER_STRIDE == SIG_DER_STRIDE,
               "include/p2e.h and wire.hpp");
-static bool wire_bad_curve(int curve, size_t n) {
-    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
-        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
-        return true;
-    }
-    return hash_batch_too_large(n);
-}
+static bool wire_bad_curve(int curve, size_t n) { return bad_curve(curve) || batch_too_large(n); }
 static bool wire_bad_sig_form(int form) {
     if (form == P2E_SIG_DER || form == P2E_SIG_COMPACT64 || form == P2E_SIG_COMPACT65) return false;
     set_error("unknown form (P2E_SIG_DER, P2E_SIG_COMPACT64 or P2E_SIG_COMPACT65)");
     return true;
 }
+static const char* wire_sig_form_name(int form) {
+    return form == P2E_SIG_DER ? "P2E_SIG_DER" : form == P2E_SIG_COMPACT64 ? "P2E_SIG_COMPACT64" : "P2E_SIG_COMPACT65";
+}
 extern "C" long p2e_point_decode_batch(p2e_ctx* c, int curve, const uint8_t* data, const uint64_t* offsets, uint8_t* px32, uint8_t* py32,
                                        size_t n, uint8_t* err) {
-    if (!data || !offsets || !px32 || !py32 || !err) {
-        set_error("null pointer (data, offsets, px32, py32 and err are all required)");
-        return P2E_E_INVALID;
-    }
-    if (wire_bad_curve(curve, n)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_IN(offsets, 8, n + 1), OV_OUT(px32, 32, n), OV_OUT(py32, 32, n), OV_OUT(err, 1, n)}) || bad_ctx(c))
-        return P2E_E_INVALID;
+    const Args args = {ARG_OPAQUE(data), ARG_IN(offsets, 8, n + 1), ARG_OUT(px32, 32, n), ARG_OUT(py32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args) || wire_bad_curve(curve, n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(px32, 32, n), OV_OUT(py32, 32, n), OV_OUT(err, 1, n)}))
-        return S.done(P2E_E_INVALID);
-    offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
-    px32 = S.out(px32, n * 32);
-    py32 = S.out(py32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (!wire_stage_elements(S, args, data, offsets, n)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
     launch_point_decode(c, curve, data, offsets, px32, py32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_point_encode_batch(p2e_ctx* c, int curve, int form, const uint8_t* px32, const uint8_t* py32, uint8_t* out, size_t n,
                                        uint8_t* err) {
-    if (!px32 || !py32 || !out || !err) {
-        set_error("null pointer (px32, py32, out and err are all required)");
-        return P2E_E_INVALID;
-    }
-    if (wire_bad_curve(curve, n)) return P2E_E_INVALID;
+    const Args args = {ARG_IN(px32, 32, n), ARG_IN(py32, 32, n), ARG_OUT(out, form == P2E_SEC1_COMPRESSED ? 33 : 65, n), ARG_OUT(err, 1, n)};
+    if (missing(args) || wire_bad_curve(curve, n)) return P2E_E_INVALID;
     if (form != P2E_SEC1_COMPRESSED && form != P2E_SEC1_UNCOMPRESSED) {
         set_error("unknown form (P2E_SEC1_COMPRESSED or P2E_SEC1_UNCOMPRESSED)");
         return P2E_E_INVALID;
     }
-    if (bad_overlap(n, {OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_OUT(out, form == P2E_SEC1_COMPRESSED ? 33 : 65, n), OV_OUT(err, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
+    if (bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    px32 = S.in(px32, n * 32);
-    py32 = S.in(py32, n * 32);
-    out = S.out(out, n * (form == P2E_SEC1_COMPRESSED ? 33 : 65));
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_point_encode(c, curve, form, px32, py32, out, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_sig_decode_batch(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* data, const uint64_t* offsets,
                                      uint8_t* r32, uint8_t* s32, uint8_t* v, size_t n, uint8_t* err) {
     if (wire_bad_curve(curve, n) || wire_bad_sig_form(form)) return P2E_E_INVALID;
-    if (!data || !r32 || !s32 || !err || (form == P2E_SIG_DER && !offsets)) {
-        set_error("null pointer (data, r32, s32 and err are all required, offsets with P2E_SIG_DER; v may be null)");
-        return P2E_E_INVALID;
-    }
+    // an argument its form does not use is ignored: offsets is DER's, v is COMPACT65's (and optional there)
+    const bool der = form == P2E_SIG_DER;
+    if (form != P2E_SIG_COMPACT65) v = nullptr;
+    if (!der) offsets = nullptr;
+    // (DER: the extent of data is known on the device alone; the compact forms have a stride)
+    const Args args = {der ? ARG_OPAQUE(data) : ARG_IN(data, form == P2E_SIG_COMPACT64 ? 64 : 65, n),
+                       ARG_IN_IF(der, offsets, 8, n + 1),
+                       ARG_OUT(r32, 32, n),
+                       ARG_OUT(s32, 32, n),
+                       ARG_OUT_OPT(v, 1, n),
+                       ARG_OUT(err, 1, n)};
+    if (missing(args, wire_sig_form_name(form))) return P2E_E_INVALID;
     if (flags != 0 && flags != P2E_SIG_REQUIRE_LOW_S && flags != P2E_SIG_NORMALIZE_S) {
         set_error("unknown flags (0, P2E_SIG_REQUIRE_LOW_S or P2E_SIG_NORMALIZE_S)");
         return P2E_E_INVALID;
     }
-    if (form != P2E_SIG_COMPACT65) v = nullptr;
-    if (form != P2E_SIG_DER) offsets = nullptr;
-    // (DER: the extent of data is known on the device alone; the compact forms have a stride)
-    if (bad_overlap(n, {OV_IN(data, form == P2E_SIG_COMPACT64 ? 64 : 65, form == P2E_SIG_DER ? 0 : n), OV_IN(offsets, 8, n + 1),
-                        OV_OUT(r32, 32, n), OV_OUT(s32, 32, n), OV_OUT(v, 1, n), OV_OUT(err, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
+    if (bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    if (form == P2E_SIG_DER) {
-        if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(r32, 32, n), OV_OUT(s32, 32, n), OV_OUT(err, 1, n)}))
-            return S.done(P2E_E_INVALID);
-        offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
-    } else {
-        data = S.in(data, n * (form == P2E_SIG_COMPACT64 ? 64 : 65));
-    }
-    r32 = S.out(r32, n * 32);
-    s32 = S.out(s32, n * 32);
-    v = S.out(v, n);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (der && !wire_stage_elements(S, args, data, offsets, n)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
     launch_sig_decode(c, curve, form, flags, data, offsets, r32, s32, v, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_sig_encode_batch(p2e_ctx* c, int curve, int form, unsigned flags, const uint8_t* r32, const uint8_t* s32,
                                      const uint8_t* v, uint8_t* out, uint8_t* out_len, size_t n, uint8_t* err) {
     if (wire_bad_curve(curve, n) || wire_bad_sig_form(form)) return P2E_E_INVALID;
-    if (!r32 || !s32 || !out || !err || (form == P2E_SIG_DER && !out_len) || (form == P2E_SIG_COMPACT65 && !v)) {
-        set_error("null pointer (r32, s32, out and err are all required, out_len with P2E_SIG_DER, v with P2E_SIG_COMPACT65)");
-        return P2E_E_INVALID;
-    }
+    // an argument its form does not use is ignored: v is COMPACT65's, out_len is DER's
+    const bool der = form == P2E_SIG_DER, with_v = form == P2E_SIG_COMPACT65;
+    if (!with_v) v = nullptr;
+    if (!der) out_len = nullptr;
+    const Args args = {ARG_IN(r32, 32, n),
+                       ARG_IN(s32, 32, n),
+                       ARG_IN_IF(with_v, v, 1, n),
+                       ARG_OUT(out, der ? P2E_SIG_DER_STRIDE : form == P2E_SIG_COMPACT64 ? 64 : 65, n),
+                       ARG_OUT_IF(der, out_len, 1, n),
+                       ARG_OUT(err, 1, n)};
+    if (missing(args, wire_sig_form_name(form))) return P2E_E_INVALID;
     if (flags != 0 && flags != P2E_SIG_NORMALIZE_S) {
         set_error("unknown flags (0 or P2E_SIG_NORMALIZE_S)");
         return P2E_E_INVALID;
     }
-    if (form != P2E_SIG_COMPACT65) v = nullptr;
-    if (form != P2E_SIG_DER) out_len = nullptr;
-    if (bad_overlap(n, {OV_IN(r32, 32, n), OV_IN(s32, 32, n), OV_IN(v, 1, n),
-                        OV_OUT(out, form == P2E_SIG_DER ? P2E_SIG_DER_STRIDE : form == P2E_SIG_COMPACT64 ? 64 : 65, n), OV_OUT(out_len, 1, n),
-                        OV_OUT(err, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
+    if (bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    r32 = S.in(r32, n * 32);
-    s32 = S.in(s32, n * 32);
-    v = S.in(v, n);
-    out = S.out(out, n * (form == P2E_SIG_DER ? P2E_SIG_DER_STRIDE : form == P2E_SIG_COMPACT64 ? 64 : 65));
-    out_len = S.out(out_len, n);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_sig_encode(c, curve, form, flags, r32, s32, v, out, out_len, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 #endif   // P2E_HAS(0)
 
@@ -2817,10 +2705,7 @@ template void launch_msm<P256>(p2e_ctx*, const MsmArgs&);
 
 #if P2E_HAS(0)
 static bool msm_bad_args(int curve, size_t n, unsigned window_bits) {
-    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
-        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
-        return true;
-    }
+    if (bad_curve(curve)) return true;
     if (window_bits != P2E_MSM_WINDOW_AUTO && (window_bits < P2E_MSM_WINDOW_MIN || window_bits > P2E_MSM_WINDOW_MAX)) {
         set_error("window_bits outside P2E_MSM_WINDOW_AUTO, [P2E_MSM_WINDOW_MIN, P2E_MSM_WINDOW_MAX]");
         return true;
@@ -2850,25 +2735,11 @@ extern "C" int p2e_point_msm_plan(int curve, size_t n, unsigned window_bits, uin
 }
 extern "C" long p2e_point_msm(p2e_ctx* c, int curve, unsigned window_bits, const uint8_t* k32, const uint8_t* px32, const uint8_t* py32,
                               size_t n, uint8_t* outx32, uint8_t* outy32, uint8_t* status, uint8_t* point_err) {
-    if (!k32 || !px32 || !py32 || !outx32 || !outy32 || !status) {
-        set_error("null pointer (k32, px32, py32, outx32, outy32 and status are all required; point_err may be null)");
-        return P2E_E_INVALID;
-    }
-    if (msm_bad_args(curve, n, window_bits)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_SHARED(k32, 32, n), OV_SHARED(px32, 32, n), OV_SHARED(py32, 32, n), OV_OUT(outx32, 32, 1), OV_OUT(outy32, 32, 1),
-                        OV_OUT(status, 1, 1), OV_OUT(point_err, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
+    const Args args = {ARG_SHARED(k32, 32, n), ARG_SHARED(px32, 32, n), ARG_SHARED(py32, 32, n),     ARG_OUT(outx32, 32, 1),
+                       ARG_OUT(outy32, 32, 1), ARG_OUT(status, 1, 1),   ARG_OUT_OPT(point_err, 1, n)};
+    if (missing(args) || msm_bad_args(curve, n, window_bits) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     const MsmPlan P = msm_plan(n, window_bits == P2E_MSM_WINDOW_AUTO ? msm_auto_window(n) : window_bits);
     Staged S(c);
-    k32 = S.in(k32, n * 32);
-    px32 = S.in(px32, n * 32);
-    py32 = S.in(py32, n * 32);
-    outx32 = S.out(outx32, 32);
-    outy32 = S.out(outy32, 32);
-    status = S.out(status, 1);
-    point_err = S.out(point_err, n);
-    if (S.rc) return S.done(S.rc);
     if (P.total > c->msm_bytes) {
         HIP_TRY(hipStreamSynchronize(c->stream));   // an earlier asynchronous call may still use the block that goes
         c->msm_bytes = 0;
@@ -2879,18 +2750,17 @@ extern "C" long p2e_point_msm(p2e_ctx* c, int curve, unsigned window_bits, const
         }
         c->msm_bytes = P.total;
     }
+    if (long rc = S.begin(args)) return rc;
     MsmArgs a = msm_args(P, c->d_msm.get());
     a.k32 = k32, a.px32 = px32, a.py32 = py32;
     a.outx32 = outx32, a.outy32 = outy32, a.status = status, a.point_err = point_err;
     a.counter = c->d_counter;
-    c->have_phases = false;
-    ZERO_COUNTER(c);
     HIP_TRY(hipMemsetAsync(c->d_msm.get(), 0, P.o_off, c->stream));   // meta, count, cursor
     if (curve == P2E_CURVE_P256)
         launch_msm<P256>(c, a);
     else
         launch_msm<Secp256k1>(c, a);
-    return S.done(finish_call(c));
+    return S.end();
 }
 #endif   // P2E_HAS(0)
 
@@ -2945,10 +2815,7 @@ static_assert(P2E_MUL_PLAN_AUTO == MUL_PLAN_AUTO && P2E_MUL_PLAN_PLAIN == MUL_PL
 // than PLAIN by far more than the spread at each measured size (MEASUREMENTS.md section 16: 0.83 of PLAIN's time at 2^12,
 // 0.84 at 2^16, 0.63 at 2^20), and below 2^12 the call is one wave's dependent chain, which GLV halves.  P-256 has PLAIN only.
 static int point_mul_prepare(int curve, unsigned plan, size_t n, int* chosen) {
-    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
-        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
-        return P2E_E_INVALID;
-    }
+    if (bad_curve(curve)) return P2E_E_INVALID;
     if (plan != P2E_MUL_PLAN_AUTO && plan != P2E_MUL_PLAN_PLAIN && plan != P2E_MUL_PLAN_GLV) {
         set_error("unknown plan (P2E_MUL_PLAN_AUTO, P2E_MUL_PLAN_PLAIN or P2E_MUL_PLAN_GLV)");
         return P2E_E_INVALID;
@@ -2957,102 +2824,61 @@ static int point_mul_prepare(int curve, unsigned plan, size_t n, int* chosen) {
         set_error("P2E_MUL_PLAN_GLV needs the endomorphism of secp256k1");
         return P2E_E_INVALID;
     }
-    if (n > ((size_t)1 << 31)) {
-        set_error("batch too large for one launch");
-        return P2E_E_INVALID;
-    }
+    if (batch_too_large(n)) return P2E_E_INVALID;
     *chosen = plan == P2E_MUL_PLAN_AUTO ? (curve == P2E_CURVE_SECP256K1 ? MUL_PLAN_GLV : MUL_PLAN_PLAIN) : (int)plan;
     return 0;
 }
 extern "C" long p2e_point_mul_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* k32, const uint8_t* px32, const uint8_t* py32,
                                     uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
-    if (!k32 || !px32 || !py32 || !outx32 || !outy32 || !err) {
-        set_error("null pointer (k32, px32, py32, outx32, outy32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(k32, 32, n),     ARG_IN(px32, 32, n),    ARG_IN(py32, 32, n),
+                       ARG_OUT(outx32, 32, n), ARG_OUT(outy32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     int chosen = 0;
     if (int rc = point_mul_prepare(curve, plan, n, &chosen)) return rc;
-    if (bad_overlap(n, {OV_IN(k32, 32, n), OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_OUT(outx32, 32, n), OV_OUT(outy32, 32, n),
-                        OV_OUT(err, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
+    if (bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    k32 = S.in(k32, n * 32);
-    px32 = S.in(px32, n * 32);
-    py32 = S.in(py32, n * 32);
-    outx32 = S.out(outx32, n * 32);
-    outy32 = S.out(outy32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     if (curve == P2E_CURVE_P256)
         launch_point_mul<P256>(c, chosen, nullptr, nullptr, k32, px32, py32, outx32, outy32, n, err);
     else
         launch_point_mul<Secp256k1>(c, chosen, nullptr, nullptr, k32, px32, py32, outx32, outy32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_point_lincomb_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* a32, const uint8_t* b32, const uint8_t* px32,
                                         const uint8_t* py32, uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
-    if (!a32 || !b32 || !px32 || !py32 || !outx32 || !outy32 || !err) {
-        set_error("null pointer (a32, b32, px32, py32, outx32, outy32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(a32, 32, n),     ARG_IN(b32, 32, n),     ARG_IN(px32, 32, n), ARG_IN(py32, 32, n),
+                       ARG_OUT(outx32, 32, n), ARG_OUT(outy32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     int chosen = 0, lane = 0;
     if (int rc = point_mul_prepare(curve, plan, n, &chosen)) return rc;
     const Aff* table = nullptr;
-    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &lane,
-                              {OV_IN(a32, 32, n), OV_IN(b32, 32, n), OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_OUT(outx32, 32, n),
-                               OV_OUT(outy32, 32, n), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = sign_prepare(c, curve, P2E_SIGN_PLAN_LANE, n, &table, &lane, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    a32 = S.in(a32, n * 32);
-    b32 = S.in(b32, n * 32);
-    px32 = S.in(px32, n * 32);
-    py32 = S.in(py32, n * 32);
-    outx32 = S.out(outx32, n * 32);
-    outy32 = S.out(outy32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     if (curve == P2E_CURVE_P256)
         launch_point_mul<P256>(c, chosen, table, a32, b32, px32, py32, outx32, outy32, n, err);
     else
         launch_point_mul<Secp256k1>(c, chosen, table, a32, b32, px32, py32, outx32, outy32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_point_add_batch(p2e_ctx* c, int curve, const uint8_t* px32, const uint8_t* py32, const uint8_t* qx32, const uint8_t* qy32,
                                     uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
-    if (!px32 || !py32 || !qx32 || !qy32 || !outx32 || !outy32 || !err) {
-        set_error("null pointer (px32, py32, qx32, qy32, outx32, outy32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(px32, 32, n),    ARG_IN(py32, 32, n),    ARG_IN(qx32, 32, n), ARG_IN(qy32, 32, n),
+                       ARG_OUT(outx32, 32, n), ARG_OUT(outy32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     int chosen = 0;
     if (int rc = point_mul_prepare(curve, P2E_MUL_PLAN_PLAIN, n, &chosen)) return rc;
-    if (bad_overlap(n, {OV_IN(px32, 32, n), OV_IN(py32, 32, n), OV_IN(qx32, 32, n), OV_IN(qy32, 32, n), OV_OUT(outx32, 32, n),
-                        OV_OUT(outy32, 32, n), OV_OUT(err, 1, n)}) ||
-        bad_ctx(c))
-        return P2E_E_INVALID;
+    if (bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    px32 = S.in(px32, n * 32);
-    py32 = S.in(py32, n * 32);
-    qx32 = S.in(qx32, n * 32);
-    qy32 = S.in(qy32, n * 32);
-    outx32 = S.out(outx32, n * 32);
-    outy32 = S.out(outy32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     if (curve == P2E_CURVE_P256)
         launch_point_add<P256>(c, px32, py32, qx32, qy32, outx32, outy32, n, err);
     else
         launch_point_add<Secp256k1>(c, px32, py32, qx32, qy32, outx32, outy32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 #endif   // P2E_HAS(0)
 
@@ -3112,36 +2938,22 @@ static_assert(P2E_WIRE_BAD_INDEX == WIRE_BAD_INDEX && P2E_POINT_TABLE_MAX_POINTS
               "include/p2e.h and point_table.hpp");
 // the stream's work done and the flagged count on the host, whatever the context's mode (create must count rejections)
 static long table_wait_count(p2e_ctx* c) {
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-        set_error(std::string("kernel launch: ") + hipGetErrorString(le));
-        return P2E_E_HIP;
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_counter, c->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (long r = fetch_count(c)) return r;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return (long)*c->h_counter;
 }
 extern "C" long p2e_point_table_create(p2e_ctx* c, int curve, const uint8_t* px32, const uint8_t* py32, size_t m, uint8_t* point_err,
                                        void** out) {
     if (out) *out = nullptr;
-    if (!px32 || !py32 || !out) {
-        set_error("null pointer (px32, py32 and out are all required; point_err may be null)");
-        return P2E_E_INVALID;
-    }
-    if (curve != P2E_CURVE_SECP256K1 && curve != P2E_CURVE_P256) {
-        set_error("unknown curve (P2E_CURVE_SECP256K1 or P2E_CURVE_P256)");
-        return P2E_E_INVALID;
-    }
+    // (each point's powers and rows are built by many lanes over two launches: nothing here is in place)
+    const Args args = {ARG_SHARED(px32, 32, m), ARG_SHARED(py32, 32, m), ARG_OUT_OPT(point_err, 1, m), ARG_OPAQUE(out)};
+    if (missing(args) || bad_curve(curve)) return P2E_E_INVALID;
     if (m < 1 || m > P2E_POINT_TABLE_MAX_POINTS) {
         set_error("a table holds 1 .. P2E_POINT_TABLE_MAX_POINTS points");
         return P2E_E_INVALID;
     }
-    // (each point's powers and rows are built by many lanes over two launches: nothing here is in place)
-    if (bad_overlap(m, {OV_SHARED(px32, 32, m), OV_SHARED(py32, 32, m), OV_OUT(point_err, 1, m)}) || bad_ctx(c)) return P2E_E_INVALID;
+    if (bad_overlap(m, args) || bad_ctx(c)) return P2E_E_INVALID;
     Staged S(c);   // (its guard puts the context's device in place and restores the caller's)
-    px32 = S.in(px32, m * 32);
-    py32 = S.in(py32, m * 32);
-    if (S.rc) return S.done(S.rc);
     std::unique_ptr<PointTable> t(new PointTable());
     t->curve = curve, t->device = c->device, t->m = m;
     const size_t rows = m * FB_WINDOWS, flag_off = (rows * TABLE_POW_BYTES + 3) & ~(size_t)3, err_off = flag_off + 4 * m;
@@ -3154,8 +2966,7 @@ extern "C" long p2e_point_table_create(p2e_ctx* c, int curve, const uint8_t* px3
     }
     u32* flag = reinterpret_cast<u32*>(scratch.get() + flag_off);
     uint8_t* perr = scratch.get() + err_off;
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     HIP_TRY(hipMemsetAsync(flag, 0, 4 * m, c->stream));
     if (curve == P2E_CURVE_P256)
         launch_table_powers<P256>(c, px32, py32, scratch.get(), m, perr);
@@ -3201,67 +3012,57 @@ extern "C" int p2e_point_table_read_window(p2e_ctx* c, const void* table, size_t
     HIP_TRY(hipMemcpy(out1024, t->tab.get() + (j * FB_WINDOWS + (size_t)w) * 16, 16 * sizeof(Aff), hipMemcpyDefault));
     return 0;
 }
-// what: as for launch_table_call; a = a32 / msg32 (null for what == 0), b = k32 / b32 / r32, s = s32 (what == 2 only),
-// out1 = outx32 / valid, out2 = outy32 (null for what == 2)
-static long table_call(p2e_ctx* c, const PointTable* t, int what, const uint32_t* idx, const uint8_t* a, const uint8_t* b,
-                       const uint8_t* s, uint8_t* out1, uint8_t* out2, size_t n, uint8_t* err) {
-    if (!t || !b || !out1 || !err || (what != 0 && !a) || (what == 2 ? !s : !out2)) {
-        set_error("null pointer (only idx may be null)");
-        return P2E_E_INVALID;
-    }
-    {   // the header's names of what a, b, s, out1 and out2 are in this call
-        static const char* const names[3][5] = {{"", "k32", "", "outx32", "outy32"},
-                                                {"a32", "b32", "", "outx32", "outy32"},
-                                                {"msg32", "r32", "s32", "valid", ""}};
-        const char* const* nm = names[what];
-        if (bad_overlap(n, {OV_IN(idx, 4, n), overlap::Span{nm[0], a, 32, n, false, false}, overlap::Span{nm[1], b, 32, n, false, false},
-                            overlap::Span{nm[2], s, 32, n, false, false}, overlap::Span{nm[3], out1, what == 2 ? (size_t)1 : (size_t)32, n, true, false},
-                            overlap::Span{nm[4], out2, 32, n, true, false}, OV_OUT(err, 1, n)}) ||
-            bad_ctx(c))
-            return P2E_E_INVALID;
-    }
+// The three calls that walk a table.  `args`: the caller's own list (table and idx in it); what: as for launch_table_call;
+// `launch(G, tab, m, curve_is_p256)`: the caller's launch_table_call with its own arguments, staged by then.
+template <class Launch>
+static long table_call(p2e_ctx* c, const void* table, int what, size_t n, Args args, Launch&& launch) {
+    if (missing(args) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
+    const PointTable* t = static_cast<const PointTable*>(table);
     if (t->device != c->device) {
         set_error("the table belongs to another device than the context");
         return P2E_E_INVALID;
     }
-    if (n > ((size_t)1 << 31)) {
-        set_error("batch too large for one launch");
-        return P2E_E_INVALID;
-    }
+    if (batch_too_large(n)) return P2E_E_INVALID;
     const Aff* G = nullptr;
     int lane = 0;
     if (what != 0)
         if (int rc = sign_prepare(c, t->curve, P2E_SIGN_PLAN_LANE, n, &G, &lane)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    idx = S.in(idx, n * 4);
-    a = S.in(a, n * 32);
-    b = S.in(b, n * 32);
-    s = S.in(s, n * 32);
-    out1 = S.out(out1, what == 2 ? n : n * 32);
-    out2 = S.out(out2, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
-    if (t->curve == P2E_CURVE_P256)
-        launch_table_call<P256>(c, what, G, t->tab.get(), idx, (u32)t->m, a, b, s, out1, out2, n, err);
-    else
-        launch_table_call<Secp256k1>(c, what, G, t->tab.get(), idx, (u32)t->m, a, b, s, out1, out2, n, err);
-    return S.done(finish_call(c));
+    if (long rc = S.begin(args)) return rc;
+    launch(G, t->tab.get(), (u32)t->m, t->curve == P2E_CURVE_P256);
+    return S.end();
 }
+// a = a32 / msg32 (null for what == 0), b = k32 / b32 / r32, s = s32 (what == 2 only), out1 = outx32 / valid, out2 = outy32
+#define TABLE_LAUNCH(what, a, b, s, out1, out2)                                                         \
+    [&](const Aff* G, const Aff* tab, u32 m, bool p256) {                                               \
+        if (p256)                                                                                       \
+            launch_table_call<P256>(c, what, G, tab, idx, m, a, b, s, out1, out2, n, err);              \
+        else                                                                                            \
+            launch_table_call<Secp256k1>(c, what, G, tab, idx, m, a, b, s, out1, out2, n, err);         \
+    }
 extern "C" long p2e_point_table_mul_batch(p2e_ctx* c, const void* table, const uint32_t* idx, const uint8_t* k32, uint8_t* outx32,
                                           uint8_t* outy32, size_t n, uint8_t* err) {
-    return table_call(c, static_cast<const PointTable*>(table), 0, idx, nullptr, k32, nullptr, outx32, outy32, n, err);
+    return table_call(c, table, 0, n,
+                      {ARG_OPAQUE(table), ARG_IN_OPT(idx, 4, n), ARG_IN(k32, 32, n), ARG_OUT(outx32, 32, n), ARG_OUT(outy32, 32, n),
+                       ARG_OUT(err, 1, n)},
+                      TABLE_LAUNCH(0, nullptr, k32, nullptr, outx32, outy32));
 }
 extern "C" long p2e_point_table_lincomb_batch(p2e_ctx* c, const void* table, const uint32_t* idx, const uint8_t* a32, const uint8_t* b32,
                                               uint8_t* outx32, uint8_t* outy32, size_t n, uint8_t* err) {
-    return table_call(c, static_cast<const PointTable*>(table), 1, idx, a32, b32, nullptr, outx32, outy32, n, err);
+    return table_call(c, table, 1, n,
+                      {ARG_OPAQUE(table), ARG_IN_OPT(idx, 4, n), ARG_IN(a32, 32, n), ARG_IN(b32, 32, n), ARG_OUT(outx32, 32, n),
+                       ARG_OUT(outy32, 32, n), ARG_OUT(err, 1, n)},
+                      TABLE_LAUNCH(1, a32, b32, nullptr, outx32, outy32));
 }
 extern "C" long p2e_ecdsa_verify_table_batch(p2e_ctx* c, const void* table, const uint32_t* idx, const uint8_t* msg32, const uint8_t* r32,
                                              const uint8_t* s32, size_t n, uint8_t* err, uint8_t* valid) {
-    return table_call(c, static_cast<const PointTable*>(table), 2, idx, msg32, r32, s32, valid, nullptr, n, err);
+    return table_call(c, table, 2, n,
+                      {ARG_OPAQUE(table), ARG_IN_OPT(idx, 4, n), ARG_IN(msg32, 32, n), ARG_IN(r32, 32, n), ARG_IN(s32, 32, n),
+                       ARG_OUT(valid, 1, n), ARG_OUT(err, 1, n)},
+                      TABLE_LAUNCH(2, msg32, r32, s32, valid, nullptr));
 }
+#undef TABLE_LAUNCH
 #endif   // P2E_HAS(0)
 
 // ====================================================================================================
@@ -3331,95 +3132,53 @@ void launch_schnorr_agg_verdict(p2e_ctx* c, const SchnorrAggLayout& L, const uns
 
 #if P2E_HAS(0)
 // the generator's table; n beyond one launch is refused (sign_prepare's rule)
-static int schnorr_prepare(p2e_ctx* c, size_t n, const Aff** table, std::initializer_list<overlap::Span> spans) {
+static int schnorr_prepare(p2e_ctx* c, size_t n, const Aff** table, Args args) {
     int lane = 0;
-    return sign_prepare(c, P2E_CURVE_SECP256K1, P2E_SIGN_PLAN_LANE, n, table, &lane, spans);
+    return sign_prepare(c, P2E_CURVE_SECP256K1, P2E_SIGN_PLAN_LANE, n, table, &lane, args);
 }
 extern "C" long p2e_schnorr_public_key_batch(p2e_ctx* c, const uint8_t* sk32, uint8_t* pk32, size_t n, uint8_t* err) {
-    if (!sk32 || !pk32 || !err) {
-        set_error("null pointer (sk32, pk32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(sk32, 32, n), ARG_OUT(pk32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table, {OV_IN(sk32, 32, n), OV_OUT(pk32, 32, n), OV_OUT(err, 1, n)})) return rc;
+    if (int rc = schnorr_prepare(c, n, &table, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    sk32 = S.in(sk32, n * 32);
-    pk32 = S.out(pk32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_schnorr_public_key(c, table, sk32, pk32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_schnorr_sign_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* sk32, const uint8_t* aux32, uint8_t* sig64, size_t n,
                                        uint8_t* err) {
-    if (!msg32 || !sk32 || !aux32 || !sig64 || !err) {
-        set_error("null pointer (msg32, sk32, aux32, sig64 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(msg32, 32, n), ARG_IN(sk32, 32, n), ARG_IN(aux32, 32, n), ARG_OUT(sig64, 64, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table,
-                                 {OV_IN(msg32, 32, n), OV_IN(sk32, 32, n), OV_IN(aux32, 32, n), OV_OUT(sig64, 64, n), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = schnorr_prepare(c, n, &table, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    msg32 = S.in(msg32, n * 32);
-    sk32 = S.in(sk32, n * 32);
-    aux32 = S.in(aux32, n * 32);
-    sig64 = S.out(sig64, n * 64);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_schnorr_sign(c, table, msg32, sk32, aux32, sig64, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_schnorr_verify_batch(p2e_ctx* c, const uint8_t* msg32, const uint8_t* pk32, const uint8_t* sig64, size_t n, uint8_t* err,
                                          uint8_t* valid) {
-    if (!msg32 || !pk32 || !sig64 || !err || !valid) {
-        set_error("null pointer (msg32, pk32, sig64, err and valid are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(msg32, 32, n), ARG_IN(pk32, 32, n), ARG_IN(sig64, 64, n), ARG_OUT(err, 1, n), ARG_OUT(valid, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table,
-                                 {OV_IN(msg32, 32, n), OV_IN(pk32, 32, n), OV_IN(sig64, 64, n), OV_OUT(err, 1, n), OV_OUT(valid, 1, n)}))
-        return rc;
+    if (int rc = schnorr_prepare(c, n, &table, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    msg32 = S.in(msg32, n * 32);
-    pk32 = S.in(pk32, n * 32);
-    sig64 = S.in(sig64, n * 64);
-    err = S.out(err, n);
-    valid = S.out(valid, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_schnorr_verify(c, table, msg32, pk32, sig64, n, err, valid);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_xonly_decode_batch(p2e_ctx* c, const uint8_t* pk32, uint8_t* px32, uint8_t* py32, size_t n, uint8_t* err) {
-    if (!pk32 || !px32 || !py32 || !err) {
-        set_error("null pointer (pk32, px32, py32 and err are all required)");
-        return P2E_E_INVALID;
-    }
-    if (n > ((size_t)1 << 31)) {
-        set_error("batch too large for one launch");
-        return P2E_E_INVALID;
-    }
-    if (bad_overlap(n, {OV_IN(pk32, 32, n), OV_OUT(px32, 32, n), OV_OUT(py32, 32, n), OV_OUT(err, 1, n)}) || bad_ctx(c)) return P2E_E_INVALID;
+    const Args args = {ARG_IN(pk32, 32, n), ARG_OUT(px32, 32, n), ARG_OUT(py32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args) || batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    pk32 = S.in(pk32, n * 32);
-    px32 = S.out(px32, n * 32);
-    py32 = S.out(py32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_xonly_decode(c, pk32, px32, py32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 // `have` bytes of `block` become at least `want`, behind a stream sync: an earlier asynchronous call may still use the block that goes
 static long schnorr_grow(p2e_ctx* c, DeviceArray<unsigned char>& block, size_t& have, size_t want) {
@@ -3436,10 +3195,9 @@ static long schnorr_grow(p2e_ctx* c, DeviceArray<unsigned char>& block, size_t& 
 }
 extern "C" long p2e_schnorr_verify_aggregate(p2e_ctx* c, const uint8_t* msg32, const uint8_t* pk32, const uint8_t* sig64, size_t n,
                                              const uint8_t* seed32, unsigned window_bits, uint8_t* verdict, uint8_t* err) {
-    if (!msg32 || !pk32 || !sig64 || !seed32 || !verdict) {
-        set_error("null pointer (msg32, pk32, sig64, seed32 and verdict are all required; err may be null)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_SHARED(msg32, 32, n),  ARG_SHARED(pk32, 32, n), ARG_SHARED(sig64, 64, n),
+                       ARG_SHARED(seed32, 32, 1), ARG_OUT(verdict, 1, 1),  ARG_OUT_OPT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     if (n > MSM_MAX_N / 2) {   // 2 n + 1 > 2^24, without the overflow of 2 n
         set_error("batch too large for one sum (2 n + 1 terms, at most 2^24)");
         return P2E_E_INVALID;
@@ -3447,41 +3205,28 @@ extern "C" long p2e_schnorr_verify_aggregate(p2e_ctx* c, const uint8_t* msg32, c
     const size_t terms = 2 * n + 1;
     if (msm_bad_args(P2E_CURVE_SECP256K1, terms, window_bits)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table,
-                                 {OV_SHARED(msg32, 32, n), OV_SHARED(pk32, 32, n), OV_SHARED(sig64, 64, n), OV_SHARED(seed32, 32, 1),
-                                  OV_OUT(verdict, 1, 1), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = schnorr_prepare(c, n, &table, args)) return rc;
     Staged S(c);
-    verdict = S.out(verdict, 1);
     if (n == 0) {   // the empty batch holds: nothing to sum
-        if (S.rc) return S.done(S.rc);
-        c->have_phases = false;
-        ZERO_COUNTER(c);
+        if (long rc = S.begin(args)) return rc;
         HIP_TRY(hipMemsetAsync(verdict, 1, 1, c->stream));
-        return S.done(finish_call(c));
+        return S.end();
     }
-    msg32 = S.in(msg32, n * 32);
-    pk32 = S.in(pk32, n * 32);
-    sig64 = S.in(sig64, n * 64);
-    seed32 = S.in(seed32, 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
     const MsmPlan P = msm_plan(terms, window_bits == P2E_MSM_WINDOW_AUTO ? msm_auto_window(terms) : window_bits);
     const SchnorrAggLayout L(n);
     if (long rc = schnorr_grow(c, c->d_schnorr, c->schnorr_bytes, L.total)) return S.done(rc);
     if (long rc = schnorr_grow(c, c->d_msm, c->msm_bytes, P.total)) return S.done(rc);
+    if (long rc = S.begin(args)) return rc;
     unsigned char* block = c->d_schnorr.get();
     MsmArgs a = msm_args(P, c->d_msm.get());
     a.k32 = block + L.o_k, a.px32 = block + L.o_px, a.py32 = block + L.o_py;
     a.outx32 = block + L.o_outx, a.outy32 = block + L.o_outy, a.status = block + L.o_status, a.point_err = nullptr;
     a.counter = reinterpret_cast<unsigned long long*>(block + L.o_rejected);   // (the context's counter holds the flag count)
-    c->have_phases = false;
-    ZERO_COUNTER(c);
     HIP_TRY(hipMemsetAsync(c->d_msm.get(), 0, P.o_off, c->stream));   // meta, count, cursor
     launch_schnorr_agg_prepare(c, table, L, block, msg32, pk32, sig64, seed32, n, err);
     launch_msm<Secp256k1>(c, a);
     launch_schnorr_agg_verdict(c, L, block, verdict);
-    return S.done(finish_call(c));
+    return S.end();
 }
 #endif   // P2E_HAS(0)
 
@@ -3537,127 +3282,71 @@ static bool bip32_bad_parents(size_t n_parents, size_t n) {
     return true;
 }
 extern "C" long p2e_bip32_master_batch(p2e_ctx* c, const uint8_t* seed, size_t seed_len, uint8_t* sk32, uint8_t* cc32, size_t n, uint8_t* err) {
-    if (!seed || !sk32 || !cc32 || !err) {
-        set_error("null pointer (seed, sk32, cc32 and err are all required)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(seed, seed_len, n), ARG_OUT(sk32, 32, n), ARG_OUT(cc32, 32, n), ARG_OUT(err, 1, n)};
+    if (missing(args)) return P2E_E_INVALID;
     if (seed_len < 16 || seed_len > 64) {
         set_error("seed_len must be 16 .. 64 bytes");
         return P2E_E_INVALID;
     }
-    if (hash_batch_too_large(n)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_IN(seed, seed_len, n), OV_OUT(sk32, 32, n), OV_OUT(cc32, 32, n), OV_OUT(err, 1, n)}) || bad_ctx(c))
-        return P2E_E_INVALID;
+    if (batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    seed = S.in(seed, n * seed_len);
-    sk32 = S.out(sk32, n * 32);
-    cc32 = S.out(cc32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_bip32_master(c, seed, seed_len, sk32, cc32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_bip32_ckd_priv_batch(p2e_ctx* c, const uint8_t* par_sk32, const uint8_t* par_cc32, size_t n_parents, const uint32_t* index,
                                          uint8_t* sk32, uint8_t* cc32, size_t n, uint8_t* err) {
-    if (!par_sk32 || !par_cc32 || !index || !sk32 || !cc32 || !err) {
-        set_error("null pointer (par_sk32, par_cc32, index, sk32, cc32 and err are all required)");
-        return P2E_E_INVALID;
-    }
-    if (bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
+    const Args args = {ARG_BCAST(par_sk32, 32, n_parents), ARG_BCAST(par_cc32, 32, n_parents), ARG_IN(index, 4, n),
+                       ARG_OUT(sk32, 32, n),               ARG_OUT(cc32, 32, n),               ARG_OUT(err, 1, n)};
+    if (missing(args) || bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table,   // (the generator's table of secp256k1, lane plan)
-                                 {OV_BCAST(par_sk32, 32, n_parents, n), OV_BCAST(par_cc32, 32, n_parents, n), OV_IN(index, 4, n),
-                                  OV_OUT(sk32, 32, n), OV_OUT(cc32, 32, n), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = schnorr_prepare(c, n, &table, args)) return rc;   // (the generator's table of secp256k1, lane plan)
     if (n == 0) return 0;
     Staged S(c);
-    par_sk32 = S.in(par_sk32, n_parents * 32);
-    par_cc32 = S.in(par_cc32, n_parents * 32);
-    index = S.in(index, n * sizeof(uint32_t));
-    sk32 = S.out(sk32, n * 32);
-    cc32 = S.out(cc32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_bip32_ckd_priv(c, table, par_sk32, par_cc32, n_parents != n, index, sk32, cc32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_bip32_ckd_pub_batch(p2e_ctx* c, const uint8_t* par_pkx32, const uint8_t* par_pky32, const uint8_t* par_cc32,
                                         size_t n_parents, const uint32_t* index, uint8_t* pkx32, uint8_t* pky32, uint8_t* cc32, size_t n,
                                         uint8_t* err) {
-    if (!par_pkx32 || !par_pky32 || !par_cc32 || !index || !pkx32 || !pky32 || !cc32 || !err) {
-        set_error("null pointer (par_pkx32, par_pky32, par_cc32, index, pkx32, pky32, cc32 and err are all required)");
-        return P2E_E_INVALID;
-    }
-    if (bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
+    const Args args = {ARG_BCAST(par_pkx32, 32, n_parents), ARG_BCAST(par_pky32, 32, n_parents), ARG_BCAST(par_cc32, 32, n_parents),
+                       ARG_IN(index, 4, n),                 ARG_OUT(pkx32, 32, n),               ARG_OUT(pky32, 32, n),
+                       ARG_OUT(cc32, 32, n),                ARG_OUT(err, 1, n)};
+    if (missing(args) || bip32_bad_parents(n_parents, n)) return P2E_E_INVALID;
     const Aff* table = nullptr;
-    if (int rc = schnorr_prepare(c, n, &table,
-                                 {OV_BCAST(par_pkx32, 32, n_parents, n), OV_BCAST(par_pky32, 32, n_parents, n),
-                                  OV_BCAST(par_cc32, 32, n_parents, n), OV_IN(index, 4, n), OV_OUT(pkx32, 32, n), OV_OUT(pky32, 32, n),
-                                  OV_OUT(cc32, 32, n), OV_OUT(err, 1, n)}))
-        return rc;
+    if (int rc = schnorr_prepare(c, n, &table, args)) return rc;
     if (n == 0) return 0;
     Staged S(c);
-    par_pkx32 = S.in(par_pkx32, n_parents * 32);
-    par_pky32 = S.in(par_pky32, n_parents * 32);
-    par_cc32 = S.in(par_cc32, n_parents * 32);
-    index = S.in(index, n * sizeof(uint32_t));
-    pkx32 = S.out(pkx32, n * 32);
-    pky32 = S.out(pky32, n * 32);
-    cc32 = S.out(cc32, n * 32);
-    err = S.out(err, n);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_bip32_ckd_pub(c, table, par_pkx32, par_pky32, par_cc32, n_parents != n, index, pkx32, pky32, cc32, n, err);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_key_hash160_batch(p2e_ctx* c, unsigned form, const uint8_t* pkx32, const uint8_t* pky32, const uint8_t* err_in,
                                       uint8_t* out20, size_t n) {
-    if (!pkx32 || !pky32 || !out20) {
-        set_error("null pointer (pkx32, pky32 and out20 are all required; err_in may be null)");
-        return P2E_E_INVALID;
-    }
+    const Args args = {ARG_IN(pkx32, 32, n), ARG_IN(pky32, 32, n), ARG_IN_OPT(err_in, 1, n), ARG_OUT(out20, 20, n)};
+    if (missing(args)) return P2E_E_INVALID;
     if (form != P2E_SEC1_COMPRESSED && form != P2E_SEC1_UNCOMPRESSED) {
         set_error("unknown form (P2E_SEC1_COMPRESSED or P2E_SEC1_UNCOMPRESSED)");
         return P2E_E_INVALID;
     }
-    if (hash_batch_too_large(n)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_IN(pkx32, 32, n), OV_IN(pky32, 32, n), OV_IN(err_in, 1, n), OV_OUT(out20, 20, n)}) || bad_ctx(c))
-        return P2E_E_INVALID;
+    if (batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    pkx32 = S.in(pkx32, n * 32);
-    pky32 = S.in(pky32, n * 32);
-    err_in = S.in(err_in, n);
-    out20 = S.out(out20, n * 20);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (long rc = S.begin(args)) return rc;
     launch_key_hash160(c, form, pkx32, pky32, err_in, out20, n);
-    return S.done(finish_call(c));
+    return S.end();
 }
 extern "C" long p2e_hash160_batch(p2e_ctx* c, const uint8_t* data, const uint64_t* offsets, uint8_t* out20, size_t n) {
-    if (!data || !offsets || !out20) {
-        set_error("null pointer (data, offsets and out20 are all required)");
-        return P2E_E_INVALID;
-    }
-    if (hash_batch_too_large(n)) return P2E_E_INVALID;
-    if (bad_overlap(n, {OV_IN(offsets, 8, n + 1), OV_OUT(out20, 20, n)}) || bad_ctx(c)) return P2E_E_INVALID;
+    const Args args = {ARG_OPAQUE(data), ARG_IN(offsets, 8, n + 1), ARG_OUT(out20, 20, n)};
+    if (missing(args) || batch_too_large(n) || bad_overlap(n, args) || bad_ctx(c)) return P2E_E_INVALID;
     if (n == 0) return 0;
     Staged S(c);
-    if (!wire_stage_elements(S, data, offsets, n, {OV_OUT(out20, 20, n)})) return S.done(P2E_E_INVALID);
-    offsets = S.in(offsets, (n + 1) * sizeof(uint64_t));
-    out20 = S.out(out20, n * 20);
-    if (S.rc) return S.done(S.rc);
-    c->have_phases = false;
-    ZERO_COUNTER(c);
+    if (!wire_stage_elements(S, args, data, offsets, n)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
     launch_hash160(c, data, offsets, out20, n);
-    return S.done(finish_call(c));
+    return S.end();
 }
 #endif   // P2E_HAS(0)
 

@@ -12,6 +12,7 @@
 import ctypes as C
 import itertools
 import os
+import re
 import subprocess
 import sys
 
@@ -131,6 +132,94 @@ def test_overlap_selftest_agrees_with_python_integers(tmp_path):
     assert subprocess.run([prog, str(path)], capture_output=True).returncode == 1
 
 
+# ---- 1b. csrc/call_args.hpp alone: one buffer list, its null text, its spans and what it stages ---------------------------------
+ROLES = {"in": 0, "out": 1, "shared": 2, "bcast": 3, "opaque": 4}
+
+
+def buffer_lists():
+    """(lanes, [(name, ptr, bytes_per_element, count, role, required)], form): lists shaped like the library's, n = 5; form:
+    the name of the call's form where its list depends on one (the wire signatures), else None."""
+    n, at = 5, lambda k: 0x7000_0000_0000 + 4096 * k
+    req = lambda name, k, bpe, count, role: (name, at(k), bpe, count, role, 1)
+    # an optional buffer, given and not given (sign_deterministic's v)
+    for v in (at(3), 0):
+        yield n, [req("msg32", 1, 32, n, "in"), req("r32", 2, 32, n, "out"), ("v", v, 1, n, "out", 0), req("err", 4, 1, n, "out")], None
+    # counts of n + 1, n and 1 (hash_batch's offsets; the single sum of point_msm beside its per-point flags)
+    yield n, [req("data", 1, 0, 0, "opaque"), req("offsets", 2, 8, n + 1, "in"), req("out32", 3, 32, n, "out")], None
+    yield n, [req("k32", 1, 32, n, "shared"), req("outx32", 2, 32, 1, "out"), req("status", 3, 1, 1, "out"),
+              ("point_err", at(4), 1, n, "out", 0)], None
+    # the parents of a BIP-32 call: one for all lanes (broadcast), one per lane, and one lane with its one parent
+    for n_parents, lanes in ((1, n), (n, n), (1, 1)):
+        yield lanes, [req("par_sk32", 1, 32, n_parents, "bcast"), req("index", 2, 4, lanes, "in"), req("sk32", 3, 32, lanes, "out")], None
+    # a zero count: no span, and nothing but an empty copy to stage
+    yield 0, [req("sk32", 1, 32, 0, "in"), req("pk32", 2, 32, 0, "out"), req("seed32", 3, 32, 1, "shared")], None
+    # missing pointers: every required name, every optional one behind the semicolon; one name alone
+    yield n, [("a32", 0, 32, n, "in", 1), req("b32", 2, 32, n, "in"), ("idx", 0, 4, n, "in", 0), ("err", 0, 1, n, "out", 1),
+              ("point_err", at(5), 1, n, "out", 0)], None
+    yield n, [("plan", 0, 8, 6, "out", 1)], None
+    yield n, [("table", 0, 0, 0, "opaque", 1), ("idx", 0, 4, n, "in", 0), req("k32", 3, 32, n, "in")], "FORM_X"
+    yield n, [], None
+
+
+def expected_of_list(k, lanes, bufs, form=None):
+    join = lambda v: v[0] if len(v) == 1 else ", ".join(v[:-1]) + " and " + v[-1]
+    need, may = [b[0] for b in bufs if b[5]], [b[0] for b in bufs if not b[5]]
+    text = "-"
+    if any(b[5] and b[1] == 0 for b in bufs):
+        text = "null pointer (" + join(need) + (" is required" if len(need) == 1 else " are all required")
+        text += f" with {form}" if form else ""
+        text += ("; " + join(may) + " may be null" if may else "") + ")"
+    lines, staged, slots = [f"list {k}", f"missing {text}"], [], []
+    for name, ptr, bpe, count, role, _req in bufs:
+        if role != "opaque" and ptr and count:
+            broadcast = role == "shared" or (role == "bcast" and count == 1 and lanes > 1)
+            lines.append(f"span {name} {ptr} {bpe} {count} {int(role == 'out')} {int(broadcast)}")
+    for name, ptr, bpe, count, role, _req in bufs:
+        if role != "opaque" and ptr:
+            slots.append(f"slot {name} {0xD0000000 + 256 * (len(staged) + 1)}")
+            staged.append(f"stage {name} {'out' if role == 'out' else 'in'} {bpe * count}")
+        else:
+            slots.append(f"slot {name} {ptr}")
+    return lines + staged + slots
+
+
+def test_one_buffer_list_gives_the_null_text_the_spans_and_the_staged_bytes(tmp_path):
+    prog = os.path.join(HERE, "overlap_selftest")
+    subprocess.check_call(["make", "-s", "-C", HERE])
+    cases = list(buffer_lists())
+    path = tmp_path / "lists.txt"
+    with open(path, "w") as f:
+        for lanes, bufs, form in cases:
+            f.write(" ".join([form or "-", str(lanes), str(len(bufs))] + [f"{b[0]} {b[1]} {b[2]} {b[3]} {ROLES[b[4]]} {b[5]}" for b in bufs]) + "\n")
+    r = subprocess.run([prog, "--lists", str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    want = [line for k, case in enumerate(cases) for line in expected_of_list(k, *case)]
+    assert r.stdout.splitlines() == want
+    # the cases hold what they are meant to: a broadcast parent and a plain one, an optional null, a zero count, one name alone
+    out = r.stdout
+    assert "span par_sk32 %d 32 1 0 1" % (0x7000_0000_0000 + 4096) in out and "span par_sk32 %d 32 5 0 0" % (0x7000_0000_0000 + 4096) in out
+    assert "span par_sk32 %d 32 1 0 0" % (0x7000_0000_0000 + 4096) in out and "stage sk32 in 0" in out and "stage offsets in 48" in out
+    assert "missing null pointer (plan is required)" in out
+    assert "missing null pointer (a32, b32 and err are all required; idx and point_err may be null)" in out
+    assert "missing null pointer (table and k32 are all required with FORM_X; idx may be null)" in out
+    # every buffer that has both: the bytes staged are the bytes the span covers
+    span, stage, k = {}, {}, -1
+    for line in out.splitlines():
+        w = line.split()
+        if w[0] == "list":
+            k = int(w[1])
+        elif w[0] == "span":
+            span[(k, w[1])] = int(w[3]) * int(w[4])
+        elif w[0] == "stage":
+            stage[(k, w[1])] = int(w[3])
+    assert len(span) > 20 and all(stage[key] == b for key, b in span.items())
+    assert all(key in span or b == 0 for key, b in stage.items())
+    # a list the program cannot read is an error, not an empty success
+    with open(path, "w") as f:
+        f.write("- 5 1 msg32 4096 32 5 9 1\n")
+    assert subprocess.run([prog, "--lists", str(path)], capture_output=True).returncode == 2
+
+
 # ---- 2. the entry points -----------------------------------------------------------------------------------------------------
 N = 4
 # One row per per-element call: its arguments behind ctx, in the header's order.
@@ -180,6 +269,20 @@ CALLS = {
     "p2e_bip32_ckd_pub_batch": [[("bcast", 32), ("bcast", 32), ("bcast", 32), ("np",), ("in", 4, "n"), OUT32, OUT32, OUT32, ("n",), ERR]],
     "p2e_key_hash160_batch": [[0, IN32, IN32, ("in", 1, "n"), ("out", 20, "n"), ("n",)]],
     "p2e_hash160_batch": [[("free",), ("in", 8, "n+1"), ("out", 20, "n"), ("n",)]],
+}
+# the pointer arguments a call may be given as NULL (include/p2e.h); every other pointer of a row is required, the "free" and
+# "slot" ones included.  ("off" arguments are not the form's own: they are NULL in every run.)
+OPTIONAL = {
+    "p2e_ecdsa_sign_deterministic_batch": {"v"},
+    "p2e_eth_address_batch": {"err"},
+    "p2e_sig_decode_batch": {"v"},
+    "p2e_point_msm": {"point_err"},
+    "p2e_point_table_create": {"point_err"},
+    "p2e_point_table_mul_batch": {"idx"},
+    "p2e_point_table_lincomb_batch": {"idx"},
+    "p2e_ecdsa_verify_table_batch": {"idx"},
+    "p2e_schnorr_verify_aggregate": {"err"},
+    "p2e_key_hash160_batch": {"err_in"},
 }
 # exact in place, as the header lists it: (output, input) by argument name
 ALLOWED = {
@@ -290,7 +393,7 @@ class Call:
             elif spec[0] == "off":
                 args.append(None)
             elif spec[0] == "slot":
-                args.append(C.c_void_p(self.slot.ctypes.data))
+                args.append(C.c_void_p(moved.get(k, self.slot.ctypes.data)))
             else:
                 args.append(C.c_void_p(moved.get(k, self.base[k])))
         rc = getattr(L, self.name)(*args)
@@ -324,6 +427,30 @@ def test_disjoint_arguments_pass_the_check_and_meet_the_null_context():
     for name in ("p2e_bip32_ckd_priv_batch", "p2e_bip32_ckd_pub_batch"):       # one parent, in its own bytes
         rc, msg = Call(name, CALLS[name][0], n_parents=1).run(None)
         assert rc == -1 and msg == "null context", (name, msg)
+
+
+def test_a_null_required_pointer_is_named_and_a_null_optional_one_is_accepted():
+    """Every pointer of every form, NULL in turn, with a null context: a required one is refused by name, an optional one gets
+    as far as the context's own null test.  Each run follows an accepted one, so the text read is the refused call's own."""
+    required = optional = 0
+    assert set(OPTIONAL) <= set(CALLS)
+    for name, row in all_forms():
+        call = Call(name, row)
+        pointers = call.positions("in", "out", "shared", "bcast", "free", "slot")
+        assert OPTIONAL.get(name, set()) <= {call.pnames[k] for k in call.positions("in", "out", "shared", "bcast", "free", "slot", "off")}
+        for k in pointers:
+            pname = call.pnames[k]
+            assert call.run(None) == (-1, "null context"), name
+            rc, msg = call.run(None, {k: 0})
+            if pname in OPTIONAL.get(name, ()):
+                assert rc == -1 and msg == "null context", (name, pname, msg)
+                optional += 1
+            else:
+                assert rc == -1 and msg.startswith("null pointer ("), (name, pname, msg)
+                assert pname in re.findall(r"\w+", msg.split(";")[0]), (name, pname, msg)
+                required += 1
+            assert not call.arena.any() and not call.slot.any()
+    assert required > 150 and optional >= 10
 
 
 def test_every_output_shifted_onto_an_input_is_refused(fake):
