@@ -21,8 +21,8 @@
  *
  * BUFFER OVERLAP
  *   What a call may be handed when an output buffer shares bytes with another argument.  The rule below holds for the
- *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_hash160_batch (keys, signing, recovery,
- *   hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32) and the two verdict-only
+ *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_taproot_verify_commitment_batch (keys, signing,
+ *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, Taproot) and the two verdict-only
  *   verifiers p2e_ecdsa_verify_batch and p2e_p256_verify_batch.  It is checked on the host, behind the call's other argument
  *   checks and before the context is looked at, and it is the same with P2E_CTX_HOST_POINTERS (staging would hide the race;
  *   the contract does not depend on the mode).
@@ -41,6 +41,8 @@
  *        p2e_schnorr_public_key_batch          pk32 = sk32;    p2e_xonly_decode_batch          px32 = pk32
  *        p2e_bip32_ckd_priv_batch, p2e_bip32_ckd_pub_batch with n_parents == n: the children over the parents (sk32 = par_sk32,
  *            pkx32 = par_pkx32, pky32 = par_pky32, cc32 = par_cc32) -- how a path is deepened level by level
+ *        p2e_taproot_tweak_pubkey_batch        out_pk32 = pk32;   p2e_taproot_tweak_seckey_batch   out_sk32 = sk32
+ *        p2e_taproot_merkle_root_batch         root32 = leaf32
  *   3. Any other intersection of an output with an input is P2E_E_INVALID, with "overlap" and the two argument names in
  *      p2e_last_error(): a shifted overlap (out == in + 32), different bytes per element (r32 on the 64-byte data of
  *      P2E_SIG_COMPACT64, addr20 on pkx32), and every input that lanes other than "its own" read -- the single parent of a
@@ -978,6 +980,60 @@ long p2e_bip32_ckd_pub_batch(p2e_ctx *ctx, const uint8_t *par_pkx32, const uint8
 long p2e_key_hash160_batch(p2e_ctx *ctx, unsigned form, const uint8_t *pkx32, const uint8_t *pky32,
                            const uint8_t *err_in /* nullable */, uint8_t *out20, size_t n);
 long p2e_hash160_batch(p2e_ctx *ctx, const uint8_t *data, const uint64_t *offsets, uint8_t *out20, size_t n);
+
+/* ---- Taproot (BIP-341) on secp256k1 (csrc/taproot.hpp): what lies between an x-only key and a BIP-340 signature.  An
+ * xpub scan on the device (p2e_bip32_ckd_pub_batch) becomes Taproot output keys -- with p2e_point_encode_batch /
+ * p2e_key_hash160_batch the witness programs --, a derived secret key becomes the key p2e_schnorr_sign_batch signs a
+ * key-path spend with, and a batch of script-path spends is checked against its output keys, without visiting the host.
+ *   count    The batch size of these five calls is named `count`, NOT `n`, on purpose: tests/test_overlap_cpu.py derives its
+ *            list of per-element calls from the declarations that return long and have a parameter named n or m, and keeps
+ *            one row per call in a table of its own; these calls carry their span table in tests/test_taproot_cpu.py until
+ *            the rows are folded in (and the parameter renamed).  BUFFER OVERLAP (top of this file) holds for them in full.
+ *   bytes    as for the Schnorr calls: every key, hash and tweak is the standard's BIG-endian 32-byte string, element i at
+ *            +32 i, every array 4-byte aligned -- but `script` (any alignment; read as p2e_hash_batch reads its data: aligned
+ *            4-byte words, and only words that hold a byte of the lane's own script) and the one-byte arrays.
+ *   tagged hashes   H_tag(x) = SHA256(SHA256(tag) || SHA256(tag) || x) for "TapLeaf", "TapBranch" and "TapTweak".
+ *   err[i]   a P2E_WIRE_* CODE: the first failing check in the order given below; a flagged element writes zeros to all its
+ *            outputs.  The return value counts the flagged elements; count == 0 returns 0.  Null pointers, host pointers,
+ *            async mode, the current device and failed calls behave as for the Schnorr calls.  In place, exactly:
+ *            out_pk32 = pk32, out_sk32 = sk32 and root32 = leaf32 are fine (every body reads all of element i's inputs
+ *            before its first store); every other overlap of an output is refused as BUFFER OVERLAP says.
+ *   p2e_taproot_leaf_hash_batch   script i = script[offsets[i], offsets[i + 1]).  In order: leaf_version[i] odd:
+ *            P2E_WIRE_BAD_PREFIX (bit 0 is the control block's parity bit); offsets[i + 1] < offsets[i] or a length >= 2^32:
+ *            P2E_WIRE_BAD_LENGTH.  Otherwise leaf32 = H_TapLeaf(version || compact_size(length) || script), the compact
+ *            size being one byte below 253, fd + 2 little-endian bytes up to 0xffff, fe + 4 bytes above.  With host
+ *            pointers the bytes script[offsets[0], offsets[count]) are staged, as for p2e_hash_batch.
+ *   p2e_taproot_merkle_root_batch   node j of element i is at path32 + 32 (i max_depth + j), j < depth[i].  max_depth > 128
+ *            is P2E_E_INVALID; with max_depth == 0 path32 may be null.  depth[i] > max_depth: P2E_WIRE_BAD_LENGTH.
+ *            k = leaf; for each node e: k = H_TapBranch(min(k, e) || max(k, e)), compared as 32-byte strings; root32 = k
+ *            (the leaf itself at depth 0).  Two compressions per level.
+ *   p2e_taproot_tweak_pubkey_batch   BIP-341 taproot_tweak_pubkey.  In order: pk >= p: P2E_WIRE_COORD_RANGE; pk^3 + 7 not a
+ *            square: P2E_WIRE_NOT_ON_CURVE; t = int(H_TapTweak(pk || root)) -- with root32 == NULL nothing is appended: the
+ *            key-path-only output of BIP-86 --, t >= n: P2E_WIRE_SCALAR_RANGE (not reduced); Q = lift_x(pk) + t G, the
+ *            neutral element: P2E_WIRE_INFINITY.  out_pk32 = bytes(x(Q)), out_parity = y(Q) & 1.  t G = P (a doubling) and
+ *            t = 0 are computed, not flagged.
+ *   p2e_taproot_tweak_seckey_batch   BIP-341 taproot_tweak_seckey.  d = 0 or d >= n: P2E_WIRE_SCALAR_RANGE; P = d G,
+ *            d := n - d where P.y is odd; t as above over bytes(P.x), t >= n: P2E_WIRE_SCALAR_RANGE; out_sk = (d + t) mod n,
+ *            zero: P2E_WIRE_INFINITY.  p2e_schnorr_public_key_batch(out_sk32) equals the out_pk32 of the public call.  d, t
+ *            and the sum never leave the lane's registers but for out_sk32.
+ *   p2e_taproot_verify_commitment_batch   BIP-341's script-path rule behind the leaf hash, one kernel: Merkle walk, tweak,
+ *            point, compare.  In order: out_parity[i] > 1: P2E_WIRE_BAD_PREFIX; depth[i] > max_depth: P2E_WIRE_BAD_LENGTH
+ *            (max_depth and path32 as above); the two key checks of the pubkey call on the internal key pk32; t >= n and a
+ *            neutral Q as there.  Where err[i] = 0: valid[i] = 1 iff bytes(x(Q)) == out_pk32[i] and y(Q) & 1 ==
+ *            out_parity[i].  An out_pk32 >= p simply never matches and is not flagged; a well-formed mismatch has err = 0,
+ *            valid = 0 and is NOT counted.  valid[i] = 0 wherever err[i] != 0.
+ * Each call is one kernel on the context's caller stream, one lane per element: no internal streams, no LDS, no scratch. */
+long p2e_taproot_leaf_hash_batch(p2e_ctx *ctx, const uint8_t *leaf_version, const uint8_t *script, const uint64_t *offsets,
+                                 uint8_t *leaf32, size_t count, uint8_t *err);
+long p2e_taproot_merkle_root_batch(p2e_ctx *ctx, const uint8_t *leaf32, const uint8_t *path32, const uint8_t *depth,
+                                   size_t max_depth, uint8_t *root32, size_t count, uint8_t *err);
+long p2e_taproot_tweak_pubkey_batch(p2e_ctx *ctx, const uint8_t *pk32, const uint8_t *root32 /* nullable */,
+                                    uint8_t *out_pk32, uint8_t *out_parity, size_t count, uint8_t *err);
+long p2e_taproot_tweak_seckey_batch(p2e_ctx *ctx, const uint8_t *sk32, const uint8_t *root32 /* nullable */,
+                                    uint8_t *out_sk32, size_t count, uint8_t *err);
+long p2e_taproot_verify_commitment_batch(p2e_ctx *ctx, const uint8_t *out_pk32, const uint8_t *out_parity,
+                                         const uint8_t *pk32, const uint8_t *leaf32, const uint8_t *path32,
+                                         const uint8_t *depth, size_t max_depth, size_t count, uint8_t *err, uint8_t *valid);
 
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */

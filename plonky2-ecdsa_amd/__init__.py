@@ -102,6 +102,8 @@ EXPORTS = (
     "p2e_schnorr_public_key_batch", "p2e_schnorr_sign_batch", "p2e_schnorr_verify_batch", "p2e_xonly_decode_batch",
     "p2e_schnorr_verify_aggregate",
     "p2e_bip32_master_batch", "p2e_bip32_ckd_priv_batch", "p2e_bip32_ckd_pub_batch", "p2e_key_hash160_batch", "p2e_hash160_batch",
+    "p2e_taproot_leaf_hash_batch", "p2e_taproot_merkle_root_batch", "p2e_taproot_tweak_pubkey_batch", "p2e_taproot_tweak_seckey_batch",
+    "p2e_taproot_verify_commitment_batch",
 )
 
 
@@ -1355,6 +1357,72 @@ class Context:
         out = out if out is not None else self._bytes(n, 20)
         bad = self._check(self._L.p2e_hash160_batch(self._h, _ptr(data), _ptr(offsets), _ptr(out), C.c_size_t(n)))
         return out, bad
+
+    # ---- Taproot on secp256k1 (include/p2e.h p2e_taproot_leaf_hash_batch and the four calls after it) ---------------------------
+    # Every key, hash and tweak is an (n, 32) array of the standard's big-endian byte strings, as in the Schnorr calls.
+    def taproot_leaf_hash_batch(self, leaf_version, script, offsets, leaf=None, err=None):
+        """H_TapLeaf(version || compact_size(len) || script i), script i = script[offsets[i]:offsets[i + 1]] laid out as for
+        hash_batch: (leaf (n, 32), err, flagged count).  WIRE_BAD_PREFIX for an odd version, WIRE_BAD_LENGTH for reversed
+        offsets or a length >= 2^32."""
+        n = self._shape(offsets)[0] - 1
+        leaf = leaf if leaf is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_taproot_leaf_hash_batch(self._h, _ptr(leaf_version), _ptr(script), _ptr(offsets), _ptr(leaf),
+                                                              C.c_size_t(n), _ptr(err)))
+        return leaf, err, bad
+
+    @staticmethod
+    def _max_depth(path, n):
+        """max_depth of a path array (n, max_depth, 32); None: no paths at all (max_depth 0)"""
+        if path is None:
+            return 0
+        if len(path.shape) != 3 or path.shape[0] != n or path.shape[2] != 32:
+            raise P2EError("path must be (n, max_depth, 32)")
+        return path.shape[1]
+
+    def taproot_merkle_root_batch(self, leaf, path, depth, root=None, err=None):
+        """The Merkle root of every leaf (n, 32) under the first depth[i] nodes of path[i] ((n, max_depth, 32), max_depth <= 128;
+        None for no paths): (root (n, 32), err, flagged count).  depth[i] > max_depth: zeros and WIRE_BAD_LENGTH."""
+        n = self._shape(leaf)[0]
+        max_depth = self._max_depth(path, n)
+        root = root if root is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_taproot_merkle_root_batch(self._h, _ptr(leaf), _ptr(path if max_depth else None), _ptr(depth),
+                                                                C.c_size_t(max_depth), _ptr(root), C.c_size_t(n), _ptr(err)))
+        return root, err, bad
+
+    def taproot_tweak_pubkey_batch(self, pk, root=None, out_pk=None, out_parity=None, err=None):
+        """BIP-341 taproot_tweak_pubkey of (n, 32) x-only keys under (n, 32) Merkle roots, or under no root (root=None, the
+        key-path-only output of BIP-86): (out_pk (n, 32), out_parity (n,), err, flagged count)."""
+        n = self._shape(pk)[0]
+        out_pk = out_pk if out_pk is not None else self._packed(n)
+        out_parity = out_parity if out_parity is not None else self._vec(n, np.uint8)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_taproot_tweak_pubkey_batch(self._h, _ptr(pk), _ptr(root), _ptr(out_pk), _ptr(out_parity),
+                                                                 C.c_size_t(n), _ptr(err)))
+        return out_pk, out_parity, err, bad
+
+    def taproot_tweak_seckey_batch(self, sk, root=None, out_sk=None, err=None):
+        """BIP-341 taproot_tweak_seckey of (n, 32) secret keys: (out_sk (n, 32), err, flagged count) -- the key that
+        schnorr_sign_batch signs a key-path spend with.  The output is secret."""
+        n = self._shape(sk)[0]
+        out_sk = out_sk if out_sk is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_taproot_tweak_seckey_batch(self._h, _ptr(sk), _ptr(root), _ptr(out_sk), C.c_size_t(n), _ptr(err)))
+        return out_sk, err, bad
+
+    def taproot_verify_commitment_batch(self, out_pk, out_parity, pk, leaf, path, depth, err=None, valid=None):
+        """BIP-341's script-path rule behind the leaf hash: does output key out_pk[i] with parity out_parity[i] commit to
+        leaf[i] under internal key pk[i] and the first depth[i] nodes of path[i]?  (err, valid, flagged count); a well-formed
+        mismatch has err 0, valid 0 and is not counted."""
+        n = self._shape(pk)[0]
+        max_depth = self._max_depth(path, n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        valid = valid if valid is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_taproot_verify_commitment_batch(self._h, _ptr(out_pk), _ptr(out_parity), _ptr(pk), _ptr(leaf),
+                                                                      _ptr(path if max_depth else None), _ptr(depth), C.c_size_t(max_depth),
+                                                                      C.c_size_t(n), _ptr(err), _ptr(valid)))
+        return err, valid, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

@@ -32,6 +32,7 @@
 #include "point_arith.hpp"
 #include "point_table.hpp"
 #include "schnorr.hpp"
+#include "taproot.hpp"
 #include "hd.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
@@ -43,7 +44,7 @@ using host::COMPACT_WIDE;
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
 // streaming passes, descriptions;  1 = the fused pipeline of the two built-in programs (run_program);  2 / 3 = the
 // curve-program pipeline instantiated for secp256k1 / P-256 (run_curve_program<CV>).  Undefined = everything in one
-// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 kernels (schnorr.hpp) ride in part 3; the BIP-32 and HASH160 kernels (hd.hpp) ride in part 1 with the other hashes.  Small static helpers (error text, staging, scratch) are compiled into every part.
+// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 and Taproot kernels (schnorr.hpp, taproot.hpp) ride in part 3; the BIP-32 and HASH160 kernels (hd.hpp) ride in part 1 with the other hashes.  Small static helpers (error text, staging, scratch) are compiled into every part.
 #ifndef P2E_PART
 #define P2E_PART (-1)
 #endif
@@ -3346,6 +3347,127 @@ extern "C" long p2e_hash160_batch(p2e_ctx* c, const uint8_t* data, const uint64_
     if (!wire_stage_elements(S, args, data, offsets, n)) return S.done(P2E_E_INVALID);
     if (long rc = S.begin(args)) return rc;
     launch_hash160(c, data, offsets, out20, n);
+    return S.end();
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// Taproot on secp256k1 (taproot.hpp): leaf hashes, Merkle roots, key tweaks, the script-path commitment check
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 3 beside the BIP-340 kernels, called from part 0
+void launch_taproot_leaf_hash(p2e_ctx* c, const uint8_t* version, const uint8_t* script, const uint64_t* offsets, uint8_t* leaf, size_t count,
+                              uint8_t* err);
+void launch_taproot_merkle_root(p2e_ctx* c, const uint8_t* leaf, const uint8_t* path, const uint8_t* depth, size_t max_depth, uint8_t* root,
+                                size_t count, uint8_t* err);
+void launch_taproot_tweak_pubkey(p2e_ctx* c, const Aff* table, const uint8_t* pk, const uint8_t* root, uint8_t* out_pk, uint8_t* out_parity,
+                                 size_t count, uint8_t* err);
+void launch_taproot_tweak_seckey(p2e_ctx* c, const Aff* table, const uint8_t* sk, const uint8_t* root, uint8_t* out_sk, size_t count,
+                                 uint8_t* err);
+void launch_taproot_verify_commitment(p2e_ctx* c, const Aff* table, const uint8_t* out_pk, const uint8_t* out_parity, const uint8_t* pk,
+                                      const uint8_t* leaf, const uint8_t* path, const uint8_t* depth, size_t max_depth, size_t count,
+                                      uint8_t* err, uint8_t* valid);
+#if P2E_HAS(3)
+void launch_taproot_leaf_hash(p2e_ctx* c, const uint8_t* version, const uint8_t* script, const uint64_t* offsets, uint8_t* leaf, size_t count,
+                              uint8_t* err) {
+    hipLaunchKernelGGL((k_taproot_leaf_hash<0>), grid1(count), dim3(BS), 0, c->stream, version, script, offsets, leaf, count, err,
+                       c->d_counter);
+}
+void launch_taproot_merkle_root(p2e_ctx* c, const uint8_t* leaf, const uint8_t* path, const uint8_t* depth, size_t max_depth, uint8_t* root,
+                                size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_taproot_merkle_root<0>), grid1(count), dim3(BS), 0, c->stream, leaf, path, depth, max_depth, root, count, err,
+                       c->d_counter);
+}
+void launch_taproot_tweak_pubkey(p2e_ctx* c, const Aff* table, const uint8_t* pk, const uint8_t* root, uint8_t* out_pk, uint8_t* out_parity,
+                                 size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_taproot_tweak_pubkey<0>), grid1(count), dim3(BS), 0, c->stream, table, pk, root, out_pk, out_parity, count, err,
+                       c->d_counter);
+}
+void launch_taproot_tweak_seckey(p2e_ctx* c, const Aff* table, const uint8_t* sk, const uint8_t* root, uint8_t* out_sk, size_t count,
+                                 uint8_t* err) {
+    hipLaunchKernelGGL((k_taproot_tweak_seckey<0>), grid1(count), dim3(BS), 0, c->stream, table, sk, root, out_sk, count, err, c->d_counter);
+}
+void launch_taproot_verify_commitment(p2e_ctx* c, const Aff* table, const uint8_t* out_pk, const uint8_t* out_parity, const uint8_t* pk,
+                                      const uint8_t* leaf, const uint8_t* path, const uint8_t* depth, size_t max_depth, size_t count,
+                                      uint8_t* err, uint8_t* valid) {
+    hipLaunchKernelGGL((k_taproot_verify_commitment<0>), grid1(count), dim3(BS), 0, c->stream, table, out_pk, out_parity, pk, leaf, path,
+                       depth, max_depth, count, err, valid, c->d_counter);
+}
+#endif   // P2E_HAS(3)
+
+#if P2E_HAS(0)
+static bool taproot_bad_depth(size_t max_depth) {
+    if (max_depth <= TAPROOT_MAX_DEPTH) return false;
+    set_error("max_depth must be at most 128");
+    return true;
+}
+// the elements of path32; 0 for arguments that are refused anyway (so that the product cannot overflow)
+static size_t taproot_nodes(size_t count, size_t max_depth) {
+    return (max_depth <= TAPROOT_MAX_DEPTH && count <= ((size_t)1 << 31)) ? count * max_depth : 0;
+}
+// (the batch size of these five calls is `count`: see include/p2e.h)
+extern "C" long p2e_taproot_leaf_hash_batch(p2e_ctx* c, const uint8_t* leaf_version, const uint8_t* script, const uint64_t* offsets,
+                                            uint8_t* leaf32, size_t count, uint8_t* err) {
+    const Args args = {ARG_IN(leaf_version, 1, count), ARG_OPAQUE(script), ARG_IN(offsets, 8, count + 1), ARG_OUT(leaf32, 32, count),
+                       ARG_OUT(err, 1, count)};
+    if (missing(args) || batch_too_large(count) || bad_overlap(count, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (!wire_stage_elements(S, args, script, offsets, count)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
+    launch_taproot_leaf_hash(c, leaf_version, script, offsets, leaf32, count, err);
+    return S.end();
+}
+extern "C" long p2e_taproot_merkle_root_batch(p2e_ctx* c, const uint8_t* leaf32, const uint8_t* path32, const uint8_t* depth, size_t max_depth,
+                                              uint8_t* root32, size_t count, uint8_t* err) {
+    const size_t nodes = taproot_nodes(count, max_depth);
+    const Args args = {ARG_IN(leaf32, 32, count), ARG_IN_IF(max_depth != 0, path32, 32, nodes), ARG_IN(depth, 1, count),
+                       ARG_OUT(root32, 32, count), ARG_OUT(err, 1, count)};
+    if (missing(args) || taproot_bad_depth(max_depth) || batch_too_large(count) || bad_overlap(count, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_taproot_merkle_root(c, leaf32, path32, depth, max_depth, root32, count, err);
+    return S.end();
+}
+extern "C" long p2e_taproot_tweak_pubkey_batch(p2e_ctx* c, const uint8_t* pk32, const uint8_t* root32, uint8_t* out_pk32, uint8_t* out_parity,
+                                               size_t count, uint8_t* err) {
+    const Args args = {ARG_IN(pk32, 32, count), ARG_IN_OPT(root32, 32, count), ARG_OUT(out_pk32, 32, count), ARG_OUT(out_parity, 1, count),
+                       ARG_OUT(err, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_taproot_tweak_pubkey(c, table, pk32, root32, out_pk32, out_parity, count, err);
+    return S.end();
+}
+extern "C" long p2e_taproot_tweak_seckey_batch(p2e_ctx* c, const uint8_t* sk32, const uint8_t* root32, uint8_t* out_sk32, size_t count,
+                                               uint8_t* err) {
+    const Args args = {ARG_IN(sk32, 32, count), ARG_IN_OPT(root32, 32, count), ARG_OUT(out_sk32, 32, count), ARG_OUT(err, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_taproot_tweak_seckey(c, table, sk32, root32, out_sk32, count, err);
+    return S.end();
+}
+extern "C" long p2e_taproot_verify_commitment_batch(p2e_ctx* c, const uint8_t* out_pk32, const uint8_t* out_parity, const uint8_t* pk32,
+                                                    const uint8_t* leaf32, const uint8_t* path32, const uint8_t* depth, size_t max_depth,
+                                                    size_t count, uint8_t* err, uint8_t* valid) {
+    const size_t nodes = taproot_nodes(count, max_depth);
+    const Args args = {ARG_IN(out_pk32, 32, count), ARG_IN(out_parity, 1, count), ARG_IN(pk32, 32, count), ARG_IN(leaf32, 32, count),
+                       ARG_IN_IF(max_depth != 0, path32, 32, nodes), ARG_IN(depth, 1, count), ARG_OUT(err, 1, count),
+                       ARG_OUT(valid, 1, count)};
+    if (missing(args) || taproot_bad_depth(max_depth)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_taproot_verify_commitment(c, table, out_pk32, out_parity, pk32, leaf32, path32, depth, max_depth, count, err, valid);
     return S.end();
 }
 #endif   // P2E_HAS(0)

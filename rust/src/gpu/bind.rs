@@ -348,6 +348,71 @@ pub fn ckd_priv(ctx: *mut P2eCtx, parents: &[(BigUint, [u8; 32])], indices: &[u3
     Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok((BigUint::from_bytes_le(&out[32 * i..32 * i + 32]), cc[i])) }).collect())
 }
 
+/// BIP-341 `taproot_tweak_pubkey` of x-only keys (`p2e_taproot_tweak_pubkey_batch`, host-pointer context) under one Merkle
+/// root each, or under no root at all (`roots = None`: BIP-86's key-path-only output): `(output key, parity of its y)` or
+/// the `P2E_WIRE_*` code.  All values are the standard's big-endian 32 bytes.
+pub fn taproot_output_keys(ctx: *mut P2eCtx, pks: &[[u8; 32]], roots: Option<&[[u8; 32]]>) -> Result<Vec<std::result::Result<([u8; 32], u8), u8>>> {
+    let n = pks.len();
+    ensure!(roots.map_or(true, |r| r.len() == n));
+    let (mut out, mut parity, mut err) = (vec![[0u8; 32]; n], vec![0u8; n], vec![0u8; n]);
+    let root_ptr = roots.map_or(std::ptr::null(), |r| r.as_ptr().cast());
+    let rc = unsafe {
+        p2e_taproot_tweak_pubkey_batch(ctx, pks.as_ptr().cast(), root_ptr, out.as_mut_ptr().cast(), parity.as_mut_ptr(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok((out[i], parity[i])) }).collect())
+}
+
+/// BIP-341 `taproot_tweak_seckey` (`p2e_taproot_tweak_seckey_batch`, host-pointer context): the keys `schnorr_sign` signs a
+/// key-path spend with.  The keys are secrets: they are the caller's to wipe.
+pub fn taproot_tweak_secret_keys(ctx: *mut P2eCtx, sks: &[[u8; 32]], roots: Option<&[[u8; 32]]>) -> Result<Vec<std::result::Result<[u8; 32], u8>>> {
+    let n = sks.len();
+    ensure!(roots.map_or(true, |r| r.len() == n));
+    let (mut out, mut err) = (vec![[0u8; 32]; n], vec![0u8; n]);
+    let root_ptr = roots.map_or(std::ptr::null(), |r| r.as_ptr().cast());
+    let rc = unsafe { p2e_taproot_tweak_seckey_batch(ctx, sks.as_ptr().cast(), root_ptr, out.as_mut_ptr().cast(), n, err.as_mut_ptr()) };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(out[i]) }).collect())
+}
+
+/// BIP-341's script-path rule for a batch of spends (`p2e_taproot_leaf_hash_batch`, then
+/// `p2e_taproot_verify_commitment_batch`, host-pointer context): does `output.0` with parity `output.1` commit to the script
+/// `leaf.1` of leaf version `leaf.0` under the internal key and the path's nodes?  A malformed element is simply `false`.
+pub fn taproot_script_path_commits(ctx: *mut P2eCtx, outputs: &[([u8; 32], u8)], internal: &[[u8; 32]], leaves: &[(u8, &[u8])],
+                                   paths: &[Vec<[u8; 32]>]) -> Result<Vec<bool>> {
+    let n = outputs.len();
+    ensure!(internal.len() == n && leaves.len() == n && paths.len() == n);
+    let max_depth = paths.iter().map(|p| p.len()).max().unwrap_or(0);
+    ensure!(max_depth <= 128, "a control block holds at most 128 nodes");
+    let (mut versions, mut script, mut offsets) = (Vec::with_capacity(n), Vec::new(), vec![0u64]);
+    for (v, s) in leaves {
+        versions.push(*v);
+        script.extend_from_slice(s);
+        offsets.push(script.len() as u64);
+    }
+    script.resize((script.len() + 3) / 4 * 4 + 4, 0);     // the library reads aligned 4-byte words
+    let (mut leaf, mut leaf_err) = (vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_taproot_leaf_hash_batch(ctx, versions.as_ptr(), script.as_ptr(), offsets.as_ptr(), leaf.as_mut_ptr().cast(), n, leaf_err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    let mut nodes = vec![[0u8; 32]; n * max_depth];
+    let mut depth = Vec::with_capacity(n);
+    for (i, p) in paths.iter().enumerate() {
+        nodes[i * max_depth..i * max_depth + p.len()].copy_from_slice(p);
+        depth.push(p.len() as u8);
+    }
+    let (out_pk, out_parity): (Vec<[u8; 32]>, Vec<u8>) = outputs.iter().cloned().unzip();
+    let (mut err, mut valid) = (vec![0u8; n], vec![0u8; n]);
+    let path_ptr = if max_depth == 0 { std::ptr::null() } else { nodes.as_ptr().cast() };
+    let rc = unsafe {
+        p2e_taproot_verify_commitment_batch(ctx, out_pk.as_ptr().cast(), out_parity.as_ptr(), internal.as_ptr().cast(), leaf.as_ptr().cast(),
+                                            path_ptr, depth.as_ptr(), max_depth, n, err.as_mut_ptr(), valid.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| leaf_err[i] == 0 && valid[i] == 1).collect())
+}
+
 /// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
 /// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
 /// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).

@@ -312,6 +312,20 @@ extern "C" {
         n: usize) -> i64;
     pub fn p2e_hash160_batch(ctx: *mut P2eCtx, data: *const u8, offsets: *const u64, out20: *mut u8, n: usize) -> i64;
 
+    // ---- Taproot (BIP-341) on secp256k1: every key, hash and tweak the standard's big-endian 32 bytes; root32 may be null
+    // (BIP-86's key-path-only output); the batch size is `count` (include/p2e.h says why); err[i] is a P2E_WIRE_* code
+    pub fn p2e_taproot_leaf_hash_batch(ctx: *mut P2eCtx, leaf_version: *const u8, script: *const u8, offsets: *const u64,
+        leaf32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_taproot_merkle_root_batch(ctx: *mut P2eCtx, leaf32: *const u8, path32: *const u8, depth: *const u8, max_depth: usize,
+        root32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_taproot_tweak_pubkey_batch(ctx: *mut P2eCtx, pk32: *const u8, root32: *const u8, out_pk32: *mut u8,
+        out_parity: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_taproot_tweak_seckey_batch(ctx: *mut P2eCtx, sk32: *const u8, root32: *const u8, out_sk32: *mut u8, count: usize,
+        err: *mut u8) -> i64;
+    pub fn p2e_taproot_verify_commitment_batch(ctx: *mut P2eCtx, out_pk32: *const u8, out_parity: *const u8, pk32: *const u8,
+        leaf32: *const u8, path32: *const u8, depth: *const u8, max_depth: usize, count: usize, err: *mut u8,
+        valid: *mut u8) -> i64;
+
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
         pky32: *mut u8) -> i32;
