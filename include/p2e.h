@@ -21,8 +21,8 @@
  *
  * BUFFER OVERLAP
  *   What a call may be handed when an output buffer shares bytes with another argument.  The rule below holds for the
- *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_taproot_verify_commitment_batch (keys, signing,
- *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, Taproot) and the two verdict-only
+ *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_sp_scan_batch (keys, signing,
+ *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, Taproot, silent payments) and the two verdict-only
  *   verifiers p2e_ecdsa_verify_batch and p2e_p256_verify_batch.  It is checked on the host, behind the call's other argument
  *   checks and before the context is looked at, and it is the same with P2E_CTX_HOST_POINTERS (staging would hide the race;
  *   the contract does not depend on the mode).
@@ -43,6 +43,8 @@
  *            pkx32 = par_pkx32, pky32 = par_pky32, cc32 = par_cc32) -- how a path is deepened level by level
  *        p2e_taproot_tweak_pubkey_batch        out_pk32 = pk32;   p2e_taproot_tweak_seckey_batch   out_sk32 = sk32
  *        p2e_taproot_merkle_root_batch         root32 = leaf32
+ *        p2e_sp_input_hash_batch               input_hash32 = ax32;   p2e_sp_send_batch   out_pk32 = input_hash32
+ *            (p2e_sp_scan_batch offers no in-place form: every overlap of one of its outputs is refused)
  *   3. Any other intersection of an output with an input is P2E_E_INVALID, with "overlap" and the two argument names in
  *      p2e_last_error(): a shifted overlap (out == in + 32), different bytes per element (r32 on the 64-byte data of
  *      P2E_SIG_COMPACT64, addr20 on pkx32), and every input that lanes other than "its own" read -- the single parent of a
@@ -1034,6 +1036,74 @@ long p2e_taproot_tweak_seckey_batch(p2e_ctx *ctx, const uint8_t *sk32, const uin
 long p2e_taproot_verify_commitment_batch(p2e_ctx *ctx, const uint8_t *out_pk32, const uint8_t *out_parity,
                                          const uint8_t *pk32, const uint8_t *leaf32, const uint8_t *path32,
                                          const uint8_t *depth, size_t max_depth, size_t count, uint8_t *err, uint8_t *valid);
+
+/* ---- Silent payments (BIP-352) on secp256k1 (csrc/sp.hpp): the sender's output keys and the receiver's scan.  A receiver does
+ * one ECDH per eligible transaction -- a general-point multiplication by the scan key --, then per step k a tagged hash, a
+ * fixed-base walk, an addition and a compare against the transaction's outputs; p2e_sp_scan_batch does all of it for one
+ * transaction per lane without visiting the host.
+ *   count    The batch size of these four calls is named `count`, as for the Taproot calls and for the same reason:
+ *            no parameter is named n or m.  They carry their span table in tests/test_sp_cpu.py.  BUFFER OVERLAP holds in full.
+ *   bytes    TWO orders, by where a value comes from.  Points and the secret scalars of the key layer are the library's
+ *            LITTLE-endian 32-byte values, as in the BIP-32 calls (they chain with p2e_bip32_*, p2e_point_add_batch,
+ *            p2e_ecdsa_public_key_batch): ax32 / ay32, scan_sk32, a_sk32, spend_pkx32 / spend_pky32, scan_pkx32 / scan_pky32,
+ *            label_x32 / label_y32.  Everything BIP-352 defines as a byte string or a hash is the standard's BIG-endian
+ *            string, as in the Schnorr and Taproot calls: outpoint36 (txid || vout, as serialised), input_hash32, the x-only
+ *            outputs32, hit_tweak32 and label_tweak32.  label_index, k and hit_output are uint32 arrays; every array is
+ *            4-byte aligned but the one-byte ones.
+ *   hashes   H_tag(x) = SHA256(SHA256(tag) || SHA256(tag) || x) for "BIP0352/Inputs", "BIP0352/SharedSecret", "BIP0352/Label".
+ *            serP is the 33-byte compressed point, ser32 four big-endian bytes, ser256 thirty-two.
+ *              input_hash = int(H_Inputs(outpoint36 || serP(A)))
+ *              S   = (input_hash b_scan mod n) A   for the receiver,   (input_hash a mod n) B_scan   for the sender
+ *              t_k = int(H_SharedSecret(serP(S) || ser32(k))),   P_k = B_spend + t_k G,   the output is bytes(x(P_k))
+ *              l_m = int(H_Label(ser256(b_scan) || ser32(m))),   L_m = l_m G   (B_spend + L_m is p2e_point_add_batch)
+ *   err[i]   a P2E_WIRE_* CODE: the first failing check in the order given below; a flagged element writes zeros to all its
+ *            outputs (n_hits = 0).  The return value counts the flagged elements; count == 0 returns 0.  Null pointers, host
+ *            pointers, async mode, the current device and failed calls behave as for the Taproot calls.  An argument shared
+ *            by the batch (one element) is checked by every lane and flags every element alike.  The checks: a secret scalar
+ *            0 or >= n: P2E_WIRE_SCALAR_RANGE (never reduced); a point (0, 0): P2E_WIRE_INFINITY; a coordinate >= p:
+ *            P2E_WIRE_COORD_RANGE; a point off the curve: P2E_WIRE_NOT_ON_CURVE.
+ *   p2e_sp_input_hash_batch   the point checks on A (a neutral A is P2E_WIRE_INFINITY: BIP-352 skips such a transaction),
+ *            then a hash of 0 or >= n: P2E_WIRE_SCALAR_RANGE.  In place: input_hash32 = ax32.
+ *   p2e_sp_label_batch   scan_sk32 is ONE element.  The scan key check, then l_m = 0 or >= n: P2E_WIRE_SCALAR_RANGE.
+ *            label_tweak32 = bytes(l_m), (label_x32, label_y32) = L_m.  No output may lie on label_index.
+ *   p2e_sp_send_batch   In order: a_sk32, input_hash32 (0 or >= n: P2E_WIRE_SCALAR_RANGE), B_scan, B_spend; t_k = 0 or >= n:
+ *            P2E_WIRE_SCALAR_RANGE; P_k neutral: P2E_WIRE_INFINITY.  out_pk32 = bytes(x(P_k)).  a, the product and S never
+ *            leave the lane's registers.  In place: out_pk32 = input_hash32.
+ *   p2e_sp_scan_batch   scan_sk32, spend_pkx32, spend_pky32 are ONE element each, label_x32 / label_y32 n_labels elements
+ *            (n_labels <= P2E_SP_MAX_LABELS; with n_labels == 0 both may be null).  Transaction i has the outputs
+ *            outputs32 + 32 j for out_offsets[i] <= j < out_offsets[i + 1] (out_offsets: count + 1 elements, in OUTPUTS, not
+ *            bytes).  In order: the scan key, B_spend, labels 0 .. n_labels - 1 (these flag every element); A_i; input_hash32[i]
+ *            if given (0 or >= n: P2E_WIRE_SCALAR_RANGE); out_offsets[i + 1] < out_offsets[i] or more than 2^32 - 1 outputs:
+ *            P2E_WIRE_BAD_LENGTH; then per step t_k = 0 or >= n: P2E_WIRE_SCALAR_RANGE, P_k neutral: P2E_WIRE_INFINITY (BIP-352
+ *            fails there too; a flag at a step k > 0 drops the hits already recorded).  With input_hash32 == NULL the scalar
+ *            is b_scan alone: A is then the "tweak data" input_hash A that indexes serve to light clients.
+ *            The scan loop of one transaction: k = 0; the candidates of step k are P_k, then P_k + L_j for j = 0 .. n_labels - 1
+ *            (this covers BIP-352's label tests on output - P_k and -output - P_k); output o matches candidate C iff
+ *            x(C) == o.  The hit is the lowest-index output not yet recorded that matches a candidate, under its first matching
+ *            candidate; it becomes hit number k, k += 1, and the loop goes on unless k == max_hits.  Without a hit it stops.  A
+ *            neutral candidate matches nothing, an output >= p never matches; neither is flagged.
+ *            n_hits[i] <= max_hits (equal: the loop stopped at the cap); hit_output[max_hits i + h] the output's index within
+ *            the transaction; hit_label[..] 0 for unlabelled, j + 1 for label j; hit_tweak32 + 32 (max_hits i + h) = bytes(t_h)
+ *            (the spending key b_spend + t_h (+ l_j) is the host's addition).  Unused slots are zero.  max_hits outside
+ *            1 .. P2E_SP_MAX_HITS or n_labels > P2E_SP_MAX_LABELS: P2E_E_INVALID.  No in-place form.  outputs32 has an extent
+ *            only the device knows (BUFFER OVERLAP 5); with host pointers the bytes outputs32[32 out_offsets[0],
+ *            32 out_offsets[count]) are staged, and an offset outside that range is P2E_E_INVALID.
+ * Each call is one kernel on the context's caller stream, one lane per element: no internal streams, no scratch. */
+#define P2E_SP_MAX_HITS 8
+#define P2E_SP_MAX_LABELS 16
+long p2e_sp_input_hash_batch(p2e_ctx *ctx, const uint8_t *outpoint36, const uint8_t *ax32, const uint8_t *ay32,
+                             uint8_t *input_hash32, size_t count, uint8_t *err);
+long p2e_sp_label_batch(p2e_ctx *ctx, const uint8_t *scan_sk32 /* 1 element */, const uint32_t *label_index,
+                        uint8_t *label_tweak32, uint8_t *label_x32, uint8_t *label_y32, size_t count, uint8_t *err);
+long p2e_sp_send_batch(p2e_ctx *ctx, const uint8_t *a_sk32, const uint8_t *input_hash32, const uint8_t *scan_pkx32,
+                       const uint8_t *scan_pky32, const uint8_t *spend_pkx32, const uint8_t *spend_pky32, const uint32_t *k,
+                       uint8_t *out_pk32, size_t count, uint8_t *err);
+long p2e_sp_scan_batch(p2e_ctx *ctx, const uint8_t *scan_sk32 /* 1 */, const uint8_t *spend_pkx32 /* 1 */,
+                       const uint8_t *spend_pky32 /* 1 */, const uint8_t *label_x32, const uint8_t *label_y32, size_t n_labels,
+                       const uint8_t *ax32, const uint8_t *ay32, const uint8_t *input_hash32 /* nullable */,
+                       const uint8_t *outputs32, const uint64_t *out_offsets /* count + 1, in outputs */, size_t max_hits,
+                       uint8_t *n_hits, uint32_t *hit_output, uint8_t *hit_label, uint8_t *hit_tweak32, size_t count,
+                       uint8_t *err);
 
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */

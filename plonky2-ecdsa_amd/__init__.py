@@ -104,6 +104,7 @@ EXPORTS = (
     "p2e_bip32_master_batch", "p2e_bip32_ckd_priv_batch", "p2e_bip32_ckd_pub_batch", "p2e_key_hash160_batch", "p2e_hash160_batch",
     "p2e_taproot_leaf_hash_batch", "p2e_taproot_merkle_root_batch", "p2e_taproot_tweak_pubkey_batch", "p2e_taproot_tweak_seckey_batch",
     "p2e_taproot_verify_commitment_batch",
+    "p2e_sp_input_hash_batch", "p2e_sp_label_batch", "p2e_sp_send_batch", "p2e_sp_scan_batch",
 )
 
 
@@ -1423,6 +1424,69 @@ class Context:
                                                                       _ptr(path if max_depth else None), _ptr(depth), C.c_size_t(max_depth),
                                                                       C.c_size_t(n), _ptr(err), _ptr(valid)))
         return err, valid, bad
+
+    # ---- silent payments on secp256k1 (include/p2e.h p2e_sp_input_hash_batch and the three calls after it) ----------------------
+    # Points and secret keys are (n, 32) little-endian arrays as in the BIP-32 calls; outpoints, input hashes, x-only outputs
+    # and tweaks are the standard's big-endian byte strings; label indices, k and hit_output are 32-bit integers.
+    def _u32(self, *shape):
+        if self.host_pointers:
+            return np.zeros(shape, dtype=np.uint32)
+        import torch
+        return torch.empty(shape, dtype=torch.int32, device=f"cuda:{self.device}")
+
+    def sp_input_hash_batch(self, outpoint, ax, ay, input_hash=None, err=None):
+        """BIP-352 input_hash = H_Inputs(outpoint || serP(A)) of (n, 36) outpoints and the points A (ax, ay (n, 32)):
+        (input_hash (n, 32) big-endian, err, flagged count)."""
+        n = self._shape(ax)[0]
+        input_hash = input_hash if input_hash is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_sp_input_hash_batch(self._h, _ptr(outpoint), _ptr(ax), _ptr(ay), _ptr(input_hash), C.c_size_t(n),
+                                                          _ptr(err)))
+        return input_hash, err, bad
+
+    def sp_label_batch(self, scan_sk, label_index, label_tweak=None, label_x=None, label_y=None, err=None):
+        """The labels label_index (n,) 32-bit of the ONE scan key scan_sk (1, 32): (label_tweak (n, 32) big-endian = l_m,
+        label_x, label_y (n, 32) = l_m G, err, flagged count)."""
+        n = self._shape(label_index)[0]
+        label_tweak = label_tweak if label_tweak is not None else self._packed(n)
+        label_x = label_x if label_x is not None else self._packed(n)
+        label_y = label_y if label_y is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_sp_label_batch(self._h, _ptr(scan_sk), _ptr(label_index), _ptr(label_tweak), _ptr(label_x), _ptr(label_y),
+                                                     C.c_size_t(n), _ptr(err)))
+        return label_tweak, label_x, label_y, err, bad
+
+    def sp_send_batch(self, a_sk, input_hash, scan_pkx, scan_pky, spend_pkx, spend_pky, k, out_pk=None, err=None):
+        """The sender's output keys: out_pk[i] = x(B_spend + t_k G), t_k from S = (input_hash a) B_scan and k[i] (32-bit):
+        (out_pk (n, 32) big-endian, err, flagged count)."""
+        n = self._shape(a_sk)[0]
+        out_pk = out_pk if out_pk is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_sp_send_batch(self._h, _ptr(a_sk), _ptr(input_hash), _ptr(scan_pkx), _ptr(scan_pky), _ptr(spend_pkx),
+                                                    _ptr(spend_pky), _ptr(k), _ptr(out_pk), C.c_size_t(n), _ptr(err)))
+        return out_pk, err, bad
+
+    def sp_scan_batch(self, scan_sk, spend_pkx, spend_pky, ax, ay, outputs, out_offsets, input_hash=None, label_x=None, label_y=None,
+                      max_hits=1, n_hits=None, hit_output=None, hit_label=None, hit_tweak=None, err=None):
+        """The receiver's scan of n transactions under ONE scan key and spend key ((1, 32) each) and the labels label_x, label_y
+        ((n_labels, 32), or None): transaction i has the input point (ax[i], ay[i]), the input hash input_hash[i] (None: A is
+        already multiplied by it) and the x-only outputs outputs[out_offsets[i]:out_offsets[i + 1]] ((total, 32) big-endian,
+        out_offsets (n + 1,) 64-bit).  (n_hits (n,), hit_output (n, max_hits) 32-bit, hit_label (n, max_hits), hit_tweak
+        (n, max_hits, 32) big-endian, err, flagged count)."""
+        n = self._shape(ax)[0]
+        n_labels = 0 if label_x is None else self._shape(label_x)[0]
+        if not 1 <= max_hits <= 8:
+            raise P2EError("max_hits must be 1 .. 8")
+        n_hits = n_hits if n_hits is not None else self._vec(n, np.uint8)
+        hit_output = hit_output if hit_output is not None else self._u32(n, max_hits)
+        hit_label = hit_label if hit_label is not None else self._bytes(n, max_hits)
+        hit_tweak = hit_tweak if hit_tweak is not None else self._bytes(n, max_hits, 32)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_sp_scan_batch(self._h, _ptr(scan_sk), _ptr(spend_pkx), _ptr(spend_pky), _ptr(label_x), _ptr(label_y),
+                                                    C.c_size_t(n_labels), _ptr(ax), _ptr(ay), _ptr(input_hash), _ptr(outputs), _ptr(out_offsets),
+                                                    C.c_size_t(max_hits), _ptr(n_hits), _ptr(hit_output), _ptr(hit_label), _ptr(hit_tweak),
+                                                    C.c_size_t(n), _ptr(err)))
+        return n_hits, hit_output, hit_label, hit_tweak, err, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

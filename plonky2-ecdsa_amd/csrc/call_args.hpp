@@ -36,7 +36,7 @@ struct Buf {
     bool required;
 };
 using List = std::initializer_list<Buf>;
-constexpr size_t kMaxBufs = 12;  // the longest list of the library has 9
+constexpr size_t kMaxBufs = 16;  // the longest list of the library has 15 (p2e_sp_scan_batch)
 
 // the macros take the variable itself: its name is the header's, its address the slot
 #define P2E_ARG(p, bytes, count, role, required) \

@@ -33,6 +33,7 @@
 #include "point_table.hpp"
 #include "schnorr.hpp"
 #include "taproot.hpp"
+#include "sp.hpp"
 #include "hd.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
@@ -44,7 +45,7 @@ using host::COMPACT_WIDE;
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
 // streaming passes, descriptions;  1 = the fused pipeline of the two built-in programs (run_program);  2 / 3 = the
 // curve-program pipeline instantiated for secp256k1 / P-256 (run_curve_program<CV>).  Undefined = everything in one
-// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 and Taproot kernels (schnorr.hpp, taproot.hpp) ride in part 3; the BIP-32 and HASH160 kernels (hd.hpp) ride in part 1 with the other hashes.  Small static helpers (error text, staging, scratch) are compiled into every part.
+// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 and Taproot kernels (schnorr.hpp, taproot.hpp) ride in part 3; the BIP-32 and HASH160 kernels (hd.hpp) ride in part 1 with the other hashes, and so do the silent-payment kernels (sp.hpp), beside the point multiplication whose walk they hold.  Small static helpers (error text, staging, scratch) are compiled into every part.
 #ifndef P2E_PART
 #define P2E_PART (-1)
 #endif
@@ -3468,6 +3469,154 @@ extern "C" long p2e_taproot_verify_commitment_batch(p2e_ctx* c, const uint8_t* o
     Staged S(c);
     if (long rc = S.begin(args)) return rc;
     launch_taproot_verify_commitment(c, table, out_pk32, out_parity, pk32, leaf32, path32, depth, max_depth, count, err, valid);
+    return S.end();
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// Silent payments (BIP-352) on secp256k1 (sp.hpp): input hashes, labels, the sender's output keys, the receiver's scan
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 1 beside the point multiplication, called from part 0
+void launch_sp_input_hash(p2e_ctx* c, const uint8_t* outpoint, const uint8_t* ax, const uint8_t* ay, uint8_t* input_hash, size_t count,
+                          uint8_t* err);
+void launch_sp_label(p2e_ctx* c, const Aff* table, const uint8_t* scan_sk, const uint32_t* label_index, uint8_t* label_tweak, uint8_t* label_x,
+                     uint8_t* label_y, size_t count, uint8_t* err);
+void launch_sp_send(p2e_ctx* c, const Aff* table, const uint8_t* a_sk, const uint8_t* input_hash, const uint8_t* scan_pkx, const uint8_t* scan_pky,
+                    const uint8_t* spend_pkx, const uint8_t* spend_pky, const uint32_t* k, uint8_t* out_pk, size_t count, uint8_t* err);
+void launch_sp_scan(p2e_ctx* c, const Aff* table, const uint8_t* scan_sk, const uint8_t* spend_pkx, const uint8_t* spend_pky,
+                    const uint8_t* label_x, const uint8_t* label_y, size_t n_labels, const uint8_t* ax, const uint8_t* ay,
+                    const uint8_t* input_hash, const uint8_t* outputs, const uint64_t* out_offsets, size_t max_hits, uint8_t* n_hits,
+                    uint32_t* hit_output, uint8_t* hit_label, uint8_t* hit_tweak, size_t count, uint8_t* err);
+#if P2E_HAS(1)
+void launch_sp_input_hash(p2e_ctx* c, const uint8_t* outpoint, const uint8_t* ax, const uint8_t* ay, uint8_t* input_hash, size_t count,
+                          uint8_t* err) {
+    hipLaunchKernelGGL((k_sp_input_hash<0>), grid1(count), dim3(BS), 0, c->stream, outpoint, ax, ay, input_hash, count, err, c->d_counter);
+}
+void launch_sp_label(p2e_ctx* c, const Aff* table, const uint8_t* scan_sk, const uint32_t* label_index, uint8_t* label_tweak, uint8_t* label_x,
+                     uint8_t* label_y, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_sp_label<0>), grid1(count), dim3(BS), 0, c->stream, table, scan_sk, label_index, label_tweak, label_x, label_y, count,
+                       err, c->d_counter);
+}
+void launch_sp_send(p2e_ctx* c, const Aff* table, const uint8_t* a_sk, const uint8_t* input_hash, const uint8_t* scan_pkx, const uint8_t* scan_pky,
+                    const uint8_t* spend_pkx, const uint8_t* spend_pky, const uint32_t* k, uint8_t* out_pk, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_sp_send<0>), grid1(count), dim3(BS), 0, c->stream, table, a_sk, input_hash, scan_pkx, scan_pky, spend_pkx, spend_pky, k,
+                       out_pk, count, err, c->d_counter);
+}
+void launch_sp_scan(p2e_ctx* c, const Aff* table, const uint8_t* scan_sk, const uint8_t* spend_pkx, const uint8_t* spend_pky,
+                    const uint8_t* label_x, const uint8_t* label_y, size_t n_labels, const uint8_t* ax, const uint8_t* ay,
+                    const uint8_t* input_hash, const uint8_t* outputs, const uint64_t* out_offsets, size_t max_hits, uint8_t* n_hits,
+                    uint32_t* hit_output, uint8_t* hit_label, uint8_t* hit_tweak, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_sp_scan<0>), grid1(count), dim3(BS), 0, c->stream, table, scan_sk, spend_pkx, spend_pky, label_x, label_y,
+                       (u32)n_labels, ax, ay, input_hash, outputs, out_offsets, (u32)max_hits, n_hits, hit_output, hit_label, hit_tweak, count,
+                       err, c->d_counter);
+}
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static bool sp_bad_limits(size_t max_hits, size_t n_labels) {
+    if (max_hits >= 1 && max_hits <= SP_MAX_HITS && n_labels <= SP_MAX_LABELS) return false;
+    set_error("max_hits must be 1 .. 8 (P2E_SP_MAX_HITS) and n_labels at most 16 (P2E_SP_MAX_LABELS)");
+    return true;
+}
+// the outputs of a staged scan: the copy holds outputs32[32 out_offsets[0], 32 out_offsets[count]) and `outputs32` becomes that
+// copy moved back by 32 out_offsets[0] (wire_stage_elements, for 32-byte elements).  Every offset must lie inside that
+// range: a lane reads its own [out_offsets[i], out_offsets[i + 1]) of the copy.  false: the error text is set.
+static bool sp_stage_outputs(Staged& S, Args args, const uint8_t*& outputs32, const uint64_t* out_offsets, size_t count) {
+    if (!S.host) return true;
+    const uint64_t first = out_offsets[0], last = out_offsets[count];
+    if (last < first || last > ((uint64_t)1 << 56)) {
+        set_error("out_offsets[count] < out_offsets[0], or beyond 2^56 outputs");
+        return false;
+    }
+    for (size_t i = 0; i <= count; i++)
+        if (out_offsets[i] < first || out_offsets[i] > last) {
+            set_error("an element of out_offsets lies outside [out_offsets[0], out_offsets[count]]");
+            return false;
+        }
+    overlap::Span spans[call_args::kMaxBufs + 1];
+    size_t num = 0;
+    for (size_t i = 0, all = call_args::spans(args, count, spans); i < all; i++)
+        if (spans[i].is_output) spans[num++] = spans[i];
+    spans[num++] = overlap::Span{"outputs32", outputs32 + 32 * first, 32, (size_t)(last - first), false, true};   // (no lane owns a byte of it)
+    if (const overlap::Clash k = overlap::check(spans, num); k.bad) {
+        set_error(std::string("overlap: ") + k.a + " and " + k.b + " share bytes (variable-length data may not touch an output)");
+        return false;
+    }
+    const uint8_t* d = S.in(outputs32 + 32 * first, 32 * (size_t)(last - first));
+    outputs32 = d ? d - 32 * first : nullptr;
+    return true;
+}
+// (the batch size of these four calls is `count`: see include/p2e.h)
+extern "C" long p2e_sp_input_hash_batch(p2e_ctx* c, const uint8_t* outpoint36, const uint8_t* ax32, const uint8_t* ay32, uint8_t* input_hash32,
+                                        size_t count, uint8_t* err) {
+    const Args args = {ARG_IN(outpoint36, 36, count), ARG_IN(ax32, 32, count), ARG_IN(ay32, 32, count), ARG_OUT(input_hash32, 32, count),
+                       ARG_OUT(err, 1, count)};
+    if (missing(args) || batch_too_large(count) || bad_overlap(count, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_sp_input_hash(c, outpoint36, ax32, ay32, input_hash32, count, err);
+    return S.end();
+}
+extern "C" long p2e_sp_label_batch(p2e_ctx* c, const uint8_t* scan_sk32, const uint32_t* label_index, uint8_t* label_tweak32, uint8_t* label_x32,
+                                   uint8_t* label_y32, size_t count, uint8_t* err) {
+    const Args args = {ARG_SHARED(scan_sk32, 32, 1), ARG_IN(label_index, 4, count), ARG_OUT(label_tweak32, 32, count),
+                       ARG_OUT(label_x32, 32, count), ARG_OUT(label_y32, 32, count), ARG_OUT(err, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_sp_label(c, table, scan_sk32, label_index, label_tweak32, label_x32, label_y32, count, err);
+    return S.end();
+}
+extern "C" long p2e_sp_send_batch(p2e_ctx* c, const uint8_t* a_sk32, const uint8_t* input_hash32, const uint8_t* scan_pkx32,
+                                  const uint8_t* scan_pky32, const uint8_t* spend_pkx32, const uint8_t* spend_pky32, const uint32_t* k,
+                                  uint8_t* out_pk32, size_t count, uint8_t* err) {
+    const Args args = {ARG_IN(a_sk32, 32, count),       ARG_IN(input_hash32, 32, count), ARG_IN(scan_pkx32, 32, count),
+                       ARG_IN(scan_pky32, 32, count),   ARG_IN(spend_pkx32, 32, count),  ARG_IN(spend_pky32, 32, count),
+                       ARG_IN(k, 4, count),             ARG_OUT(out_pk32, 32, count),    ARG_OUT(err, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_sp_send(c, table, a_sk32, input_hash32, scan_pkx32, scan_pky32, spend_pkx32, spend_pky32, k, out_pk32, count, err);
+    return S.end();
+}
+extern "C" long p2e_sp_scan_batch(p2e_ctx* c, const uint8_t* scan_sk32, const uint8_t* spend_pkx32, const uint8_t* spend_pky32,
+                                  const uint8_t* label_x32, const uint8_t* label_y32, size_t n_labels, const uint8_t* ax32, const uint8_t* ay32,
+                                  const uint8_t* input_hash32, const uint8_t* outputs32, const uint64_t* out_offsets, size_t max_hits,
+                                  uint8_t* n_hits, uint32_t* hit_output, uint8_t* hit_label, uint8_t* hit_tweak32, size_t count, uint8_t* err) {
+    // the extents of refused arguments are 0, so that no product can overflow; nothing of the scan may be used in place
+    const bool sane = max_hits >= 1 && max_hits <= SP_MAX_HITS && n_labels <= SP_MAX_LABELS && count <= ((size_t)1 << 31);
+    const size_t slots = sane ? count * max_hits : 0, labels = sane ? n_labels : 0;
+    const Args args = {ARG_SHARED(scan_sk32, 32, 1),
+                       ARG_SHARED(spend_pkx32, 32, 1),
+                       ARG_SHARED(spend_pky32, 32, 1),
+                       P2E_ARG(label_x32, 32, labels, Shared, n_labels != 0),
+                       P2E_ARG(label_y32, 32, labels, Shared, n_labels != 0),
+                       ARG_SHARED(ax32, 32, count),
+                       ARG_SHARED(ay32, 32, count),
+                       P2E_ARG(input_hash32, 32, count, Shared, false),
+                       ARG_OPAQUE(outputs32),
+                       ARG_IN(out_offsets, 8, count + 1),
+                       ARG_OUT(n_hits, 1, count),
+                       ARG_OUT(hit_output, 4, slots),
+                       ARG_OUT(hit_label, 1, slots),
+                       ARG_OUT(hit_tweak32, 32, slots),
+                       ARG_OUT(err, 1, count)};
+    if (missing(args) || sp_bad_limits(max_hits, n_labels)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (!sp_stage_outputs(S, args, outputs32, out_offsets, count)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
+    launch_sp_scan(c, table, scan_sk32, spend_pkx32, spend_pky32, n_labels ? label_x32 : nullptr, n_labels ? label_y32 : nullptr, n_labels, ax32,
+                   ay32, input_hash32, outputs32, out_offsets, max_hits, n_hits, hit_output, hit_label, hit_tweak32, count, err);
     return S.end();
 }
 #endif   // P2E_HAS(0)

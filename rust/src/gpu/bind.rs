@@ -413,6 +413,92 @@ pub fn taproot_script_path_commits(ctx: *mut P2eCtx, outputs: &[([u8; 32], u8)],
     Ok((0..n).map(|i| leaf_err[i] == 0 && valid[i] == 1).collect())
 }
 
+/// One hit of a silent-payment scan: the output's index within its transaction, 0 for an unlabelled hit or `j + 1` for label
+/// `j`, and the big-endian tweak `t_k` (the spending key is `b_spend + t_k (+ l_j)`).
+pub type SpHit = (u32, u8, [u8; 32]);
+
+/// BIP-352 input hashes (`p2e_sp_input_hash_batch`, host-pointer context): `H_Inputs(outpoint || serP(A))` as big-endian
+/// 32 bytes for each smallest outpoint (36 bytes as serialised) and summed input key `A` (little-endian), or the code.
+pub fn sp_input_hashes(ctx: *mut P2eCtx, outpoints: &[[u8; 36]], inputs: &[([u8; 32], [u8; 32])]) -> Result<Vec<std::result::Result<[u8; 32], u8>>> {
+    let n = outpoints.len();
+    ensure!(inputs.len() == n);
+    let (ax, ay): (Vec<[u8; 32]>, Vec<[u8; 32]>) = inputs.iter().cloned().unzip();
+    let (mut out, mut err) = (vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_sp_input_hash_batch(ctx, outpoints.as_ptr().cast(), ax.as_ptr().cast(), ay.as_ptr().cast(), out.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(out[i]) }).collect())
+}
+
+/// BIP-352 labels of one scan key (`p2e_sp_label_batch`, host-pointer context): `(l_m big-endian, (x, y) of l_m G
+/// little-endian)` for each index `m`, or the code.  `scan_sk` is a secret: it is the caller's to wipe.
+pub fn sp_labels(ctx: *mut P2eCtx, scan_sk: &[u8; 32], indices: &[u32]) -> Result<Vec<std::result::Result<([u8; 32], ([u8; 32], [u8; 32])), u8>>> {
+    let n = indices.len();
+    let (mut tweak, mut x, mut y, mut err) = (vec![[0u8; 32]; n], vec![[0u8; 32]; n], vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_sp_label_batch(ctx, scan_sk.as_ptr(), indices.as_ptr(), tweak.as_mut_ptr().cast(), x.as_mut_ptr().cast(), y.as_mut_ptr().cast(), n,
+                           err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok((tweak[i], (x[i], y[i]))) }).collect())
+}
+
+/// BIP-352 output keys of a sender (`p2e_sp_send_batch`, host-pointer context): `x(B_spend + t_k G)` with `t_k` from
+/// `(input_hash a) B_scan` and `k`, or the `P2E_WIRE_*` code.  Keys and points are little-endian, `input_hash` and the result
+/// the standard's big-endian 32 bytes.  `a` is a secret: it is the caller's to wipe.
+pub fn sp_output_keys(ctx: *mut P2eCtx, a: &[[u8; 32]], input_hash: &[[u8; 32]], scan_pk: &[([u8; 32], [u8; 32])],
+                      spend_pk: &[([u8; 32], [u8; 32])], k: &[u32]) -> Result<Vec<std::result::Result<[u8; 32], u8>>> {
+    let n = a.len();
+    ensure!(input_hash.len() == n && scan_pk.len() == n && spend_pk.len() == n && k.len() == n);
+    let (scx, scy): (Vec<[u8; 32]>, Vec<[u8; 32]>) = scan_pk.iter().cloned().unzip();
+    let (spx, spy): (Vec<[u8; 32]>, Vec<[u8; 32]>) = spend_pk.iter().cloned().unzip();
+    let (mut out, mut err) = (vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_sp_send_batch(ctx, a.as_ptr().cast(), input_hash.as_ptr().cast(), scx.as_ptr().cast(), scy.as_ptr().cast(), spx.as_ptr().cast(),
+                          spy.as_ptr().cast(), k.as_ptr(), out.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(out[i]) }).collect())
+}
+
+/// BIP-352 scan of a batch of transactions under one scan key, one spend key and up to 16 labels (`p2e_sp_input_hash_batch`
+/// is the caller's, or the index's: `input_hash = None` takes `inputs` as tweak data).  Transaction `i` is the input point
+/// `inputs[i]` and the x-only outputs `outputs[i]`; the result is its hits, at most `max_hits` (1 .. 8), or the
+/// `P2E_WIRE_*` code.  `scan_sk` is a secret: it is the caller's to wipe.
+pub fn sp_scan(ctx: *mut P2eCtx, scan_sk: &[u8; 32], spend_pk: &([u8; 32], [u8; 32]), labels: &[([u8; 32], [u8; 32])],
+               inputs: &[([u8; 32], [u8; 32])], input_hash: Option<&[[u8; 32]]>, outputs: &[Vec<[u8; 32]>], max_hits: usize)
+               -> Result<Vec<std::result::Result<Vec<SpHit>, u8>>> {
+    let n = inputs.len();
+    ensure!(outputs.len() == n && input_hash.map_or(true, |h| h.len() == n));
+    ensure!((1..=8).contains(&max_hits) && labels.len() <= 16, "at most 8 hits per transaction and 16 labels");
+    let (lx, ly): (Vec<[u8; 32]>, Vec<[u8; 32]>) = labels.iter().cloned().unzip();
+    let (ax, ay): (Vec<[u8; 32]>, Vec<[u8; 32]>) = inputs.iter().cloned().unzip();
+    let (mut flat, mut offsets) = (Vec::new(), vec![0u64]);
+    for o in outputs {
+        flat.extend_from_slice(o);
+        offsets.push(flat.len() as u64);
+    }
+    flat.push([0u8; 32]); // never read: keeps the pointer of a batch without outputs valid
+    let (mut n_hits, mut err) = (vec![0u8; n], vec![0u8; n]);
+    let (mut hit_output, mut hit_label, mut hit_tweak) = (vec![0u32; n * max_hits], vec![0u8; n * max_hits], vec![[0u8; 32]; n * max_hits]);
+    let label_ptr = |v: &Vec<[u8; 32]>| -> *const u8 { if labels.is_empty() { std::ptr::null() } else { v.as_ptr().cast() } };
+    let hash_ptr: *const u8 = input_hash.map_or(std::ptr::null(), |h| h.as_ptr().cast());
+    let rc = unsafe {
+        p2e_sp_scan_batch(ctx, scan_sk.as_ptr(), spend_pk.0.as_ptr(), spend_pk.1.as_ptr(), label_ptr(&lx), label_ptr(&ly), labels.len(),
+                          ax.as_ptr().cast(), ay.as_ptr().cast(), hash_ptr, flat.as_ptr().cast(), offsets.as_ptr(), max_hits,
+                          n_hits.as_mut_ptr(), hit_output.as_mut_ptr(), hit_label.as_mut_ptr(), hit_tweak.as_mut_ptr().cast(), n,
+                          err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| {
+        if err[i] != 0 {
+            return Err(err[i]);
+        }
+        Ok((0..n_hits[i] as usize).map(|h| (hit_output[max_hits * i + h], hit_label[max_hits * i + h], hit_tweak[max_hits * i + h])).collect())
+    }).collect())
+}
+
 /// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
 /// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
 /// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).

@@ -326,6 +326,21 @@ extern "C" {
         leaf32: *const u8, path32: *const u8, depth: *const u8, max_depth: usize, count: usize, err: *mut u8,
         valid: *mut u8) -> i64;
 
+    // ---- silent payments (BIP-352) on secp256k1: points and secret keys little-endian 32 bytes, outpoints, input hashes, x-only
+    // outputs and tweaks the standard's big-endian strings; scan_sk32 / spend_pk* are ONE element, label_* n_labels elements;
+    // input_hash32 of the scan may be null; out_offsets counts outputs; the batch size is `count`; err[i] is a P2E_WIRE_* code
+    pub fn p2e_sp_input_hash_batch(ctx: *mut P2eCtx, outpoint36: *const u8, ax32: *const u8, ay32: *const u8, input_hash32: *mut u8,
+        count: usize, err: *mut u8) -> i64;
+    pub fn p2e_sp_label_batch(ctx: *mut P2eCtx, scan_sk32: *const u8, label_index: *const u32, label_tweak32: *mut u8,
+        label_x32: *mut u8, label_y32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_sp_send_batch(ctx: *mut P2eCtx, a_sk32: *const u8, input_hash32: *const u8, scan_pkx32: *const u8,
+        scan_pky32: *const u8, spend_pkx32: *const u8, spend_pky32: *const u8, k: *const u32, out_pk32: *mut u8, count: usize,
+        err: *mut u8) -> i64;
+    pub fn p2e_sp_scan_batch(ctx: *mut P2eCtx, scan_sk32: *const u8, spend_pkx32: *const u8, spend_pky32: *const u8,
+        label_x32: *const u8, label_y32: *const u8, n_labels: usize, ax32: *const u8, ay32: *const u8, input_hash32: *const u8,
+        outputs32: *const u8, out_offsets: *const u64, max_hits: usize, n_hits: *mut u8, hit_output: *mut u32, hit_label: *mut u8,
+        hit_tweak32: *mut u8, count: usize, err: *mut u8) -> i64;
+
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
         pky32: *mut u8) -> i32;
