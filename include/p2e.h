@@ -21,8 +21,8 @@
  *
  * BUFFER OVERLAP
  *   What a call may be handed when an output buffer shares bytes with another argument.  The rule below holds for the
- *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_sp_scan_batch (keys, signing,
- *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, Taproot, silent payments) and the two verdict-only
+ *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_musig_sig_agg_batch (keys, signing,
+ *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, Taproot, silent payments, MuSig2) and the two verdict-only
  *   verifiers p2e_ecdsa_verify_batch and p2e_p256_verify_batch.  It is checked on the host, behind the call's other argument
  *   checks and before the context is looked at, and it is the same with P2E_CTX_HOST_POINTERS (staging would hide the race;
  *   the contract does not depend on the mode).
@@ -45,6 +45,7 @@
  *        p2e_taproot_merkle_root_batch         root32 = leaf32
  *        p2e_sp_input_hash_batch               input_hash32 = ax32;   p2e_sp_send_batch   out_pk32 = input_hash32
  *            (p2e_sp_scan_batch offers no in-place form: every overlap of one of its outputs is refused)
+ *        p2e_musig_apply_tweak_batch           keyagg192_out = keyagg192_in   (the only in-place form of the seven MuSig2 calls)
  *   3. Any other intersection of an output with an input is P2E_E_INVALID, with "overlap" and the two argument names in
  *      p2e_last_error(): a shifted overlap (out == in + 32), different bytes per element (r32 on the 64-byte data of
  *      P2E_SIG_COMPACT64, addr20 on pkx32), and every input that lanes other than "its own" read -- the single parent of a
@@ -1104,6 +1105,101 @@ long p2e_sp_scan_batch(p2e_ctx *ctx, const uint8_t *scan_sk32 /* 1 */, const uin
                        const uint8_t *outputs32, const uint64_t *out_offsets /* count + 1, in outputs */, size_t max_hits,
                        uint8_t *n_hits, uint32_t *hit_output, uint8_t *hit_label, uint8_t *hit_tweak32, size_t count,
                        uint8_t *err);
+
+/* ---- MuSig2 (BIP-327) on secp256k1 (csrc/musig.hpp): the multi-party form of a BIP-340 signature, from the key list to the
+ * final signature.  A co-signer does per session what these seven calls do per element: hash a key list, multiply general
+ * points by 256-bit coefficients, combine nonces, produce or check a partial signature.  The finished sig64 is an ordinary
+ * BIP-340 signature under agg_pk32: p2e_schnorr_verify_batch accepts it.
+ *   count    The batch size of these seven calls is named `count`, as for the Taproot and silent-payment calls and for the
+ *            same reason.  They carry their span table in tests/test_musig_cpu.py.  BUFFER OVERLAP holds in full; every body
+ *            reads all inputs of element i before its first store.  The ONE in-place form is p2e_musig_apply_tweak_batch's
+ *            keyagg192_out = keyagg192_in; every other overlap of an output is P2E_E_INVALID.
+ *   bytes    TWO orders, as for the silent-payment calls.  Points and secret scalars of the key layer are the library's
+ *            LITTLE-endian 32-byte values (they chain with p2e_bip32_* and p2e_ecdsa_public_key_batch): pkx32 / pky32, sk32,
+ *            secnonce64 = k_1 || k_2, pubnonce128 and aggnonce128 = x(R_1) || y(R_1) || x(R_2) || y(R_2).  A signer's
+ *            public nonce is what p2e_ecdsa_public_key_batch returns for k_1 and k_2.  Hashes, tweak32, msg32, psig32,
+ *            agg_pk32 and sig64 are the standard's BIG-endian strings.  (0, 0) is the point at infinity where one is legal:
+ *            the two halves of an AGGREGATE nonce only.  Every array is 4-byte aligned but the one-byte ones.
+ *   signers  key_offsets has count + 1 uint64 elements, in SIGNERS, not bytes: session i owns the signers
+ *            [key_offsets[i], key_offsets[i + 1]) of a per-signer array (pkx32 / pky32 of the key aggregation, pubnonce128 of the
+ *            nonce aggregation, psig32 of the signature aggregation).  A session with no signer, with more than
+ *            P2E_MUSIG_MAX_SIGNERS, or with key_offsets[i + 1] < key_offsets[i] is P2E_WIRE_BAD_LENGTH.  A per-signer array has
+ *            an extent only the device knows (BUFFER OVERLAP 5); with host pointers the signers [key_offsets[0],
+ *            key_offsets[count]) are staged, and an offset outside that range is P2E_E_INVALID.
+ *   hashes   H_tag(x) = SHA256(SHA256(tag) || SHA256(tag) || x); cbytes(P) the 33-byte compressed point, cbytes_ext the same
+ *            with 33 zero bytes for the point at infinity, xbytes(P) the 32-byte x.
+ *              pk2 = the first key whose cbytes differ from pk_1's (none where all keys are equal)
+ *              L   = H_"KeyAgg list"(cbytes(pk_1) || .. || cbytes(pk_u))
+ *              a_i = 1 if cbytes(pk_i) == cbytes(pk2), else int(H_"KeyAgg coefficient"(L || cbytes(pk_i))) mod n
+ *              Q   = sum a_i P_i;   gacc = 1, tacc = 0
+ *              tweak: g = n - 1 if x-only and y(Q) odd, else 1;  Q' = g Q + t G, gacc' = g gacc, tacc' = t + g tacc mod n
+ *              b   = int(H_"MuSig/noncecoef"(cbytes_ext(R_1) || cbytes_ext(R_2) || xbytes(Q) || msg)) mod n
+ *              R   = R_1 + b R_2, or G where that is the point at infinity;  e = int(H_"BIP0340/challenge"(xbytes(R) || xbytes(Q) || msg)) mod n
+ *              s_i = k_1' + b k_2' + e a_i g gacc d_i mod n  (k' = n - k where y(R) is odd, g from the parity of y(Q))
+ *              s   = sum s_i + e g tacc mod n;  sig64 = xbytes(R) || bytes(s)
+ *   keyagg192   +0 x(Q), +32 y(Q) little-endian; +64 tacc big-endian; +96 L; +128 x of pk2 big-endian (zeros where there is
+ *            none); +160 uint32 flags: bit 0 = gacc is n - 1, bit 1 = pk2 present, bit 2 = y(pk2) odd; +164 .. 191 zero.  A call
+ *            that reads a record checks it, in this order: the point ((0, 0), which is what a flagged element left:
+ *            P2E_WIRE_INFINITY; a coordinate >= p: P2E_WIRE_COORD_RANGE; off the curve: P2E_WIRE_NOT_ON_CURVE), tacc >= n:
+ *            P2E_WIRE_SCALAR_RANGE, x(pk2) >= p: P2E_WIRE_COORD_RANGE, an unknown flag bit: P2E_WIRE_BAD_PREFIX.
+ *   session128  +0 b, +32 e big-endian; +64 xbytes(R); +96 uint32 flags: bit 0 = y(R) odd; +100 .. 127 zero.  Checked where it
+ *            is read: b or e >= n: P2E_WIRE_SCALAR_RANGE; xbytes(R) all zero (a flagged element's): P2E_WIRE_INFINITY;
+ *            x(R) >= p: P2E_WIRE_COORD_RANGE; an unknown flag bit: P2E_WIRE_BAD_PREFIX.
+ *   err[i]   a P2E_WIRE_* CODE: the first failing check in the order given below; a flagged element writes zeros to all its
+ *            outputs, so a flag travels down the chain (the next call finds a zeroed record).  The return value counts the
+ *            flagged elements; count == 0 returns 0.  Null pointers, host pointers, async mode, the current device and failed
+ *            calls behave as for the Taproot calls.  A point that must not be (0, 0) is checked as p2e_point_mul_batch would
+ *            flag it: (0, 0): P2E_WIRE_INFINITY; a coordinate >= p: P2E_WIRE_COORD_RANGE; off the curve:
+ *            P2E_WIRE_NOT_ON_CURVE.  Nothing >= n is ever reduced silently.
+ *   p2e_musig_key_agg_batch   The length; the keys in their order (the first failing key gives the code); Q at infinity:
+ *            P2E_WIRE_INFINITY.  agg_pk32 = xbytes(Q).
+ *   p2e_musig_apply_tweak_batch   mode P2E_MUSIG_TWEAK_PLAIN: t = tweak32, g = 1; P2E_MUSIG_TWEAK_XONLY: t = tweak32, x-only;
+ *            P2E_MUSIG_TWEAK_TAPROOT: x-only with t = int(H_"TapTweak"(xbytes(Q) || tweak32)), tweak32 the Merkle root, or, with
+ *            tweak32 == NULL, nothing appended (BIP-86's key-path-only output) -- the key p2e_taproot_tweak_pubkey_batch gives
+ *            for agg_pk32.  Any other mode, or a null tweak32 in modes 0 and 1, is P2E_E_INVALID.  The record; t >= n:
+ *            P2E_WIRE_SCALAR_RANGE; Q' at infinity: P2E_WIRE_INFINITY.  Tweaks are applied one call after the other.
+ *   p2e_musig_nonce_agg_batch   The length; per signer R_1 then R_2, neither may be (0, 0).  A sum at infinity is (0, 0), no error.
+ *   p2e_musig_session_batch   The record; R_1 then R_2 of the aggregate nonce, each (0, 0) or on the curve.
+ *   p2e_musig_partial_sign_batch   One lane per session, for the caller's own signer in it.  In order: k_1, k_2, sk32 (each 0 or
+ *            >= n: P2E_WIRE_SCALAR_RANGE), the key record, the session record.  The signer's key d' G is computed here and its
+ *            coefficient is taken from L and pk2 of the record.  k_1, k_2, d' and every product of them never leave the lane's
+ *            registers.  TWO departures from the standard's Sign: secnonce64 carries no public key, so checking that the nonce
+ *            was made for this key is the caller's; and the library cannot know whether d' G is in the key list (a key that is
+ *            not gets a hashed coefficient like any other, and the aggregate signature does not verify).
+ *            Checking the result with p2e_musig_partial_verify_batch catches both.  A SECRET NONCE MUST NEVER BE USED TWICE:
+ *            two partial signatures with one secnonce64 under different b or e reveal the secret key.  The library keeps no
+ *            state and cannot detect reuse; wipe secnonce64 after the call.
+ *   p2e_musig_partial_verify_batch   One lane per partial signature; its session is session_index[i] (NULL: i) of the n_sessions
+ *            records.  In order: session_index[i] >= n_sessions: P2E_WIRE_BAD_INDEX; psig32 >= n: P2E_WIRE_SCALAR_RANGE; R_1, R_2
+ *            of the signer's pubnonce128; the signer's key; the key record; the session record.  valid[i] = 1 iff
+ *            s G == Re + (e a g gacc mod n) P with Re = R_1 + b R_2, negated where y(R) is odd; 0 where err[i] != 0 (every
+ *            element is written, as by p2e_schnorr_verify_batch).  n_sessions == 0 is P2E_E_INVALID.
+ *   p2e_musig_sig_agg_batch   The length; the key record; the session record; the partial signatures in their order (>= n:
+ *            P2E_WIRE_SCALAR_RANGE).
+ * Each call is one kernel on the context's caller stream, one lane per element: no internal streams, no scratch. */
+#define P2E_MUSIG_MAX_SIGNERS 1024
+#define P2E_MUSIG_TWEAK_PLAIN 0
+#define P2E_MUSIG_TWEAK_XONLY 1
+#define P2E_MUSIG_TWEAK_TAPROOT 2
+long p2e_musig_key_agg_batch(p2e_ctx *ctx, const uint8_t *pkx32 /* per signer */, const uint8_t *pky32 /* per signer */,
+                             const uint64_t *key_offsets /* count + 1, in signers */, uint8_t *keyagg192, uint8_t *agg_pk32,
+                             size_t count, uint8_t *err);
+long p2e_musig_apply_tweak_batch(p2e_ctx *ctx, const uint8_t *keyagg192_in, const uint8_t *tweak32 /* nullable in mode 2 */,
+                                 int mode, uint8_t *keyagg192_out, uint8_t *agg_pk32, size_t count, uint8_t *err);
+long p2e_musig_nonce_agg_batch(p2e_ctx *ctx, const uint8_t *pubnonce128 /* per signer */,
+                               const uint64_t *key_offsets /* count + 1, in signers */, uint8_t *aggnonce128, size_t count,
+                               uint8_t *err);
+long p2e_musig_session_batch(p2e_ctx *ctx, const uint8_t *keyagg192, const uint8_t *aggnonce128, const uint8_t *msg32,
+                             uint8_t *session128, size_t count, uint8_t *err);
+long p2e_musig_partial_sign_batch(p2e_ctx *ctx, const uint8_t *secnonce64, const uint8_t *sk32, const uint8_t *keyagg192,
+                                  const uint8_t *session128, uint8_t *psig32, size_t count, uint8_t *err);
+long p2e_musig_partial_verify_batch(p2e_ctx *ctx, const uint8_t *psig32, const uint8_t *pubnonce128, const uint8_t *pkx32,
+                                    const uint8_t *pky32, const uint32_t *session_index /* nullable: identity */,
+                                    const uint8_t *keyagg192 /* n_sessions */, const uint8_t *session128 /* n_sessions */,
+                                    size_t n_sessions, size_t count, uint8_t *err, uint8_t *valid);
+long p2e_musig_sig_agg_batch(p2e_ctx *ctx, const uint8_t *psig32 /* per signer */,
+                             const uint64_t *key_offsets /* count + 1, in signers */, const uint8_t *keyagg192,
+                             const uint8_t *session128, uint8_t *sig64, size_t count, uint8_t *err);
 
 /* ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40 sign_message with
  * sk, msg, nonce drawn from splitmix64(seed, i).  Host buffers of n*32 bytes each. -------------------- */

@@ -49,6 +49,8 @@ MSM_OK, MSM_NEUTRAL, MSM_BAD_POINT = 0, 1, 2               # include/p2e.h P2E_M
 WIRE_BAD_INDEX = 10                                        # the three point-table calls: idx[i] >= the table's point count
 POINT_TABLE_MAX_POINTS, POINT_TABLE_BYTES_PER_POINT = 65536, 67584   # include/p2e.h P2E_POINT_TABLE_*
 MUL_PLAN_AUTO, MUL_PLAN_PLAIN, MUL_PLAN_GLV = 0, 1, 2       # include/p2e.h P2E_MUL_PLAN_* (point_mul_batch, point_lincomb_batch)
+MUSIG_MAX_SIGNERS = 1024                                   # include/p2e.h P2E_MUSIG_MAX_SIGNERS
+MUSIG_TWEAK_PLAIN, MUSIG_TWEAK_XONLY, MUSIG_TWEAK_TAPROOT = 0, 1, 2   # include/p2e.h P2E_MUSIG_TWEAK_*
 SEC1_COMPRESSED, SEC1_UNCOMPRESSED = 0, 1                  # include/p2e.h P2E_SEC1_*
 SIG_DER, SIG_COMPACT64, SIG_COMPACT65 = 0, 1, 2            # include/p2e.h P2E_SIG_*
 SIG_REQUIRE_LOW_S, SIG_NORMALIZE_S = 1, 2
@@ -105,6 +107,8 @@ EXPORTS = (
     "p2e_taproot_leaf_hash_batch", "p2e_taproot_merkle_root_batch", "p2e_taproot_tweak_pubkey_batch", "p2e_taproot_tweak_seckey_batch",
     "p2e_taproot_verify_commitment_batch",
     "p2e_sp_input_hash_batch", "p2e_sp_label_batch", "p2e_sp_send_batch", "p2e_sp_scan_batch",
+    "p2e_musig_key_agg_batch", "p2e_musig_apply_tweak_batch", "p2e_musig_nonce_agg_batch", "p2e_musig_session_batch",
+    "p2e_musig_partial_sign_batch", "p2e_musig_partial_verify_batch", "p2e_musig_sig_agg_batch",
 )
 
 
@@ -1487,6 +1491,81 @@ class Context:
                                                     C.c_size_t(max_hits), _ptr(n_hits), _ptr(hit_output), _ptr(hit_label), _ptr(hit_tweak),
                                                     C.c_size_t(n), _ptr(err)))
         return n_hits, hit_output, hit_label, hit_tweak, err, bad
+
+    # ---- MuSig2 on secp256k1 (include/p2e.h p2e_musig_key_agg_batch and the six calls after it) ------------------------------------
+    # Points, secret keys and nonces are little-endian as in the BIP-32 calls (a public nonce is (n, 128) = x(R_1) || y(R_1) ||
+    # x(R_2) || y(R_2)); tweaks, messages, partial signatures, agg_pk and sig are the standard's big-endian byte strings; keyagg
+    # is the (n, 192) record and session the (n, 128) record of the header.  key_offsets is (n + 1,) 64-bit, in signers.
+    def musig_key_agg_batch(self, pkx, pky, key_offsets, keyagg=None, agg_pk=None, err=None):
+        """KeyAgg of n sessions: session i owns the keys pkx / pky[key_offsets[i]:key_offsets[i + 1]] ((total, 32)):
+        (keyagg (n, 192), agg_pk (n, 32) big-endian, err, flagged count)."""
+        n = self._shape(key_offsets)[0] - 1
+        keyagg = keyagg if keyagg is not None else self._bytes(n, 192)
+        agg_pk = agg_pk if agg_pk is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_musig_key_agg_batch(self._h, _ptr(pkx), _ptr(pky), _ptr(key_offsets), _ptr(keyagg), _ptr(agg_pk),
+                                                          C.c_size_t(n), _ptr(err)))
+        return keyagg, agg_pk, err, bad
+
+    def musig_apply_tweak_batch(self, keyagg, tweak, mode, keyagg_out=None, agg_pk=None, err=None):
+        """ApplyTweak: mode MUSIG_TWEAK_PLAIN / MUSIG_TWEAK_XONLY with the tweaks tweak (n, 32) big-endian, or MUSIG_TWEAK_TAPROOT with
+        tweak the Merkle roots or None (BIP-86).  keyagg_out may be keyagg itself: (keyagg_out, agg_pk, err, flagged count)."""
+        n = self._shape(keyagg)[0]
+        keyagg_out = keyagg_out if keyagg_out is not None else self._bytes(n, 192)
+        agg_pk = agg_pk if agg_pk is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_musig_apply_tweak_batch(self._h, _ptr(keyagg), _ptr(tweak), C.c_int(mode), _ptr(keyagg_out), _ptr(agg_pk),
+                                                              C.c_size_t(n), _ptr(err)))
+        return keyagg_out, agg_pk, err, bad
+
+    def musig_nonce_agg_batch(self, pubnonce, key_offsets, aggnonce=None, err=None):
+        """NonceAgg: session i sums the public nonces pubnonce[key_offsets[i]:key_offsets[i + 1]] ((total, 128)):
+        (aggnonce (n, 128), err, flagged count)."""
+        n = self._shape(key_offsets)[0] - 1
+        aggnonce = aggnonce if aggnonce is not None else self._bytes(n, 128)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_musig_nonce_agg_batch(self._h, _ptr(pubnonce), _ptr(key_offsets), _ptr(aggnonce), C.c_size_t(n), _ptr(err)))
+        return aggnonce, err, bad
+
+    def musig_session_batch(self, keyagg, aggnonce, msg, session=None, err=None):
+        """The session values b, e and R of n sessions: (session (n, 128), err, flagged count)."""
+        n = self._shape(keyagg)[0]
+        session = session if session is not None else self._bytes(n, 128)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_musig_session_batch(self._h, _ptr(keyagg), _ptr(aggnonce), _ptr(msg), _ptr(session), C.c_size_t(n),
+                                                          _ptr(err)))
+        return session, err, bad
+
+    def musig_partial_sign_batch(self, secnonce, sk, keyagg, session, psig=None, err=None):
+        """The caller's partial signature in each of n sessions from secnonce (n, 64) = k_1 || k_2 and sk (n, 32), little-endian.
+        A secret nonce must never be used twice.  (psig (n, 32) big-endian, err, flagged count)."""
+        n = self._shape(sk)[0]
+        psig = psig if psig is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_musig_partial_sign_batch(self._h, _ptr(secnonce), _ptr(sk), _ptr(keyagg), _ptr(session), _ptr(psig),
+                                                               C.c_size_t(n), _ptr(err)))
+        return psig, err, bad
+
+    def musig_partial_verify_batch(self, psig, pubnonce, pkx, pky, keyagg, session, session_index=None, err=None, valid=None):
+        """PartialSigVerify of n partial signatures; signature i belongs to session session_index[i] ((n,) 32-bit; None: i) of the
+        records keyagg / session: (err, valid, flagged count)."""
+        n = self._shape(psig)[0]
+        err = err if err is not None else self._vec(n, np.uint8)
+        valid = valid if valid is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_musig_partial_verify_batch(self._h, _ptr(psig), _ptr(pubnonce), _ptr(pkx), _ptr(pky), _ptr(session_index),
+                                                                 _ptr(keyagg), _ptr(session), C.c_size_t(self._shape(keyagg)[0]), C.c_size_t(n),
+                                                                 _ptr(err), _ptr(valid)))
+        return err, valid, bad
+
+    def musig_sig_agg_batch(self, psig, key_offsets, keyagg, session, sig=None, err=None):
+        """PartialSigAgg: session i sums psig[key_offsets[i]:key_offsets[i + 1]] ((total, 32) big-endian): (sig (n, 64), err,
+        flagged count).  p2e_schnorr_verify_batch accepts sig under the session's agg_pk."""
+        n = self._shape(key_offsets)[0] - 1
+        sig = sig if sig is not None else self._bytes(n, 64)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_musig_sig_agg_batch(self._h, _ptr(psig), _ptr(key_offsets), _ptr(keyagg), _ptr(session), _ptr(sig),
+                                                          C.c_size_t(n), _ptr(err)))
+        return sig, err, bad
 
     # ---- hashing, RFC 6979 nonces, the deterministic signer, addresses (include/p2e.h p2e_hash_batch and the three after it) ----
     def hash_batch(self, data, offsets, alg=HASH_SHA256, out_form=DIGEST_BYTES, out=None):

@@ -34,6 +34,7 @@
 #include "schnorr.hpp"
 #include "taproot.hpp"
 #include "sp.hpp"
+#include "musig.hpp"
 #include "hd.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
@@ -45,7 +46,7 @@ using host::COMPACT_WIDE;
 // because a single hipcc job over all kernels takes five minutes:  0 = context, single generators, layout helpers,
 // streaming passes, descriptions;  1 = the fused pipeline of the two built-in programs (run_program);  2 / 3 = the
 // curve-program pipeline instantiated for secp256k1 / P-256 (run_curve_program<CV>).  Undefined = everything in one
-// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 and Taproot kernels (schnorr.hpp, taproot.hpp) ride in part 3; the BIP-32 and HASH160 kernels (hd.hpp) ride in part 1 with the other hashes, and so do the silent-payment kernels (sp.hpp), beside the point multiplication whose walk they hold.  Small static helpers (error text, staging, scratch) are compiled into every part.
+// unit.  The hashing, nonce and address kernels (hash.hpp) and the key and signature codecs (wire.hpp) ride in part 1, the part that builds fastest; the BIP-340 and Taproot kernels (schnorr.hpp, taproot.hpp) ride in part 3; the BIP-32 and HASH160 kernels (hd.hpp) ride in part 1 with the other hashes, and so do the silent-payment and MuSig2 kernels (sp.hpp, musig.hpp), beside the point multiplication whose walk they hold.  Small static helpers (error text, staging, scratch) are compiled into every part.
 #ifndef P2E_PART
 #define P2E_PART (-1)
 #endif
@@ -3617,6 +3618,205 @@ extern "C" long p2e_sp_scan_batch(p2e_ctx* c, const uint8_t* scan_sk32, const ui
     if (long rc = S.begin(args)) return rc;
     launch_sp_scan(c, table, scan_sk32, spend_pkx32, spend_pky32, n_labels ? label_x32 : nullptr, n_labels ? label_y32 : nullptr, n_labels, ax32,
                    ay32, input_hash32, outputs32, out_offsets, max_hits, n_hits, hit_output, hit_label, hit_tweak32, count, err);
+    return S.end();
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// MuSig2 (BIP-327) on secp256k1 (musig.hpp): key aggregation, tweaks, nonce aggregation, session values, partial signatures,
+// their verification and the final signature
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 1 beside the point multiplication, called from part 0
+void launch_musig_key_agg(p2e_ctx* c, const uint8_t* pkx, const uint8_t* pky, const uint64_t* key_offsets, uint8_t* keyagg, uint8_t* agg_pk,
+                          size_t count, uint8_t* err);
+void launch_musig_apply_tweak(p2e_ctx* c, const Aff* table, const uint8_t* keyagg_in, const uint8_t* tweak, int mode, uint8_t* keyagg_out,
+                              uint8_t* agg_pk, size_t count, uint8_t* err);
+void launch_musig_nonce_agg(p2e_ctx* c, const uint8_t* pubnonce, const uint64_t* key_offsets, uint8_t* aggnonce, size_t count, uint8_t* err);
+void launch_musig_session(p2e_ctx* c, const Aff* table, const uint8_t* keyagg, const uint8_t* aggnonce, const uint8_t* msg, uint8_t* session,
+                          size_t count, uint8_t* err);
+void launch_musig_partial_sign(p2e_ctx* c, const Aff* table, const uint8_t* secnonce, const uint8_t* sk, const uint8_t* keyagg,
+                               const uint8_t* session, uint8_t* psig, size_t count, uint8_t* err);
+void launch_musig_partial_verify(p2e_ctx* c, const Aff* table, const uint8_t* psig, const uint8_t* pubnonce, const uint8_t* pkx,
+                                 const uint8_t* pky, const uint32_t* session_index, const uint8_t* keyagg, const uint8_t* session,
+                                 size_t n_sessions, size_t count, uint8_t* err, uint8_t* valid);
+void launch_musig_sig_agg(p2e_ctx* c, const uint8_t* psig, const uint64_t* key_offsets, const uint8_t* keyagg, const uint8_t* session,
+                          uint8_t* sig, size_t count, uint8_t* err);
+#if P2E_HAS(1)
+void launch_musig_key_agg(p2e_ctx* c, const uint8_t* pkx, const uint8_t* pky, const uint64_t* key_offsets, uint8_t* keyagg, uint8_t* agg_pk,
+                          size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_musig_key_agg<0>), grid1(count), dim3(BS), 0, c->stream, pkx, pky, key_offsets, keyagg, agg_pk, count, err,
+                       c->d_counter);
+}
+void launch_musig_apply_tweak(p2e_ctx* c, const Aff* table, const uint8_t* keyagg_in, const uint8_t* tweak, int mode, uint8_t* keyagg_out,
+                              uint8_t* agg_pk, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_musig_apply_tweak<0>), grid1(count), dim3(BS), 0, c->stream, table, keyagg_in, tweak, mode, keyagg_out, agg_pk, count,
+                       err, c->d_counter);
+}
+void launch_musig_nonce_agg(p2e_ctx* c, const uint8_t* pubnonce, const uint64_t* key_offsets, uint8_t* aggnonce, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_musig_nonce_agg<0>), grid1(count), dim3(BS), 0, c->stream, pubnonce, key_offsets, aggnonce, count, err, c->d_counter);
+}
+void launch_musig_session(p2e_ctx* c, const Aff* table, const uint8_t* keyagg, const uint8_t* aggnonce, const uint8_t* msg, uint8_t* session,
+                          size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_musig_session<0>), grid1(count), dim3(BS), 0, c->stream, table, keyagg, aggnonce, msg, session, count, err,
+                       c->d_counter);
+}
+void launch_musig_partial_sign(p2e_ctx* c, const Aff* table, const uint8_t* secnonce, const uint8_t* sk, const uint8_t* keyagg,
+                               const uint8_t* session, uint8_t* psig, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_musig_partial_sign<0>), grid1(count), dim3(BS), 0, c->stream, table, secnonce, sk, keyagg, session, psig, count, err,
+                       c->d_counter);
+}
+void launch_musig_partial_verify(p2e_ctx* c, const Aff* table, const uint8_t* psig, const uint8_t* pubnonce, const uint8_t* pkx,
+                                 const uint8_t* pky, const uint32_t* session_index, const uint8_t* keyagg, const uint8_t* session,
+                                 size_t n_sessions, size_t count, uint8_t* err, uint8_t* valid) {
+    hipLaunchKernelGGL((k_musig_partial_verify<0>), grid1(count), dim3(BS), 0, c->stream, table, psig, pubnonce, pkx, pky, session_index, keyagg,
+                       session, n_sessions, count, err, valid, c->d_counter);
+}
+void launch_musig_sig_agg(p2e_ctx* c, const uint8_t* psig, const uint64_t* key_offsets, const uint8_t* keyagg, const uint8_t* session,
+                          uint8_t* sig, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_musig_sig_agg<0>), grid1(count), dim3(BS), 0, c->stream, psig, key_offsets, keyagg, session, sig, count, err,
+                       c->d_counter);
+}
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+// One per-signer array of a staged call (`stride` bytes per signer): the copy holds signers [key_offsets[0], key_offsets[count])
+// and `p` becomes that copy moved back by stride * key_offsets[0], as sp_stage_outputs does for the outputs of a scan.  The
+// offsets are checked once per call (`check`), the array against the call's outputs every time.  false: the error text is set.
+static bool musig_stage_signers(Staged& S, Args args, const char* name, const uint8_t*& p, size_t stride, const uint64_t* key_offsets,
+                                size_t count, bool check) {
+    if (!S.host) return true;
+    const uint64_t first = key_offsets[0], last = key_offsets[count];
+    if (check) {
+        if (last < first || last > ((uint64_t)1 << 48)) {
+            set_error("key_offsets[count] < key_offsets[0], or beyond 2^48 signers");
+            return false;
+        }
+        for (size_t i = 0; i <= count; i++)
+            if (key_offsets[i] < first || key_offsets[i] > last) {
+                set_error("an element of key_offsets lies outside [key_offsets[0], key_offsets[count]]");
+                return false;
+            }
+    }
+    overlap::Span spans[call_args::kMaxBufs + 1];
+    size_t num = 0;
+    for (size_t i = 0, all = call_args::spans(args, count, spans); i < all; i++)
+        if (spans[i].is_output) spans[num++] = spans[i];
+    spans[num++] = overlap::Span{name, p + stride * first, stride, (size_t)(last - first), false, true};   // (no lane owns a byte of it)
+    if (const overlap::Clash k = overlap::check(spans, num); k.bad) {
+        set_error(std::string("overlap: ") + k.a + " and " + k.b + " share bytes (per-signer data may not touch an output)");
+        return false;
+    }
+    const uint8_t* d = S.in(p + stride * first, stride * (size_t)(last - first));
+    p = d ? d - stride * first : nullptr;
+    return true;
+}
+// (the batch size of these seven calls is `count`: see include/p2e.h)
+extern "C" long p2e_musig_key_agg_batch(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, const uint64_t* key_offsets, uint8_t* keyagg192,
+                                        uint8_t* agg_pk32, size_t count, uint8_t* err) {
+    const Args args = {ARG_OPAQUE(pkx32), ARG_OPAQUE(pky32), ARG_SHARED(key_offsets, 8, count + 1), ARG_OUT(keyagg192, 192, count),
+                       ARG_OUT(agg_pk32, 32, count), ARG_OUT(err, 1, count)};
+    if (missing(args) || batch_too_large(count) || bad_overlap(count, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (!musig_stage_signers(S, args, "pkx32", pkx32, 32, key_offsets, count, true) ||
+        !musig_stage_signers(S, args, "pky32", pky32, 32, key_offsets, count, false))
+        return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
+    launch_musig_key_agg(c, pkx32, pky32, key_offsets, keyagg192, agg_pk32, count, err);
+    return S.end();
+}
+extern "C" long p2e_musig_apply_tweak_batch(p2e_ctx* c, const uint8_t* keyagg192_in, const uint8_t* tweak32, int mode, uint8_t* keyagg192_out,
+                                            uint8_t* agg_pk32, size_t count, uint8_t* err) {
+    const Args args = {ARG_IN(keyagg192_in, 192, count), P2E_ARG(tweak32, 32, count, Shared, mode != P2E_MUSIG_TWEAK_TAPROOT),
+                       ARG_OUT(keyagg192_out, 192, count), ARG_OUT(agg_pk32, 32, count), ARG_OUT(err, 1, count)};
+    if (mode != P2E_MUSIG_TWEAK_PLAIN && mode != P2E_MUSIG_TWEAK_XONLY && mode != P2E_MUSIG_TWEAK_TAPROOT) {
+        set_error("unknown mode (P2E_MUSIG_TWEAK_PLAIN, P2E_MUSIG_TWEAK_XONLY or P2E_MUSIG_TWEAK_TAPROOT)");
+        return P2E_E_INVALID;
+    }
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_musig_apply_tweak(c, table, keyagg192_in, tweak32, mode, keyagg192_out, agg_pk32, count, err);
+    return S.end();
+}
+extern "C" long p2e_musig_nonce_agg_batch(p2e_ctx* c, const uint8_t* pubnonce128, const uint64_t* key_offsets, uint8_t* aggnonce128,
+                                          size_t count, uint8_t* err) {
+    const Args args = {ARG_OPAQUE(pubnonce128), ARG_SHARED(key_offsets, 8, count + 1), ARG_OUT(aggnonce128, 128, count), ARG_OUT(err, 1, count)};
+    if (missing(args) || batch_too_large(count) || bad_overlap(count, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (!musig_stage_signers(S, args, "pubnonce128", pubnonce128, 128, key_offsets, count, true)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
+    launch_musig_nonce_agg(c, pubnonce128, key_offsets, aggnonce128, count, err);
+    return S.end();
+}
+extern "C" long p2e_musig_session_batch(p2e_ctx* c, const uint8_t* keyagg192, const uint8_t* aggnonce128, const uint8_t* msg32,
+                                        uint8_t* session128, size_t count, uint8_t* err) {
+    const Args args = {ARG_SHARED(keyagg192, 192, count), ARG_SHARED(aggnonce128, 128, count), ARG_SHARED(msg32, 32, count),
+                       ARG_OUT(session128, 128, count), ARG_OUT(err, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_musig_session(c, table, keyagg192, aggnonce128, msg32, session128, count, err);
+    return S.end();
+}
+extern "C" long p2e_musig_partial_sign_batch(p2e_ctx* c, const uint8_t* secnonce64, const uint8_t* sk32, const uint8_t* keyagg192,
+                                             const uint8_t* session128, uint8_t* psig32, size_t count, uint8_t* err) {
+    const Args args = {ARG_SHARED(secnonce64, 64, count),   ARG_SHARED(sk32, 32, count), ARG_SHARED(keyagg192, 192, count),
+                       ARG_SHARED(session128, 128, count), ARG_OUT(psig32, 32, count),  ARG_OUT(err, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_musig_partial_sign(c, table, secnonce64, sk32, keyagg192, session128, psig32, count, err);
+    return S.end();
+}
+extern "C" long p2e_musig_partial_verify_batch(p2e_ctx* c, const uint8_t* psig32, const uint8_t* pubnonce128, const uint8_t* pkx32,
+                                               const uint8_t* pky32, const uint32_t* session_index, const uint8_t* keyagg192,
+                                               const uint8_t* session128, size_t n_sessions, size_t count, uint8_t* err, uint8_t* valid) {
+    // (a refused n_sessions has the extent 0, so that no product can overflow)
+    const size_t sessions = n_sessions <= ((size_t)1 << 32) ? n_sessions : 0;
+    const Args args = {ARG_SHARED(psig32, 32, count),
+                       ARG_SHARED(pubnonce128, 128, count),
+                       ARG_SHARED(pkx32, 32, count),
+                       ARG_SHARED(pky32, 32, count),
+                       P2E_ARG(session_index, 4, count, Shared, false),
+                       ARG_SHARED(keyagg192, 192, sessions),
+                       ARG_SHARED(session128, 128, sessions),
+                       ARG_OUT(err, 1, count),
+                       ARG_OUT(valid, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    if (n_sessions == 0 || n_sessions > ((size_t)1 << 32)) {
+        set_error("n_sessions must be 1 .. 2^32");
+        return P2E_E_INVALID;
+    }
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_musig_partial_verify(c, table, psig32, pubnonce128, pkx32, pky32, session_index, keyagg192, session128, n_sessions, count, err,
+                                valid);
+    return S.end();
+}
+extern "C" long p2e_musig_sig_agg_batch(p2e_ctx* c, const uint8_t* psig32, const uint64_t* key_offsets, const uint8_t* keyagg192,
+                                        const uint8_t* session128, uint8_t* sig64, size_t count, uint8_t* err) {
+    const Args args = {ARG_OPAQUE(psig32),          ARG_SHARED(key_offsets, 8, count + 1), ARG_SHARED(keyagg192, 192, count), ARG_SHARED(session128, 128, count),
+                       ARG_OUT(sig64, 64, count), ARG_OUT(err, 1, count)};
+    if (missing(args) || batch_too_large(count) || bad_overlap(count, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (!musig_stage_signers(S, args, "psig32", psig32, 32, key_offsets, count, true)) return S.done(P2E_E_INVALID);
+    if (long rc = S.begin(args)) return rc;
+    launch_musig_sig_agg(c, psig32, key_offsets, keyagg192, session128, sig64, count, err);
     return S.end();
 }
 #endif   // P2E_HAS(0)

@@ -499,6 +499,126 @@ pub fn sp_scan(ctx: *mut P2eCtx, scan_sk: &[u8; 32], spend_pk: &([u8; 32], [u8; 
     }).collect())
 }
 
+/// The `keyagg192` record of a MuSig2 session (include/p2e.h): the aggregate key with its tweak accumulators.
+pub type MusigKeyAgg = [u8; 192];
+/// The `session128` record of a MuSig2 session: `b`, `e`, `xbytes(R)` and the parity of `y(R)`.
+pub type MusigSession = [u8; 128];
+/// A public or an aggregate nonce: `x(R_1) || y(R_1) || x(R_2) || y(R_2)`, little-endian.
+pub type MusigNonce = [u8; 128];
+
+/// `key_offsets` of per-session lists: the flattened items and the `count + 1` offsets, in items.
+fn musig_flatten<T: Clone>(lists: &[Vec<T>], pad: T) -> (Vec<T>, Vec<u64>) {
+    let (mut flat, mut offsets) = (Vec::new(), vec![0u64]);
+    for l in lists {
+        flat.extend_from_slice(l);
+        offsets.push(flat.len() as u64);
+    }
+    flat.push(pad); // never read: keeps the pointer of a batch without signers valid
+    (flat, offsets)
+}
+
+/// BIP-327 KeyAgg (`p2e_musig_key_agg_batch`, host-pointer context): per session the record and the big-endian x-only
+/// aggregate key of its public keys (little-endian `(x, y)`), or the `P2E_WIRE_*` code.
+pub fn musig_key_agg(ctx: *mut P2eCtx, keys: &[Vec<([u8; 32], [u8; 32])>]) -> Result<Vec<std::result::Result<(MusigKeyAgg, [u8; 32]), u8>>> {
+    let n = keys.len();
+    let (flat, offsets) = musig_flatten(keys, ([0u8; 32], [0u8; 32]));
+    let (x, y): (Vec<[u8; 32]>, Vec<[u8; 32]>) = flat.into_iter().unzip();
+    let (mut rec, mut pk, mut err) = (vec![[0u8; 192]; n], vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_musig_key_agg_batch(ctx, x.as_ptr().cast(), y.as_ptr().cast(), offsets.as_ptr(), rec.as_mut_ptr().cast(), pk.as_mut_ptr().cast(), n,
+                                err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok((rec[i], pk[i])) }).collect())
+}
+
+/// BIP-327 ApplyTweak (`p2e_musig_apply_tweak_batch`): `mode` is `P2E_MUSIG_TWEAK_PLAIN` (0), `_XONLY` (1) or `_TAPROOT` (2, where
+/// `tweaks` are Merkle roots, or `None` for BIP-86's key-path-only output).  Per session the new record and x-only key, or the code.
+pub fn musig_apply_tweak(ctx: *mut P2eCtx, records: &[MusigKeyAgg], tweaks: Option<&[[u8; 32]]>, mode: i32)
+                         -> Result<Vec<std::result::Result<(MusigKeyAgg, [u8; 32]), u8>>> {
+    let n = records.len();
+    ensure!(tweaks.map_or(mode == 2, |t| t.len() == n), "one tweak per session (none only in the Taproot mode)");
+    let tweak_ptr: *const u8 = tweaks.map_or(std::ptr::null(), |t| t.as_ptr().cast());
+    let (mut rec, mut pk, mut err) = (vec![[0u8; 192]; n], vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_musig_apply_tweak_batch(ctx, records.as_ptr().cast(), tweak_ptr, mode, rec.as_mut_ptr().cast(), pk.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok((rec[i], pk[i])) }).collect())
+}
+
+/// BIP-327 NonceAgg (`p2e_musig_nonce_agg_batch`): per session the sum of its signers' public nonces, or the code.
+pub fn musig_nonce_agg(ctx: *mut P2eCtx, nonces: &[Vec<MusigNonce>]) -> Result<Vec<std::result::Result<MusigNonce, u8>>> {
+    let n = nonces.len();
+    let (flat, offsets) = musig_flatten(nonces, [0u8; 128]);
+    let (mut agg, mut err) = (vec![[0u8; 128]; n], vec![0u8; n]);
+    let rc = unsafe { p2e_musig_nonce_agg_batch(ctx, flat.as_ptr().cast(), offsets.as_ptr(), agg.as_mut_ptr().cast(), n, err.as_mut_ptr()) };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(agg[i]) }).collect())
+}
+
+/// The session values of BIP-327 (`p2e_musig_session_batch`): per session the record of `b`, `e` and `R`, or the code.
+pub fn musig_sessions(ctx: *mut P2eCtx, records: &[MusigKeyAgg], aggnonces: &[MusigNonce], msgs: &[[u8; 32]])
+                      -> Result<Vec<std::result::Result<MusigSession, u8>>> {
+    let n = records.len();
+    ensure!(aggnonces.len() == n && msgs.len() == n);
+    let (mut ses, mut err) = (vec![[0u8; 128]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_musig_session_batch(ctx, records.as_ptr().cast(), aggnonces.as_ptr().cast(), msgs.as_ptr().cast(), ses.as_mut_ptr().cast(), n,
+                                err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(ses[i]) }).collect())
+}
+
+/// The caller's partial signatures (`p2e_musig_partial_sign_batch`), one per session: `secnonces[i] = k_1 || k_2` and `sk[i]`
+/// little-endian.  A secret nonce must never be used twice; both are secrets and the caller's to wipe.  Check the result with
+/// [`musig_partial_verify`]: the library cannot know whether the key is in the session's list.
+pub fn musig_partial_sign(ctx: *mut P2eCtx, secnonces: &[[u8; 64]], sk: &[[u8; 32]], records: &[MusigKeyAgg], sessions: &[MusigSession])
+                          -> Result<Vec<std::result::Result<[u8; 32], u8>>> {
+    let n = sk.len();
+    ensure!(secnonces.len() == n && records.len() == n && sessions.len() == n);
+    let (mut psig, mut err) = (vec![[0u8; 32]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_musig_partial_sign_batch(ctx, secnonces.as_ptr().cast(), sk.as_ptr().cast(), records.as_ptr().cast(), sessions.as_ptr().cast(),
+                                     psig.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(psig[i]) }).collect())
+}
+
+/// BIP-327 PartialSigVerify (`p2e_musig_partial_verify_batch`): partial signature `i` of the signer with the public nonce
+/// `pubnonces[i]` and the key `keys[i]`, in session `index[i]` of the records.  `Ok(valid)`, or the code.
+pub fn musig_partial_verify(ctx: *mut P2eCtx, psigs: &[[u8; 32]], pubnonces: &[MusigNonce], keys: &[([u8; 32], [u8; 32])], index: &[u32],
+                            records: &[MusigKeyAgg], sessions: &[MusigSession]) -> Result<Vec<std::result::Result<bool, u8>>> {
+    let n = psigs.len();
+    ensure!(pubnonces.len() == n && keys.len() == n && index.len() == n && records.len() == sessions.len() && !records.is_empty());
+    let (x, y): (Vec<[u8; 32]>, Vec<[u8; 32]>) = keys.iter().cloned().unzip();
+    let (mut err, mut valid) = (vec![0u8; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_musig_partial_verify_batch(ctx, psigs.as_ptr().cast(), pubnonces.as_ptr().cast(), x.as_ptr().cast(), y.as_ptr().cast(), index.as_ptr(),
+                                       records.as_ptr().cast(), sessions.as_ptr().cast(), records.len(), n, err.as_mut_ptr(), valid.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(valid[i] == 1) }).collect())
+}
+
+/// BIP-327 PartialSigAgg (`p2e_musig_sig_agg_batch`): per session the BIP-340 signature made of its partial signatures, or
+/// the code.  `schnorr_verify` accepts it under the session's x-only aggregate key.
+pub fn musig_sig_agg(ctx: *mut P2eCtx, psigs: &[Vec<[u8; 32]>], records: &[MusigKeyAgg], sessions: &[MusigSession])
+                     -> Result<Vec<std::result::Result<[u8; 64], u8>>> {
+    let n = psigs.len();
+    ensure!(records.len() == n && sessions.len() == n);
+    let (flat, offsets) = musig_flatten(psigs, [0u8; 32]);
+    let (mut sig, mut err) = (vec![[0u8; 64]; n], vec![0u8; n]);
+    let rc = unsafe {
+        p2e_musig_sig_agg_batch(ctx, flat.as_ptr().cast(), offsets.as_ptr(), records.as_ptr().cast(), sessions.as_ptr().cast(),
+                                sig.as_mut_ptr().cast(), n, err.as_mut_ptr())
+    };
+    ensure!(rc >= 0, "p2e: {}", unsafe { CStr::from_ptr(p2e_last_error()) }.to_string_lossy());
+    Ok((0..n).map(|i| if err[i] != 0 { Err(err[i]) } else { Ok(sig[i]) }).collect())
+}
+
 /// Hashes of a batch of byte strings as message scalars (`p2e_hash_batch` with `P2E_DIGEST_SCALAR`, host-pointer context):
 /// the digest read as a big-endian integer, which is what `sign_messages*` and `recover_public_keys` take as `msg`.
 /// `alg` is `P2E_HASH_SHA256`, `P2E_HASH_SHA256D` or `P2E_HASH_KECCAK256` (Ethereum's Keccak, not SHA3-256).

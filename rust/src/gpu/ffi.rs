@@ -341,6 +341,26 @@ extern "C" {
         outputs32: *const u8, out_offsets: *const u64, max_hits: usize, n_hits: *mut u8, hit_output: *mut u32, hit_label: *mut u8,
         hit_tweak32: *mut u8, count: usize, err: *mut u8) -> i64;
 
+    // ---- MuSig2 (BIP-327) on secp256k1: points, secret keys and nonces little-endian 32-byte values (pubnonce128 / aggnonce128 =
+    // x(R_1) || y(R_1) || x(R_2) || y(R_2), secnonce64 = k_1 || k_2), tweaks, messages, partial signatures, agg_pk32 and sig64 the
+    // standard's big-endian strings; keyagg192 and session128 are the records of include/p2e.h; key_offsets (count + 1) counts
+    // signers; tweak32 may be null in mode 2, session_index may be null; the batch size is `count`; err[i] is a P2E_WIRE_* code
+    pub fn p2e_musig_key_agg_batch(ctx: *mut P2eCtx, pkx32: *const u8, pky32: *const u8, key_offsets: *const u64, keyagg192: *mut u8,
+        agg_pk32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_musig_apply_tweak_batch(ctx: *mut P2eCtx, keyagg192_in: *const u8, tweak32: *const u8, mode: i32, keyagg192_out: *mut u8,
+        agg_pk32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_musig_nonce_agg_batch(ctx: *mut P2eCtx, pubnonce128: *const u8, key_offsets: *const u64, aggnonce128: *mut u8,
+        count: usize, err: *mut u8) -> i64;
+    pub fn p2e_musig_session_batch(ctx: *mut P2eCtx, keyagg192: *const u8, aggnonce128: *const u8, msg32: *const u8,
+        session128: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_musig_partial_sign_batch(ctx: *mut P2eCtx, secnonce64: *const u8, sk32: *const u8, keyagg192: *const u8,
+        session128: *const u8, psig32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_musig_partial_verify_batch(ctx: *mut P2eCtx, psig32: *const u8, pubnonce128: *const u8, pkx32: *const u8,
+        pky32: *const u8, session_index: *const u32, keyagg192: *const u8, session128: *const u8, n_sessions: usize, count: usize,
+        err: *mut u8, valid: *mut u8) -> i64;
+    pub fn p2e_musig_sig_agg_batch(ctx: *mut P2eCtx, psig32: *const u8, key_offsets: *const u64, keyagg192: *const u8,
+        session128: *const u8, sig64: *mut u8, count: usize, err: *mut u8) -> i64;
+
     // ---- synthetic inputs (host only): valid signatures per curve/ecdsa.rs:25-40
     pub fn p2e_synth_signatures(seed: u64, first: usize, n: usize, msg32: *mut u8, r32: *mut u8, s32: *mut u8, pkx32: *mut u8,
         pky32: *mut u8) -> i32;
