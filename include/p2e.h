@@ -22,7 +22,7 @@
  * BUFFER OVERLAP
  *   What a call may be handed when an output buffer shares bytes with another argument.  The rule below holds for the
  *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_musig_sig_agg_batch (keys, signing,
- *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, Taproot, silent payments, MuSig2) and the two verdict-only
+ *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, PBKDF2 / BIP-39, Taproot, silent payments, MuSig2) and the two verdict-only
  *   verifiers p2e_ecdsa_verify_batch and p2e_p256_verify_batch.  It is checked on the host, behind the call's other argument
  *   checks and before the context is looked at, and it is the same with P2E_CTX_HOST_POINTERS (staging would hide the race;
  *   the contract does not depend on the mode).
@@ -56,7 +56,8 @@
  *   4. Adjacent ranges (the end of one is the start of the other) do not overlap.  n == 0 checks nothing and returns 0 as
  *      before.  A null nullable argument, and an argument the chosen form does not use, is skipped.  A range whose end
  *      wraps round the address space is refused.  Inputs may overlap each other freely.
- *   5. Variable-length `data` (p2e_hash_batch, p2e_hash160_batch, p2e_point_decode_batch, P2E_SIG_DER in p2e_sig_decode_batch)
+ *   5. Variable-length `data` (p2e_hash_batch, p2e_hash160_batch, p2e_point_decode_batch, P2E_SIG_DER in p2e_sig_decode_batch,
+ *      the passwords, salts, mnemonics and passphrases of p2e_pbkdf2_hmac_sha512_batch and p2e_bip39_seed_batch)
  *      has an extent only the device knows.  It must not overlap any output: the CALLER's duty.  It is checked only where the
  *      call reads offsets[0] and offsets[n] on the host anyway (P2E_CTX_HOST_POINTERS), with the same error.
  *   6. The column-matrix calls (single generators, fused fills, aux / gate-internal / constraint-block passes, wire assembly,
@@ -983,6 +984,48 @@ long p2e_bip32_ckd_pub_batch(p2e_ctx *ctx, const uint8_t *par_pkx32, const uint8
 long p2e_key_hash160_batch(p2e_ctx *ctx, unsigned form, const uint8_t *pkx32, const uint8_t *pky32,
                            const uint8_t *err_in /* nullable */, uint8_t *out20, size_t n);
 long p2e_hash160_batch(p2e_ctx *ctx, const uint8_t *data, const uint64_t *offsets, uint8_t *out20, size_t n);
+
+/* ---- PBKDF2-HMAC-SHA512 and BIP-39 seeds (csrc/kdf.hpp): the step in front of p2e_bip32_master_batch.  What a wallet holds
+ * is a mnemonic sentence and a passphrase; seed = PBKDF2-HMAC-SHA512(sentence, "mnemonic" || passphrase, 2048, 64), about
+ * 4 100 SHA-512 compressions where a hardened child costs four.  Defined by RFC 8018 5.2, RFC 2104, FIPS 180-4 and BIP-39.
+ *   count    The batch size of these two calls is named `count`, as for the Taproot, silent-payment and MuSig2 calls and for
+ *            the same reason: tests/test_overlap_cpu.py derives its list of per-element calls from the declarations with a
+ *            parameter named n or m, so no parameter here is named n or m.  They carry their span table in
+ *            tests/test_kdf_cpu.py.  BUFFER OVERLAP (top of this file) holds in full and there is NO in-place form: an output
+ *            may touch no input.
+ *   data     password, salt, mnemonic and passphrase are laid out exactly as the data of p2e_hash_batch: one concatenated
+ *            buffer of any alignment, element i = [offsets[i], offsets[i + 1]); read as aligned 4-byte words, and only words
+ *            that hold a byte of the lane's own element.  With host pointers the bytes [offsets[0], offsets[last]) are staged
+ *            and may touch no output.  Bytes are taken as given: UTF-8 NFKD normalisation is the caller's job, and BIP-39's
+ *            wordlist and checksum are not looked at (its seed derivation does not look at them either).
+ *   broadcast   n_passwords, n_salts, n_mnemonics are 1 or count; with 1 < count every lane uses element 0 -- one mnemonic
+ *            against many passphrases, many mnemonics against one passphrase.  n_passphrases is 0, 1 or count; 0 goes with
+ *            passphrase == NULL and pp_offsets == NULL and means the empty passphrase.  Anything else is P2E_E_INVALID.
+ *   p2e_pbkdf2_hmac_sha512_batch   The HMAC key is the password itself if it is at most 128 bytes, else its SHA-512 digest.
+ *            U_1 = HMAC(P, S || 00 00 00 01), U_j = HMAC(P, U_{j-1}), T = U_1 ^ ... ^ U_iterations; dk[dk_len i ..] = the
+ *            first dk_len bytes of T.  dk_len is a multiple of 4 in 4 .. 64 (one block of output), dk is 4-byte aligned.
+ *            iterations == 0, iterations > P2E_PBKDF2_MAX_ITERATIONS or a bad dk_len is P2E_E_INVALID.  The call is ONE
+ *            kernel whose running time grows with `iterations` -- 2 (iterations - 1) + 4 .. 8 compressions per lane, nothing
+ *            else shares the launch and it cannot be interrupted --, which is why there is a cap: 2^20 iterations are about
+ *            500 times a BIP-39 seed.
+ *   p2e_bip39_seed_batch   The same kernel with the eight bytes "mnemonic" in front of the salt (a constant of the kernel,
+ *            nothing is concatenated on the host), 2048 iterations and 64 bytes out: seed64[64 i ..] is what
+ *            p2e_bip32_master_batch takes with seed_len = 64.
+ *   err[i]   P2E_WIRE_BAD_LENGTH for a reversed offset pair or a length >= 2^32 of either operand (a broadcast operand
+ *            flags every element alike).  A flagged element writes zeros to all its output bytes and runs no iteration.  The
+ *            return value counts the flagged elements; count == 0 returns 0.  Null pointers, host pointers, async mode, the
+ *            current device and failed calls behave as for the BIP-32 calls.
+ * One kernel on the context's caller stream, one lane per element: no internal streams, no LDS, no scratch; passwords, key
+ * states and every U_j live in registers only. */
+#define P2E_PBKDF2_MAX_ITERATIONS (1u << 20)
+long p2e_pbkdf2_hmac_sha512_batch(p2e_ctx *ctx, const uint8_t *password, const uint64_t *pw_offsets /* n_passwords + 1 */,
+                                  size_t n_passwords /* 1 or count */, const uint8_t *salt,
+                                  const uint64_t *salt_offsets /* n_salts + 1 */, size_t n_salts /* 1 or count */,
+                                  uint32_t iterations, size_t dk_len, uint8_t *dk, size_t count, uint8_t *err);
+long p2e_bip39_seed_batch(p2e_ctx *ctx, const uint8_t *mnemonic, const uint64_t *mn_offsets /* n_mnemonics + 1 */,
+                          size_t n_mnemonics /* 1 or count */, const uint8_t *passphrase /* nullable */,
+                          const uint64_t *pp_offsets /* nullable with it */, size_t n_passphrases /* 0, 1 or count */,
+                          uint8_t *seed64, size_t count, uint8_t *err);
 
 /* ---- Taproot (BIP-341) on secp256k1 (csrc/taproot.hpp): what lies between an x-only key and a BIP-340 signature.  An
  * xpub scan on the device (p2e_bip32_ckd_pub_batch) becomes Taproot output keys -- with p2e_point_encode_batch /

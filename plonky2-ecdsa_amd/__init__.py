@@ -104,6 +104,7 @@ EXPORTS = (
     "p2e_schnorr_public_key_batch", "p2e_schnorr_sign_batch", "p2e_schnorr_verify_batch", "p2e_xonly_decode_batch",
     "p2e_schnorr_verify_aggregate",
     "p2e_bip32_master_batch", "p2e_bip32_ckd_priv_batch", "p2e_bip32_ckd_pub_batch", "p2e_key_hash160_batch", "p2e_hash160_batch",
+    "p2e_pbkdf2_hmac_sha512_batch", "p2e_bip39_seed_batch",
     "p2e_taproot_leaf_hash_batch", "p2e_taproot_merkle_root_batch", "p2e_taproot_tweak_pubkey_batch", "p2e_taproot_tweak_seckey_batch",
     "p2e_taproot_verify_commitment_batch",
     "p2e_sp_input_hash_batch", "p2e_sp_label_batch", "p2e_sp_send_batch", "p2e_sp_scan_batch",
@@ -345,6 +346,23 @@ def point_msm_plan(n: int, curve: int = CURVE_SECP256K1, window_bits: int = MSM_
     if rc:
         raise P2EError(f"p2e_point_msm_plan failed ({rc}): {lib().p2e_last_error().decode()}")
     return dict(zip(("window_bits", "windows", "buckets", "seg", "scratch_bytes", "max_lane_additions"), [int(v) for v in buf]))
+
+
+PBKDF2_MAX_ITERATIONS = 1 << 20    # include/p2e.h P2E_PBKDF2_MAX_ITERATIONS
+
+
+def pack_bytes(items):
+    """A list of bytes or str as (buffer uint8, offsets uint64 (len + 1,)): the variable-length layout of hash_batch and of
+    the PBKDF2 / BIP-39 calls.  A str is normalised as BIP-39 asks, unicodedata.normalize("NFKD", s).encode(); bytes are
+    taken as given.  The buffer is padded to whole 4-byte words (a lane reads aligned words; no padding byte is used)."""
+    import unicodedata
+    raw = [unicodedata.normalize("NFKD", s).encode() if isinstance(s, str) else bytes(s) for s in items]
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    if raw:
+        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    buf = np.zeros((int(offsets[-1]) + 3) // 4 * 4 + 4, dtype=np.uint8)
+    buf[:int(offsets[-1])] = np.frombuffer(b"".join(raw), dtype=np.uint8)
+    return buf, offsets
 
 
 def synth_signatures(seed: int, n: int, first: int = 0):
@@ -1362,6 +1380,57 @@ class Context:
         out = out if out is not None else self._bytes(n, 20)
         bad = self._check(self._L.p2e_hash160_batch(self._h, _ptr(data), _ptr(offsets), _ptr(out), C.c_size_t(n)))
         return out, bad
+
+    # ---- PBKDF2-HMAC-SHA512 and BIP-39 seeds (include/p2e.h p2e_pbkdf2_hmac_sha512_batch, p2e_bip39_seed_batch) -----------------
+    def _var(self, items):
+        """(buffer, offsets, elements) of a variable-length operand: a (buffer, offsets) pair as it is -- numpy arrays with
+        host_pointers, torch CUDA tensors otherwise --, a list of bytes / str through pack_bytes (uploaded where the context
+        takes device pointers)."""
+        if isinstance(items, tuple):
+            buf, offsets = items
+            return buf, offsets, self._shape(offsets)[0] - 1
+        buf, offsets = pack_bytes(items)
+        if not self.host_pointers:
+            import torch
+            dev = f"cuda:{self.device}"
+            buf, offsets = torch.from_numpy(buf).to(dev), torch.from_numpy(offsets.view(np.int64)).to(dev)
+        return buf, offsets, len(items)
+
+    @staticmethod
+    def _lanes(what, counts, count):
+        """the batch size of operands that hold one element or one per lane"""
+        count = max(counts) if count is None else count
+        if any(k != 1 and k != count for k in counts):
+            raise P2EError(f"{what} must hold one element or one per lane")
+        return count
+
+    def pbkdf2_hmac_sha512_batch(self, passwords, salts, iterations, dk_len=64, count=None, dk=None, err=None):
+        """PBKDF2-HMAC-SHA512 (RFC 8018), one output block: dk[i] = the first dk_len (a multiple of 4 in 4 .. 64) bytes of
+        T = U_1 ^ ... ^ U_iterations under password i and salt i.  passwords and salts are lists of bytes / str (pack_bytes)
+        or (buffer, offsets) pairs laid out as for hash_batch; one element serves the whole batch.  (dk (count, dk_len), err,
+        flagged count): WIRE_BAD_LENGTH and zeros for reversed offsets or a length >= 2^32."""
+        pw, pw_off, n_pw = self._var(passwords)
+        sa, sa_off, n_sa = self._var(salts)
+        count = self._lanes("passwords and salts", (n_pw, n_sa), count)
+        dk = dk if dk is not None else self._bytes(count, dk_len)
+        err = err if err is not None else self._vec(count, np.uint8)
+        bad = self._check(self._L.p2e_pbkdf2_hmac_sha512_batch(self._h, _ptr(pw), _ptr(pw_off), C.c_size_t(n_pw), _ptr(sa), _ptr(sa_off),
+                                                               C.c_size_t(n_sa), C.c_uint32(iterations), C.c_size_t(dk_len), _ptr(dk),
+                                                               C.c_size_t(count), _ptr(err)))
+        return dk, err, bad
+
+    def bip39_seed_batch(self, mnemonics, passphrases=None, count=None, seed=None, err=None):
+        """BIP-39 seeds: seed[i] = PBKDF2-HMAC-SHA512(mnemonic i, "mnemonic" || passphrase i, 2048, 64), what
+        bip32_master_batch takes.  Operands as for pbkdf2_hmac_sha512_batch (a str is NFKD-normalised); passphrases=None is
+        the empty passphrase.  The wordlist and the checksum are not looked at.  (seed (count, 64), err, flagged count)."""
+        mn, mn_off, n_mn = self._var(mnemonics)
+        pp, pp_off, n_pp = self._var(passphrases) if passphrases is not None else (None, None, 0)
+        count = self._lanes("mnemonics and passphrases", (n_mn, n_pp) if n_pp else (n_mn,), count)
+        seed = seed if seed is not None else self._bytes(count, 64)
+        err = err if err is not None else self._vec(count, np.uint8)
+        bad = self._check(self._L.p2e_bip39_seed_batch(self._h, _ptr(mn), _ptr(mn_off), C.c_size_t(n_mn), _ptr(pp), _ptr(pp_off),
+                                                       C.c_size_t(n_pp), _ptr(seed), C.c_size_t(count), _ptr(err)))
+        return seed, err, bad
 
     # ---- Taproot on secp256k1 (include/p2e.h p2e_taproot_leaf_hash_batch and the four calls after it) ---------------------------
     # Every key, hash and tweak is an (n, 32) array of the standard's big-endian byte strings, as in the Schnorr calls.

@@ -36,6 +36,7 @@
 #include "sp.hpp"
 #include "musig.hpp"
 #include "hd.hpp"
+#include "kdf.hpp"
 #include "hash.hpp"
 #include "wire.hpp"
 
@@ -2418,19 +2419,19 @@ void launch_eth_address(p2e_ctx* c, const uint8_t* pkx32, const uint8_t* pky32, 
 // the variable-length input of a staged call: the copy holds data[offsets[0], offsets[n]) and `data` becomes that copy moved
 // back by offsets[0], as in p2e_hash_batch.  false: offsets[n] < offsets[0] (the error text is set)
 // `args`: the call's list, not yet staged (offsets is read here on the host); the extent of data, known here alone, must
-// not touch the list's outputs (BUFFER OVERLAP, include/p2e.h)
-static bool wire_stage_elements(Staged& S, Args args, const uint8_t*& data, const uint64_t* offsets, size_t n) {
+// not touch the list's outputs (BUFFER OVERLAP, include/p2e.h).  `name`: what the argument is called where a call has two
+static bool wire_stage_elements(Staged& S, Args args, const uint8_t*& data, const uint64_t* offsets, size_t n, const char* name = "data") {
     if (!S.host) return true;
     const uint64_t first = offsets[0], last = offsets[n];
     if (last < first) {
-        set_error("offsets[n] < offsets[0]");
+        set_error(std::strcmp(name, "data") ? std::string("the last offset of ") + name + " lies below the first" : "offsets[n] < offsets[0]");
         return false;
     }
     overlap::Span spans[call_args::kMaxBufs + 1];
     size_t num = 0;
     for (size_t i = 0, all = call_args::spans(args, n, spans); i < all; i++)
         if (spans[i].is_output) spans[num++] = spans[i];
-    spans[num++] = overlap::Span{"data", data + first, 1, (size_t)(last - first), false, true};   // (no lane owns a byte of it)
+    spans[num++] = overlap::Span{name, data + first, 1, (size_t)(last - first), false, true};   // (no lane owns a byte of it)
     if (const overlap::Clash k = overlap::check(spans, num); k.bad) {
         set_error(std::string("overlap: ") + k.a + " and " + k.b + " share bytes (variable-length data may not touch an output)");
         return false;
@@ -3350,6 +3351,95 @@ extern "C" long p2e_hash160_batch(p2e_ctx* c, const uint8_t* data, const uint64_
     if (long rc = S.begin(args)) return rc;
     launch_hash160(c, data, offsets, out20, n);
     return S.end();
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// PBKDF2-HMAC-SHA512 and BIP-39 seeds (kdf.hpp): the step in front of the master key
+// ====================================================================================================
+// one launch on the caller's stream; defined in part 1 beside the other hashing kernels, called from part 0
+void launch_pbkdf2_sha512(p2e_ctx* c, bool bip39, const uint8_t* password, const uint64_t* pw_offsets, bool pw_bcast, const uint8_t* salt,
+                          const uint64_t* salt_offsets, bool salt_bcast, uint32_t iterations, size_t dk_len, uint8_t* dk, size_t count,
+                          uint8_t* err);
+#if P2E_HAS(1)
+void launch_pbkdf2_sha512(p2e_ctx* c, bool bip39, const uint8_t* password, const uint64_t* pw_offsets, bool pw_bcast, const uint8_t* salt,
+                          const uint64_t* salt_offsets, bool salt_bcast, uint32_t iterations, size_t dk_len, uint8_t* dk, size_t count,
+                          uint8_t* err) {
+    if (bip39)
+        hipLaunchKernelGGL((k_pbkdf2_sha512<8>), grid1(count), dim3(BS), 0, c->stream, password, pw_offsets, pw_bcast ? 1 : 0, salt, salt_offsets,
+                           salt_bcast ? 1 : 0, iterations, (u32)(dk_len / 4), dk, count, err, c->d_counter);
+    else
+        hipLaunchKernelGGL((k_pbkdf2_sha512<0>), grid1(count), dim3(BS), 0, c->stream, password, pw_offsets, pw_bcast ? 1 : 0, salt, salt_offsets,
+                           salt_bcast ? 1 : 0, iterations, (u32)(dk_len / 4), dk, count, err, c->d_counter);
+}
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+static_assert(P2E_PBKDF2_MAX_ITERATIONS == PBKDF2_MAX_ITERATIONS, "include/p2e.h and kdf.hpp must agree");
+// an operand of n_x elements serves `count` lanes: one each, or one for all (`or_none`: or none at all)
+static bool kdf_bad_elements(const char* what, size_t n_x, size_t count, bool or_none = false) {
+    if (n_x == 1 || n_x == count || (or_none && n_x == 0)) return false;
+    set_error(std::string(what) + (or_none ? " must be 0, 1 or count" : " must be 1 or count"));
+    return true;
+}
+// the entries of an operand's offsets; 0 for counts that are refused anyway (so that the sum cannot wrap)
+static size_t kdf_offsets(size_t n_x, size_t count) { return (n_x == 1 || n_x == count) && n_x <= ((size_t)1 << 31) ? n_x + 1 : 0; }
+// both calls behind their argument checks.  The offsets are read by lanes that own no element of them (lane i reads entry
+// i + 1, every lane reads a broadcast operand's two): never in place.  (the batch size is `count`: see include/p2e.h)
+static long kdf_run(p2e_ctx* c, bool bip39, Args args, const char* pw_name, const uint8_t* password, const uint64_t* pw_offsets, size_t n_passwords,
+                    const char* salt_name, const uint8_t* salt, const uint64_t* salt_offsets, size_t n_salts, uint32_t iterations, size_t dk_len,
+                    uint8_t* dk, size_t count, uint8_t* err) {
+    if (batch_too_large(count) || bad_overlap(count, args) || bad_ctx(c)) return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (!wire_stage_elements(S, args, password, pw_offsets, n_passwords, pw_name)) return S.done(P2E_E_INVALID);
+    if (salt_offsets && !wire_stage_elements(S, args, salt, salt_offsets, n_salts, salt_name)) return S.done(P2E_E_INVALID);
+    // (the list's slots are the caller's variables: stage the offsets and outputs through copies of the same names)
+    const Args staged = {ARG_SHARED(pw_offsets, 8, n_passwords + 1), ARG_IN_IF(salt_offsets != nullptr, salt_offsets, 8, n_salts + 1),
+                         ARG_OUT(dk, dk_len, count), ARG_OUT(err, 1, count)};
+    if (long rc = S.begin(staged)) return rc;
+    launch_pbkdf2_sha512(c, bip39, password, pw_offsets, n_passwords != count, salt, salt_offsets, n_salts != count, iterations, dk_len, dk, count,
+                         err);
+    return S.end();
+}
+extern "C" long p2e_pbkdf2_hmac_sha512_batch(p2e_ctx* c, const uint8_t* password, const uint64_t* pw_offsets, size_t n_passwords,
+                                             const uint8_t* salt, const uint64_t* salt_offsets, size_t n_salts, uint32_t iterations, size_t dk_len,
+                                             uint8_t* dk, size_t count, uint8_t* err) {
+    const bool dk_ok = dk_len >= 4 && dk_len <= 64 && dk_len % 4 == 0;
+    const Args args = {ARG_OPAQUE(password), ARG_SHARED(pw_offsets, 8, kdf_offsets(n_passwords, count)),
+                       ARG_OPAQUE(salt),     ARG_SHARED(salt_offsets, 8, kdf_offsets(n_salts, count)),
+                       ARG_OUT(dk, dk_ok ? dk_len : 0, count), ARG_OUT(err, 1, count)};
+    if (missing(args) || kdf_bad_elements("n_passwords", n_passwords, count) || kdf_bad_elements("n_salts", n_salts, count)) return P2E_E_INVALID;
+    if (iterations == 0 || iterations > P2E_PBKDF2_MAX_ITERATIONS) {
+        set_error("iterations must be 1 .. P2E_PBKDF2_MAX_ITERATIONS (2^20)");
+        return P2E_E_INVALID;
+    }
+    if (!dk_ok) {
+        set_error("dk_len must be a multiple of 4 in 4 .. 64");
+        return P2E_E_INVALID;
+    }
+    return kdf_run(c, false, args, "password", password, pw_offsets, n_passwords, "salt", salt, salt_offsets, n_salts, iterations, dk_len, dk, count,
+                   err);
+}
+extern "C" long p2e_bip39_seed_batch(p2e_ctx* c, const uint8_t* mnemonic, const uint64_t* mn_offsets, size_t n_mnemonics,
+                                     const uint8_t* passphrase, const uint64_t* pp_offsets, size_t n_passphrases, uint8_t* seed64, size_t count,
+                                     uint8_t* err) {
+    const bool with_pp = n_passphrases != 0;
+    const Args args = {ARG_OPAQUE(mnemonic),
+                       ARG_SHARED(mn_offsets, 8, kdf_offsets(n_mnemonics, count)),
+                       P2E_ARG(passphrase, 0, 0, Opaque, with_pp),
+                       P2E_ARG(pp_offsets, 8, with_pp ? kdf_offsets(n_passphrases, count) : 0, Shared, with_pp),
+                       ARG_OUT(seed64, 64, count),
+                       ARG_OUT(err, 1, count)};
+    if (missing(args, with_pp ? nullptr : "n_passphrases == 0") || kdf_bad_elements("n_mnemonics", n_mnemonics, count) ||
+        kdf_bad_elements("n_passphrases", n_passphrases, count, true))
+        return P2E_E_INVALID;
+    if (!with_pp && (passphrase || pp_offsets) && count != 0) {
+        set_error("n_passphrases == 0 goes with a null passphrase and null pp_offsets");
+        return P2E_E_INVALID;
+    }
+    return kdf_run(c, true, args, "mnemonic", mnemonic, mn_offsets, n_mnemonics, "passphrase", with_pp ? passphrase : nullptr,
+                   with_pp ? pp_offsets : nullptr, n_passphrases, BIP39_ITERATIONS, 64, seed64, count, err);
 }
 #endif   // P2E_HAS(0)
 

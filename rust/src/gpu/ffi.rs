@@ -312,6 +312,15 @@ extern "C" {
         n: usize) -> i64;
     pub fn p2e_hash160_batch(ctx: *mut P2eCtx, data: *const u8, offsets: *const u64, out20: *mut u8, n: usize) -> i64;
 
+    // ---- PBKDF2-HMAC-SHA512 and BIP-39 seeds: operands laid out as the data of p2e_hash_batch, n_x = 1 (one element for the
+    // batch) or count; passphrase and pp_offsets null with n_passphrases = 0; the batch size is `count` (include/p2e.h says
+    // why); err[i] is P2E_WIRE_BAD_LENGTH or 0.  iterations <= P2E_PBKDF2_MAX_ITERATIONS = 1 << 20; dk_len a multiple of 4 in 4 ..= 64
+    pub fn p2e_pbkdf2_hmac_sha512_batch(ctx: *mut P2eCtx, password: *const u8, pw_offsets: *const u64, n_passwords: usize,
+        salt: *const u8, salt_offsets: *const u64, n_salts: usize, iterations: u32, dk_len: usize, dk: *mut u8, count: usize,
+        err: *mut u8) -> i64;
+    pub fn p2e_bip39_seed_batch(ctx: *mut P2eCtx, mnemonic: *const u8, mn_offsets: *const u64, n_mnemonics: usize,
+        passphrase: *const u8, pp_offsets: *const u64, n_passphrases: usize, seed64: *mut u8, count: usize, err: *mut u8) -> i64;
+
     // ---- Taproot (BIP-341) on secp256k1: every key, hash and tweak the standard's big-endian 32 bytes; root32 may be null
     // (BIP-86's key-path-only output); the batch size is `count` (include/p2e.h says why); err[i] is a P2E_WIRE_* code
     pub fn p2e_taproot_leaf_hash_batch(ctx: *mut P2eCtx, leaf_version: *const u8, script: *const u8, offsets: *const u64,
