@@ -22,7 +22,7 @@
  * BUFFER OVERLAP
  *   What a call may be handed when an output buffer shares bytes with another argument.  The rule below holds for the
  *   PER-ELEMENT calls: every entry point from p2e_ecdsa_public_key_batch to p2e_musig_sig_agg_batch (keys, signing,
- *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, PBKDF2 / BIP-39, Taproot, silent payments, MuSig2) and the two verdict-only
+ *   recovery, hashing, wire forms, point arithmetic, point tables, the many-point sum, Schnorr, BIP-32, PBKDF2 / BIP-39, Taproot, silent payments, a P + b Q and DLEQ proofs, MuSig2) and the two verdict-only
  *   verifiers p2e_ecdsa_verify_batch and p2e_p256_verify_batch.  It is checked on the host, behind the call's other argument
  *   checks and before the context is looked at, and it is the same with P2E_CTX_HOST_POINTERS (staging would hide the race;
  *   the contract does not depend on the mode).
@@ -45,6 +45,9 @@
  *        p2e_taproot_merkle_root_batch         root32 = leaf32
  *        p2e_sp_input_hash_batch               input_hash32 = ax32;   p2e_sp_send_batch   out_pk32 = input_hash32
  *            (p2e_sp_scan_batch offers no in-place form: every overlap of one of its outputs is refused)
+ *        p2e_point_lincomb2_batch              (outx32, outy32) = (px32, py32) or (qx32, qy32); outx32 = a32   (no output on b32)
+ *        p2e_dleq_prove_batch                  (cx32, cy32) = (bx32, by32)   (no output on a_sk32, aux_rand32 or msg32;
+ *            p2e_dleq_verify_batch offers no in-place form)
  *        p2e_musig_apply_tweak_batch           keyagg192_out = keyagg192_in   (the only in-place form of the seven MuSig2 calls)
  *   3. Any other intersection of an output with an input is P2E_E_INVALID, with "overlap" and the two argument names in
  *      p2e_last_error(): a shifted overlap (out == in + 32), different bytes per element (r32 on the 64-byte data of
@@ -1148,6 +1151,55 @@ long p2e_sp_scan_batch(p2e_ctx *ctx, const uint8_t *scan_sk32 /* 1 */, const uin
                        const uint8_t *outputs32, const uint64_t *out_offsets /* count + 1, in outputs */, size_t max_hits,
                        uint8_t *n_hits, uint32_t *hit_output, uint8_t *hit_label, uint8_t *hit_tweak32, size_t count,
                        uint8_t *err);
+
+/* ---- a P + b Q per element on either curve, and discrete-log-equality proofs (BIP-374) on secp256k1 (csrc/point_arith.hpp,
+ * csrc/dleq.hpp).  A collaborative silent-payment sender (several signers, a hardware signer, PSBTs under BIP-375) publishes
+ * its ECDH share C = a B_scan with a proof that C uses the a of its public key A = a G; the coordinator checks every proof
+ * before it adds the shares.  The verifier's s B - e C is a linear combination of two general points: one joint walk.
+ *   count    The batch size of these three calls is named `count`, as for the silent-payment calls and for the same reason.
+ *            They carry their span table in tests/test_dleq_cpu.py.
+ *   p2e_point_lincomb2_batch   out_i = a_i P_i + b_i Q_i.  The conventions are p2e_point_lincomb_batch's: little-endian values;
+ *            scalars reduced with one conditional subtraction, not flagged; (0, 0) a legal neutral operand; P checked before Q
+ *            (P2E_WIRE_COORD_RANGE, then P2E_WIRE_NOT_ON_CURVE; operands are checked whatever the scalars are); a neutral
+ *            result is P2E_WIRE_INFINITY and zeros.  Defined, none an error by itself: a = 0, b = 0, P or Q neutral, Q = +-P,
+ *            Q = +-lambda P, a P = b Q (doubled), a P = -b Q (the neutral result).  plan as for p2e_point_mul_batch
+ *            (P2E_MUL_PLAN_GLV on P2E_CURVE_P256 is P2E_E_INVALID); every plan writes the bytes p2e_point_mul_batch,
+ *            p2e_point_mul_batch and p2e_point_add_batch write for the same operands.  One walk per lane with one accumulator:
+ *            256 doublings under P2E_MUL_PLAN_PLAIN, 128 under P2E_MUL_PLAN_GLV, against 512 / 256 of the three calls.
+ *            In place: (outx32, outy32) = (px32, py32), (outx32, outy32) = (qx32, qy32), outx32 = a32.  No output on b32.
+ *   DLEQ     bytes: points and a_sk32 are the library's LITTLE-endian 32-byte values (they chain with p2e_sp_*, p2e_bip32_* and
+ *            the point calls); aux_rand32 and msg32 are byte strings; proof64 = bytes32(e) || bytes32(s), BIG-endian as the
+ *            standard writes it.  G is the curve's generator.  H_tag(x) = SHA256(SHA256(tag) || SHA256(tag) || x) for
+ *            "BIP0374/aux", "BIP0374/nonce", "BIP0374/challenge"; cbytes(X) = (02 | parity of y) || bytes32(x); m' is msg32[i], or
+ *            empty where msg32 is NULL (for the whole batch).  err[i] is a P2E_WIRE_* CODE, the first failing check in the
+ *            order given; a flagged element writes zeros to all its outputs; the return value counts the flagged elements.
+ *            This definition has not been checked against the vectors published with BIP-374.
+ *   p2e_dleq_prove_batch   In order: a = 0 or a >= n: P2E_WIRE_SCALAR_RANGE; B (0, 0): P2E_WIRE_INFINITY, a coordinate >= p:
+ *            P2E_WIRE_COORD_RANGE, off the curve: P2E_WIRE_NOT_ON_CURVE.  A = a G, C = a B;
+ *            t = bytes32(a) xor H_aux(aux_rand); k = int(H_nonce(t || cbytes(A) || cbytes(C) || m')) mod n, k = 0:
+ *            P2E_WIRE_INFINITY; R1 = k G, R2 = k B;
+ *            e = int(H_challenge(cbytes(A) || cbytes(B) || cbytes(C) || cbytes(G) || cbytes(R1) || cbytes(R2) || m')), not reduced
+ *            for the wire; s = (k + e a) mod n.  proof64 and, where cx32 is given (cy32 then too), C are written.  a, t and k
+ *            never leave the lane's registers.  The standard's last step -- verify the fresh proof -- is NOT done, as
+ *            p2e_schnorr_sign_batch does not verify what it signed: chain p2e_dleq_verify_batch (examples/dleq_share.c).
+ *            In place: (cx32, cy32) = (bx32, by32) and nothing else (no output on a_sk32, aux_rand32 or msg32).
+ *   p2e_dleq_verify_batch   In order: A, then B, then C ((0, 0): P2E_WIRE_INFINITY; a coordinate >= p: P2E_WIRE_COORD_RANGE; off
+ *            the curve: P2E_WIRE_NOT_ON_CURVE); s >= n: P2E_WIRE_SCALAR_RANGE.  e is any 256-bit value and is used modulo n.
+ *            Where err[i] == 0: R1 = s G - e A, R2 = s B - e C; valid[i] = 1 iff neither is the neutral element and bytes32(e)
+ *            equals the challenge hash over A, B, C, G, R1, R2, m'.  A well-formed but wrong proof has err = 0, valid = 0 and is
+ *            NOT counted; valid[i] = 0 wherever err[i] != 0 (the contract of p2e_schnorr_verify_batch).  No in-place form.
+ * Each call is one kernel on the context's caller stream, one lane per element: no internal streams, no scratch block, no table in
+ * LDS, nothing in the private segment.  Null pointers, P2E_MUL_PLAN_*, host pointers, async mode, the
+ * current device and failed calls behave as for the point-arithmetic and silent-payment calls; count == 0 returns 0. */
+long p2e_point_lincomb2_batch(p2e_ctx *ctx, int curve, unsigned plan, const uint8_t *a32, const uint8_t *b32,
+                              const uint8_t *px32, const uint8_t *py32, const uint8_t *qx32, const uint8_t *qy32,
+                              uint8_t *outx32, uint8_t *outy32, size_t count, uint8_t *err);
+long p2e_dleq_prove_batch(p2e_ctx *ctx, const uint8_t *a_sk32, const uint8_t *bx32, const uint8_t *by32,
+                          const uint8_t *aux_rand32, const uint8_t *msg32 /* nullable */, uint8_t *proof64,
+                          uint8_t *cx32 /* nullable */, uint8_t *cy32 /* nullable, with cx32 */, size_t count, uint8_t *err);
+long p2e_dleq_verify_batch(p2e_ctx *ctx, const uint8_t *ax32, const uint8_t *ay32, const uint8_t *bx32, const uint8_t *by32,
+                           const uint8_t *cx32, const uint8_t *cy32, const uint8_t *proof64, const uint8_t *msg32 /* nullable */,
+                           size_t count, uint8_t *err, uint8_t *valid);
 
 /* ---- MuSig2 (BIP-327) on secp256k1 (csrc/musig.hpp): the multi-party form of a BIP-340 signature, from the key list to the
  * final signature.  A co-signer does per session what these seven calls do per element: hash a key list, multiply general

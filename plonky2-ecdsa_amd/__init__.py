@@ -108,6 +108,7 @@ EXPORTS = (
     "p2e_taproot_leaf_hash_batch", "p2e_taproot_merkle_root_batch", "p2e_taproot_tweak_pubkey_batch", "p2e_taproot_tweak_seckey_batch",
     "p2e_taproot_verify_commitment_batch",
     "p2e_sp_input_hash_batch", "p2e_sp_label_batch", "p2e_sp_send_batch", "p2e_sp_scan_batch",
+    "p2e_point_lincomb2_batch", "p2e_dleq_prove_batch", "p2e_dleq_verify_batch",
     "p2e_musig_key_agg_batch", "p2e_musig_apply_tweak_batch", "p2e_musig_nonce_agg_batch", "p2e_musig_session_batch",
     "p2e_musig_partial_sign_batch", "p2e_musig_partial_verify_batch", "p2e_musig_sig_agg_batch",
 )
@@ -1560,6 +1561,43 @@ class Context:
                                                     C.c_size_t(max_hits), _ptr(n_hits), _ptr(hit_output), _ptr(hit_label), _ptr(hit_tweak),
                                                     C.c_size_t(n), _ptr(err)))
         return n_hits, hit_output, hit_label, hit_tweak, err, bad
+
+    # ---- a P + b Q and DLEQ proofs (include/p2e.h p2e_point_lincomb2_batch, p2e_dleq_prove_batch, p2e_dleq_verify_batch) ------------
+    def point_lincomb2_batch(self, a, b, px, py, qx, qy, curve=CURVE_SECP256K1, plan=MUL_PLAN_AUTO, outx=None, outy=None, err=None):
+        """a[i] * (px[i], py[i]) + b[i] * (qx[i], qy[i]) per element in one joint walk, inputs and codes as for
+        point_lincomb_batch (P is checked before Q): (outx, outy, err, flagged count) -- the bytes of point_mul_batch,
+        point_mul_batch and point_add_batch.  WIRE_INFINITY where the sum is the neutral element."""
+        n = self._shape(a)[0]
+        outx = outx if outx is not None else self._packed(n)
+        outy = outy if outy is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_point_lincomb2_batch(self._h, C.c_int(curve), C.c_uint(plan), _ptr(a), _ptr(b), _ptr(px), _ptr(py),
+                                                           _ptr(qx), _ptr(qy), _ptr(outx), _ptr(outy), C.c_size_t(n), _ptr(err)))
+        return outx, outy, err, bad
+
+    def dleq_prove_batch(self, a_sk, bx, by, aux_rand, msg=None, proof=None, cx=None, cy=None, err=None, want_c=True):
+        """The shares C[i] = a[i] B[i] and BIP-374 proofs that they use the a of A = a G: a_sk, bx, by (n, 32) little-endian,
+        aux_rand and msg (n, 32) byte strings (msg None: no message): (proof (n, 64) = bytes32(e) || bytes32(s) big-endian,
+        cx, cy (n, 32) little-endian or None with want_c=False, err, flagged count).  The fresh proof is not verified."""
+        n = self._shape(a_sk)[0]
+        proof = proof if proof is not None else self._bytes(n, 64)
+        if want_c:
+            cx = cx if cx is not None else self._packed(n)
+            cy = cy if cy is not None else self._packed(n)
+        err = err if err is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_dleq_prove_batch(self._h, _ptr(a_sk), _ptr(bx), _ptr(by), _ptr(aux_rand), _ptr(msg), _ptr(proof),
+                                                       _ptr(cx), _ptr(cy), C.c_size_t(n), _ptr(err)))
+        return proof, cx, cy, err, bad
+
+    def dleq_verify_batch(self, ax, ay, bx, by, cx, cy, proof, msg=None, err=None, valid=None):
+        """valid[i] = 1 iff proof[i] shows log_G A[i] = log_B[i] C[i] (under msg[i], or no message): (err, valid, flagged
+        count).  A well-formed wrong proof is err 0, valid 0 and not counted."""
+        n = self._shape(ax)[0]
+        err = err if err is not None else self._vec(n, np.uint8)
+        valid = valid if valid is not None else self._vec(n, np.uint8)
+        bad = self._check(self._L.p2e_dleq_verify_batch(self._h, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by), _ptr(cx), _ptr(cy), _ptr(proof),
+                                                        _ptr(msg), C.c_size_t(n), _ptr(err), _ptr(valid)))
+        return err, valid, bad
 
     # ---- MuSig2 on secp256k1 (include/p2e.h p2e_musig_key_agg_batch and the six calls after it) ------------------------------------
     # Points, secret keys and nonces are little-endian as in the BIP-32 calls (a public nonce is (n, 128) = x(R_1) || y(R_1) ||

@@ -34,6 +34,7 @@
 #include "schnorr.hpp"
 #include "taproot.hpp"
 #include "sp.hpp"
+#include "dleq.hpp"
 #include "musig.hpp"
 #include "hd.hpp"
 #include "kdf.hpp"
@@ -3708,6 +3709,137 @@ extern "C" long p2e_sp_scan_batch(p2e_ctx* c, const uint8_t* scan_sk32, const ui
     if (long rc = S.begin(args)) return rc;
     launch_sp_scan(c, table, scan_sk32, spend_pkx32, spend_pky32, n_labels ? label_x32 : nullptr, n_labels ? label_y32 : nullptr, n_labels, ax32,
                    ay32, input_hash32, outputs32, out_offsets, max_hits, n_hits, hit_output, hit_label, hit_tweak32, count, err);
+    return S.end();
+}
+#endif   // P2E_HAS(0)
+
+// ====================================================================================================
+// a P + b Q per element (point_arith.hpp's joint walk) and DLEQ proofs (BIP-374) on secp256k1 (dleq.hpp)
+// ====================================================================================================
+// one launch each on the caller's stream; defined in part 1 beside the point multiplication, called from part 0.
+// plan: MUL_PLAN_PLAIN or MUL_PLAN_GLV (secp256k1 only), already chosen
+template <class CV>
+void launch_point_lincomb2(p2e_ctx* c, int plan, const uint8_t* a, const uint8_t* b, const uint8_t* px, const uint8_t* py, const uint8_t* qx,
+                           const uint8_t* qy, uint8_t* outx, uint8_t* outy, size_t count, uint8_t* err);
+void launch_dleq_prove(p2e_ctx* c, const Aff* table, const uint8_t* a_sk, const uint8_t* bx, const uint8_t* by, const uint8_t* aux_rand,
+                       const uint8_t* msg, uint8_t* proof, uint8_t* cx, uint8_t* cy, size_t count, uint8_t* err);
+void launch_dleq_verify(p2e_ctx* c, const Aff* table, const uint8_t* ax, const uint8_t* ay, const uint8_t* bx, const uint8_t* by,
+                        const uint8_t* cx, const uint8_t* cy, const uint8_t* proof, const uint8_t* msg, size_t count, uint8_t* err,
+                        uint8_t* valid);
+#if P2E_HAS(1)
+template <class CV>
+void launch_point_lincomb2(p2e_ctx* c, int plan, const uint8_t* a, const uint8_t* b, const uint8_t* px, const uint8_t* py, const uint8_t* qx,
+                           const uint8_t* qy, uint8_t* outx, uint8_t* outy, size_t count, uint8_t* err) {
+    if constexpr (CV::kAZero) {
+        if (plan == MUL_PLAN_GLV) {
+            hipLaunchKernelGGL((k_point_lincomb2<CV, MUL_PLAN_GLV>), grid1(count), dim3(BS), 0, c->stream, a, b, px, py, qx, qy, outx, outy,
+                               count, err, c->d_counter);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_point_lincomb2<CV, MUL_PLAN_PLAIN>), grid1(count), dim3(BS), 0, c->stream, a, b, px, py, qx, qy, outx, outy, count,
+                       err, c->d_counter);
+}
+template void launch_point_lincomb2<Secp256k1>(p2e_ctx*, int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*,
+                                               const uint8_t*, uint8_t*, uint8_t*, size_t, uint8_t*);
+template void launch_point_lincomb2<P256>(p2e_ctx*, int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*,
+                                          const uint8_t*, uint8_t*, uint8_t*, size_t, uint8_t*);
+void launch_dleq_prove(p2e_ctx* c, const Aff* table, const uint8_t* a_sk, const uint8_t* bx, const uint8_t* by, const uint8_t* aux_rand,
+                       const uint8_t* msg, uint8_t* proof, uint8_t* cx, uint8_t* cy, size_t count, uint8_t* err) {
+    hipLaunchKernelGGL((k_dleq_prove<0>), grid1(count), dim3(BS), 0, c->stream, table, a_sk, bx, by, aux_rand, msg, proof, cx, cy, count, err,
+                       c->d_counter);
+}
+void launch_dleq_verify(p2e_ctx* c, const Aff* table, const uint8_t* ax, const uint8_t* ay, const uint8_t* bx, const uint8_t* by,
+                        const uint8_t* cx, const uint8_t* cy, const uint8_t* proof, const uint8_t* msg, size_t count, uint8_t* err,
+                        uint8_t* valid) {
+    hipLaunchKernelGGL((k_dleq_verify<0>), grid1(count), dim3(BS), 0, c->stream, table, ax, ay, bx, by, cx, cy, proof, msg, valid, count, err,
+                       c->d_counter);
+}
+#endif   // P2E_HAS(1)
+
+#if P2E_HAS(0)
+// BUFFER OVERLAP passes every exact in-place pair of an output and a per-lane input; these calls list their forms (x on x, y on
+// y), and an output exactly on any OTHER per-lane input is refused here, with the same text.  count == 0 checks nothing.
+struct NamedPtr {
+    const void* p;
+    const char* name;
+};
+static bool unlisted_in_place(size_t count, const void* out, const char* out_name, std::initializer_list<NamedPtr> inputs) {
+    if (count == 0 || !out) return false;
+    for (const NamedPtr& in : inputs)
+        if (in.p == out) {
+            set_error(std::string("overlap: ") + in.name + " and " + out_name + " share bytes (not an in-place form of this call)");
+            return true;
+        }
+    return false;
+}
+// (the batch size of these three calls is `count`: see include/p2e.h)
+// b32 is Shared: of the scalars only a32 may carry the output (outx32 = a32, as p2e_point_mul_batch's outx32 = k32)
+extern "C" long p2e_point_lincomb2_batch(p2e_ctx* c, int curve, unsigned plan, const uint8_t* a32, const uint8_t* b32, const uint8_t* px32,
+                                         const uint8_t* py32, const uint8_t* qx32, const uint8_t* qy32, uint8_t* outx32, uint8_t* outy32,
+                                         size_t count, uint8_t* err) {
+    const Args args = {ARG_IN(a32, 32, count),  ARG_SHARED(b32, 32, count), ARG_IN(px32, 32, count),    ARG_IN(py32, 32, count),
+                       ARG_IN(qx32, 32, count), ARG_IN(qy32, 32, count),    ARG_OUT(outx32, 32, count), ARG_OUT(outy32, 32, count),
+                       ARG_OUT(err, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    int chosen = 0;
+    if (int rc = point_mul_prepare(curve, plan, count, &chosen)) return rc;
+    if (bad_overlap(count, args) || unlisted_in_place(count, outx32, "outx32", {{py32, "py32"}, {qy32, "qy32"}}) ||
+        unlisted_in_place(count, outy32, "outy32", {{a32, "a32"}, {px32, "px32"}, {qx32, "qx32"}}) || bad_ctx(c))
+        return P2E_E_INVALID;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    if (curve == P2E_CURVE_P256)
+        launch_point_lincomb2<P256>(c, chosen, a32, b32, px32, py32, qx32, qy32, outx32, outy32, count, err);
+    else
+        launch_point_lincomb2<Secp256k1>(c, chosen, a32, b32, px32, py32, qx32, qy32, outx32, outy32, count, err);
+    return S.end();
+}
+// the one in-place form: (cx32, cy32) = (bx32, by32); the secret, the randomness and the message are Shared (never in place)
+extern "C" long p2e_dleq_prove_batch(p2e_ctx* c, const uint8_t* a_sk32, const uint8_t* bx32, const uint8_t* by32, const uint8_t* aux_rand32,
+                                     const uint8_t* msg32, uint8_t* proof64, uint8_t* cx32, uint8_t* cy32, size_t count, uint8_t* err) {
+    const bool want_c = cx32 != nullptr || cy32 != nullptr;
+    const Args args = {ARG_SHARED(a_sk32, 32, count),
+                       ARG_IN(bx32, 32, count),
+                       ARG_IN(by32, 32, count),
+                       ARG_SHARED(aux_rand32, 32, count),
+                       P2E_ARG(msg32, 32, count, Shared, false),
+                       ARG_OUT(proof64, 64, count),
+                       ARG_OUT_IF(want_c, cx32, 32, count),
+                       ARG_OUT_IF(want_c, cy32, 32, count),
+                       ARG_OUT(err, 1, count)};
+    if (missing(args, want_c ? "the share (cx32 and cy32 go together)" : nullptr)) return P2E_E_INVALID;
+    if (unlisted_in_place(count, cx32, "cx32", {{by32, "by32"}}) || unlisted_in_place(count, cy32, "cy32", {{bx32, "bx32"}})) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_dleq_prove(c, table, a_sk32, bx32, by32, aux_rand32, msg32, proof64, cx32, cy32, count, err);
+    return S.end();
+}
+// no in-place form: every input is Shared
+extern "C" long p2e_dleq_verify_batch(p2e_ctx* c, const uint8_t* ax32, const uint8_t* ay32, const uint8_t* bx32, const uint8_t* by32,
+                                      const uint8_t* cx32, const uint8_t* cy32, const uint8_t* proof64, const uint8_t* msg32, size_t count,
+                                      uint8_t* err, uint8_t* valid) {
+    const Args args = {ARG_SHARED(ax32, 32, count),
+                       ARG_SHARED(ay32, 32, count),
+                       ARG_SHARED(bx32, 32, count),
+                       ARG_SHARED(by32, 32, count),
+                       ARG_SHARED(cx32, 32, count),
+                       ARG_SHARED(cy32, 32, count),
+                       ARG_SHARED(proof64, 64, count),
+                       P2E_ARG(msg32, 32, count, Shared, false),
+                       ARG_OUT(err, 1, count),
+                       ARG_OUT(valid, 1, count)};
+    if (missing(args)) return P2E_E_INVALID;
+    const Aff* table = nullptr;
+    if (int rc = schnorr_prepare(c, count, &table, args)) return rc;
+    if (count == 0) return 0;
+    Staged S(c);
+    if (long rc = S.begin(args)) return rc;
+    launch_dleq_verify(c, table, ax32, ay32, bx32, by32, cx32, cy32, proof64, msg32, count, err, valid);
     return S.end();
 }
 #endif   // P2E_HAS(0)

@@ -42,6 +42,16 @@
 // a G + b P: sign.hpp's sign_base_mul<CV, SIGN_PLAN_LANE> for a G, the chosen walk for b P, then ONE complete addition
 // (either operand may be empty: a = 0, b = 0, P neutral; a G = b P is doubled; a G = -b P is the neutral element).
 // P + Q: one complete mixed addition of the two affine points, then one inversion.
+//
+// a P + b Q (p2e_point_lincomb2_batch): ONE joint (Straus) walk with one accumulator, one-bit digits over the AFFINE operands.
+//   PLAIN  the 128 two-bit windows of a and b together, each window two steps of (double, + P if a's bit, + Q if b's bit).
+//   GLV    the four 128-bit halves of the two decompositions together, 128 doublings in all: per step + (+-P), + (+-lambda P),
+//          + (+-Q), + (+-lambda Q).  lambda (x, y) = (beta x, y) is one multiplication per operand before the loop.
+// Every addition is mixed (Z2 = 1) and COMPLETE (msm_add): with two points the size arguments carry over even less than above
+// -- Q may be +-P or +-lambda P, so entries of the two operands coincide or cancel in the middle of the walk.  Nothing but P, Q,
+// beta x_P, beta x_Q and the accumulator lives across the loop (174 / 210 VGPRs on secp256k1, two waves per SIMD; two-bit digits
+// over two Jacobian tables need 256 + 57 and one wave: NEGATIVE_RESULTS.md section 4).  A wave runs an addition when any lane
+// has the bit, so per wave this is 4 x 128 mixed additions under GLV (MEASUREMENTS.md section 24).
 // secp256k1 computes on lazy 29-bit limbs, P-256 on canonical words (RecField<CV>); PLAIN, a G + b P and P + Q are one
 // text for both.
 #pragma once
@@ -147,6 +157,93 @@ P2E_HD SignSum<CV> point_var_mul(const Aff& P, bool neutral, const U256& k) {
         return recover_var_mul<CV>(P, k);
 }
 
+// ---- a P + b Q: one joint (Straus) walk, one accumulator (see the header) --------------------------------------------------
+// the operand `base` (Z = 1) with abscissa x (its own, or beta times it) if `take`, its opposite if `neg`
+template <class CV>
+P2E_HD SignSum<CV> joint_entry(const typename SignArith<CV>::Pt& base, const typename RecField<CV>::E& x, bool take, bool neg) {
+    typedef SignArith<CV> A;
+    typedef RecField<CV> FA;
+    SignSum<CV> e;
+    e.p = base;
+    e.p.X = x;
+    e.have = take;
+    typename A::Pt m = e.p;
+    m.Y = FA::sub(FA::from(u256_zero()), base.Y);
+    e.p = A::select(neg, m, e.p);   // (a register select, as everywhere: no private memory)
+    return e;
+}
+// the top bit of the WORDS-word value d, which moves up one bit
+template <int WORDS>
+P2E_HD u32 joint_next_bit(u32 (&d)[WORDS]) {
+    const u32 bit = d[WORDS - 1] >> 31;
+    P2E_UNROLL
+    for (int j = WORDS - 1; j > 0; j--) d[j] = (d[j] << 1) | (d[j - 1] >> 31);
+    d[0] <<= 1;
+    return bit;
+}
+// PLAIN: 128 windows of two bits over a and b, each window two steps of (double, + P if a's bit, + Q if b's bit)
+template <class CV>
+P2E_HD SignSum<CV> point_joint_plain(const Aff& P, bool p_have, const U256& a, const Aff& Q, bool q_have, const U256& b) {
+    typedef SignArith<CV> A;
+    const typename A::Pt tp = A::from_aff(P), tq = A::from_aff(Q);
+    u32 da[8], db[8];
+    P2E_UNROLL
+    for (int j = 0; j < 8; j++) da[j] = a.w[j], db[j] = b.w[j];
+    SignSum<CV> s = msm_neutral<CV>();
+    for (int t = 0; t < 2 * RECOVER_WINDOWS; t++) {
+        const u32 ba = joint_next_bit<8>(da), bb = joint_next_bit<8>(db);
+        s = msm_dbl<CV>(s);
+        s = msm_add<CV, true>(s, joint_entry<CV>(tp, tp.X, p_have && ba != 0, false));
+        s = msm_add<CV, true>(s, joint_entry<CV>(tq, tq.X, q_have && bb != 0, false));
+    }
+    return s;
+}
+P2E_HD void glv_check_halves(const GlvOut& g) {
+#if defined(P2E_F29_BOUNDS) && !defined(__HIP_DEVICE_COMPILE__)
+    if (g.k1.w[4] | g.k1.w[5] | g.k1.w[6] | g.k1.w[7] | g.k2.w[4] | g.k2.w[5] | g.k2.w[6] | g.k2.w[7]) {
+        fprintf(stderr, "point_joint_glv: |k1| or |k2| >= 2^128\n");
+        abort();
+    }
+#else
+    (void)g;
+#endif
+}
+// GLV (secp256k1): a = +-a1 +- a2 lambda, b = +-b1 +- b2 lambda; the four halves (< 2^128: the header) walk together, 128
+// doublings in all, per step + (+-P), + (+-lambda P), + (+-Q), + (+-lambda Q) for the four bits
+template <class CV>
+P2E_HD SignSum<CV> point_joint_glv(const Aff& P, bool p_have, const U256& a, const Aff& Q, bool q_have, const U256& b) {
+    typedef SignArith<CV> A;
+    typedef RecField<CV> FA;
+    const GlvOut ga = glv_decompose(a), gb = glv_decompose(b);
+    glv_check_halves(ga);
+    glv_check_halves(gb);
+    const typename A::Pt tp = A::from_aff(P), tq = A::from_aff(Q);
+    const typename FA::E beta = FA::from(glv_beta());
+    const typename FA::E lpx = FA::mul(tp.X, beta), lqx = FA::mul(tq.X, beta);   // lambda (x, y) = (beta x, y)
+    const bool na1 = ga.n1 != 0, na2 = ga.n2 != 0, nb1 = gb.n1 != 0, nb2 = gb.n2 != 0;
+    u32 a1[4], a2[4], b1[4], b2[4];
+    P2E_UNROLL
+    for (int j = 0; j < 4; j++) a1[j] = ga.k1.w[j], a2[j] = ga.k2.w[j], b1[j] = gb.k1.w[j], b2[j] = gb.k2.w[j];
+    SignSum<CV> s = msm_neutral<CV>();
+    for (int t = 0; t < 2 * GLV_WINDOWS; t++) {
+        const u32 x1 = joint_next_bit<4>(a1), x2 = joint_next_bit<4>(a2), y1 = joint_next_bit<4>(b1), y2 = joint_next_bit<4>(b2);
+        s = msm_dbl<CV>(s);
+        s = msm_add<CV, true>(s, joint_entry<CV>(tp, tp.X, p_have && x1 != 0, na1));
+        s = msm_add<CV, true>(s, joint_entry<CV>(tp, lpx, p_have && x2 != 0, na2));
+        s = msm_add<CV, true>(s, joint_entry<CV>(tq, tq.X, q_have && y1 != 0, nb1));
+        s = msm_add<CV, true>(s, joint_entry<CV>(tq, lqx, q_have && y2 != 0, nb2));
+    }
+    return s;
+}
+// a P + b Q for checked operands and a, b < n; a neutral operand (`have` false) and a zero scalar add nothing
+template <class CV, int PLAN>
+P2E_HD SignSum<CV> point_joint_mul(const Aff& P, bool p_have, const U256& a, const Aff& Q, bool q_have, const U256& b) {
+    if constexpr (PLAN == MUL_PLAN_GLV)
+        return point_joint_glv<CV>(P, p_have, a, Q, q_have, b);
+    else
+        return point_joint_plain<CV>(P, p_have, a, Q, q_have, b);
+}
+
 // affine coordinates of `s` to element i, zeros where `e` is set or the sum is the neutral element; returns the code
 template <class CV>
 P2E_HD uint8_t point_finish(uint8_t e, const SignSum<CV>& s, uint8_t* outx32, uint8_t* outy32, size_t i) {
@@ -213,8 +310,38 @@ P2E_HD uint8_t body_point_add(const uint8_t* px32, const uint8_t* py32, const ui
     return point_finish<CV>(e, s, outx32, outy32, i);
 }
 
+// out_i = a_i P_i + b_i Q_i
+// (include/p2e.h BUFFER OVERLAP relies on this body reading every input of element i before its first store)
+template <class CV, int PLAN>
+P2E_HD uint8_t body_point_lincomb2(const uint8_t* a32, const uint8_t* b32, const uint8_t* px32, const uint8_t* py32, const uint8_t* qx32,
+                                   const uint8_t* qy32, uint8_t* outx32, uint8_t* outy32, size_t i) {
+    Aff P, Q;
+    P.x = load_packed(px32, i), P.y = load_packed(py32, i);
+    Q.x = load_packed(qx32, i), Q.y = load_packed(qy32, i);
+    const U256 a = sign_scalar<CV>(a32, i), b = sign_scalar<CV>(b32, i);
+    bool p_neutral, q_neutral;
+    uint8_t e = point_check<CV>(P.x, P.y, p_neutral);
+    const uint8_t eq = point_check<CV>(Q.x, Q.y, q_neutral);
+    if (!e) e = eq;
+    SignSum<CV> s = msm_neutral<CV>();
+    if (!e) s = point_joint_mul<CV, PLAN>(P, !p_neutral, a, Q, !q_neutral, b);
+    return point_finish<CV>(e, s, outx32, outy32, i);
+}
+
 #if defined(__HIPCC__)
 // thread g owns element g
+template <class CV, int PLAN>
+__global__ __launch_bounds__(256) void k_point_lincomb2(const uint8_t* a32, const uint8_t* b32, const uint8_t* px32, const uint8_t* py32,
+                                                        const uint8_t* qx32, const uint8_t* qy32, uint8_t* outx32, uint8_t* outy32,
+                                                        size_t count, uint8_t* err, unsigned long long* counter) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    uint8_t e = 0;
+    if (i < count) {
+        e = body_point_lincomb2<CV, PLAN>(a32, b32, px32, py32, qx32, qy32, outx32, outy32, i);
+        err[i] = e;
+    }
+    sign_count_err(e, counter);
+}
 template <class CV, int PLAN>
 __global__ __launch_bounds__(256) void k_point_mul(const uint8_t* k32, const uint8_t* px32, const uint8_t* py32, uint8_t* outx32,
                                                    uint8_t* outy32, size_t n, uint8_t* err, unsigned long long* counter) {

@@ -350,6 +350,16 @@ extern "C" {
         outputs32: *const u8, out_offsets: *const u64, max_hits: usize, n_hits: *mut u8, hit_output: *mut u32, hit_label: *mut u8,
         hit_tweak32: *mut u8, count: usize, err: *mut u8) -> i64;
 
+    // ---- a P + b Q per element (either curve) and DLEQ proofs (BIP-374) on secp256k1: points and a_sk32 little-endian,
+    // aux_rand32 / msg32 byte strings, proof64 = bytes32(e) || bytes32(s) big-endian; msg32, cx32 / cy32 nullable
+    pub fn p2e_point_lincomb2_batch(ctx: *mut P2eCtx, curve: i32, plan: u32, a32: *const u8, b32: *const u8, px32: *const u8,
+        py32: *const u8, qx32: *const u8, qy32: *const u8, outx32: *mut u8, outy32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_dleq_prove_batch(ctx: *mut P2eCtx, a_sk32: *const u8, bx32: *const u8, by32: *const u8, aux_rand32: *const u8,
+        msg32: *const u8, proof64: *mut u8, cx32: *mut u8, cy32: *mut u8, count: usize, err: *mut u8) -> i64;
+    pub fn p2e_dleq_verify_batch(ctx: *mut P2eCtx, ax32: *const u8, ay32: *const u8, bx32: *const u8, by32: *const u8,
+        cx32: *const u8, cy32: *const u8, proof64: *const u8, msg32: *const u8, count: usize, err: *mut u8,
+        valid: *mut u8) -> i64;
+
     // ---- MuSig2 (BIP-327) on secp256k1: points, secret keys and nonces little-endian 32-byte values (pubnonce128 / aggnonce128 =
     // x(R_1) || y(R_1) || x(R_2) || y(R_2), secnonce64 = k_1 || k_2), tweaks, messages, partial signatures, agg_pk32 and sig64 the
     // standard's big-endian strings; keyagg192 and session128 are the records of include/p2e.h; key_offsets (count + 1) counts
